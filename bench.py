@@ -11,6 +11,8 @@ every call, select_kernel.cpp:371-378) with inputs already resident in HBM.
       127.0.0.1) BEFORE it touches a GPU and exits with their status -- the reference's multi-card model is likewise N
       processes, one per device (benchmark_msprof/main.cpp:24-26, framework/benchmark/benchmark.py:249-253).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...     (what the driver runs)
+  python bench.py ... --dump-outputs DIR
+      also writes what the last timed step returned (DIR/out.npy, float32) so that two builds can be compared output for output.
 
 N > 1: the dense GEMM does not shard ("replicas only"): every rank runs the same
 problem, `value` = N x per-replica work / max-over-ranks time (weak scaling).  The path that does shard --
@@ -99,7 +101,46 @@ def parse_args(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="no GPU: gloo backend, CPU tensors and a numpy stand-in for the step -- exercises the launcher, the "
                          "rendezvous, the barrier / max-over-ranks timing and the JSON contract (tests/test_bench_launcher.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; rank 0): out.npy = the bf16 output matrix, whole when it fits in 32 MiB as float32, else a "
+                         "fixed seeded sample of its rows in ascending order.  The inputs are seeded, so two builds run with the "
+                         "same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs: float32 bytes per output; a larger output is dumped as a seeded row sample
+
+
+def dump_rows(out):
+    """`out` (2-D torch tensor or numpy array) as the float32 array --dump-outputs writes: every row when they fit DUMP_BYTES,
+    else a fixed seeded sample of rows in ascending order -- the same rows in every run of the same shape."""
+    import numpy as np
+    m, n = out.shape
+    keep = max(1, DUMP_BYTES // (4 * n))
+    if m > keep:
+        idx = np.sort(np.random.default_rng(0).choice(m, keep, replace=False))
+        if isinstance(out, np.ndarray):
+            out = out[idx]
+        else:
+            import torch
+            out = out.index_select(0, torch.from_numpy(idx).to(out.device))
+    if not isinstance(out, np.ndarray):
+        out = out.float().cpu().numpy()
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def dump_outputs(dirpath, arrays: dict) -> dict:
+    """Write each array as DIR/<name>.npy; returns {name: shape} for the record."""
+    import numpy as np
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(d / f"{name}.npy", arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 def launch_ranks(args) -> int:
@@ -796,10 +837,11 @@ def main():
     if args.stub:
         import numpy as np
         xs = np.ones((64, 64), np.float32)
+        out = np.empty((64, 64), np.float32)
         t = None
 
         def step():
-            np.matmul(xs, xs)
+            np.matmul(xs, xs, out=out)
     else:
         import deepgemm_ascend_amd as dga_mod
         dga = dga_mod
@@ -847,6 +889,8 @@ def main():
         dist.all_gather(gathered, torch.tensor([kernel_us], device=dev, dtype=torch.float64))
         per_rank_us = [round(float(x), 3) for x in gathered]
         kernel_us = float(tt[1])
+    # what the last timed step handed its caller, taken before any later leg reuses `out`
+    dumped = dump_outputs(args.dump_outputs, {"out": dump_rows(out)}) if args.dump_outputs and rank == 0 else None
 
     # what the ranks saw: so that the first real multi-GPU run of this line can be read without the logs
     ranks_seen = None
@@ -870,6 +914,8 @@ def main():
                    "backend": backend, "stub": bool(args.stub)},
         "per_rank_kernel_us": per_rank_us,
     }
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
     if ranks_seen is not None:
         try:
             ver = torch.cuda.nccl.version()

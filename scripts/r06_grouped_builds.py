@@ -1,5 +1,5 @@
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 import deepgemm_ascend_amd as dga
 G, MMAX, N, K = 256, 128, 2048, 7168

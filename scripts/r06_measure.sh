@@ -4,7 +4,7 @@
 # together with the runtime / sys trace domains), FETCH_SIZE and WRITE_SIZE in their own passes (TCC slots).
 # The headline policy is the operator's default, bf16_exact (in contract); "fast" = the opt-in fp8-instruction policy.
 set -eo pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/r06
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 import deepgemm_ascend_amd as dga
 for m, n, k in ((1279, 5003, 7680), (2048, 7168, 4096), (3511, 6151, 8192)):

@@ -11,6 +11,8 @@ Fixtures (SURVEY.md 8c "Golden vectors to commit"):
   scaled_64x256x400.npz   (iii) non-unit scales and a K tail block; expected from the oracle (parity unpinned)
   grouped_g4_m16.npz      (iv)  G=4, M_max=16, masked_m=[0,1,7,16]; expected from the oracle (parity unpinned)
   config_vectors.json     (v)   28-int Config tuples from the reference header itself
+  config_random_vectors.json (v') the same for 60 seeded random (m, n, k, knobs) cases
+                                (`... make_golden.py config_random` writes this one alone)
   op_tiling_vectors.json  (vi)  (m1,n1,k1,kernelSerial,blockDim,padding) from the reference's Python mirror
                                 (coreNum 20) and the C++ probes recorded in SURVEY.md 8(a7) (coreNum 24)
   ref_gen_golden_96x160x320.npz (vii) the files the reference's OWN generator writes: deep_gemm_ascend/scripts/gen_golden.py
@@ -81,6 +83,24 @@ def configs():
            "best": [{"args": list(a), "config": O.ref_config("best", *a)} for a in best],
            "bench": [{"args": list(a), "config": O.ref_config("bench", *a)} for a in bench]}
     (HERE / "config_vectors.json").write_text(json.dumps(out, indent=0))
+
+
+def config_random():
+    """The 60 seeded random cases of tests/test_config.py's comparison with the reference binary, with the binary's answers."""
+    import random
+    rnd = random.Random(7)
+    cases = []
+    for _ in range(60):
+        m, n, k = rnd.randint(1, 9000), rnd.randint(1, 9000), rnd.randint(1, 20000)
+        batch = rnd.randint(1, 4)
+        knobs = [rnd.randint(1, 6), rnd.randint(1, 6), rnd.randint(1, 16), rnd.randint(1, 16)]
+        db = rnd.randint(1, 12)
+        knobs += [db * rnd.randint(1, 4), db]
+        cases.append({"batch": batch, "mnk": [m, n, k], "knobs": knobs,
+                      "best": O.ref_config("best", 1, m, n, k), "bench": O.ref_config("bench", m, n, k, *knobs)})
+    (HERE / "config_random_vectors.json").write_text(json.dumps(
+        {"order": "struct Config declaration order, get_best_config.hpp:12-31; best = get_best_config(1, m, n, k), "
+                  "bench = get_bench_config(m, n, k, *knobs)", "cases": cases}, indent=0))
 
 
 def op_tiling():
@@ -241,7 +261,10 @@ if __name__ == "__main__":
         ref_gen_golden()
     elif sys.argv[1:] == ["ref_gen_golden_e4m3"]:
         ref_gen_golden_e4m3()
+    elif sys.argv[1:] == ["config_random"]:
+        config_random()
     else:
         O.build()
-        table(); c1(); scaled(); grouped(); configs(); op_tiling(); ref_gen_golden(); ref_gen_golden_e4m3(); select_strategy()
+        table(); c1(); scaled(); grouped(); configs(); config_random(); op_tiling(); ref_gen_golden(); ref_gen_golden_e4m3()
+        select_strategy()
     print("fixtures written to", HERE)

@@ -100,3 +100,35 @@ def test_compact_of_a_full_size_record_is_under_4_kb_and_keeps_the_contract():
     assert c["config"]["workload"].startswith("dense_4096") and "model" not in c["config"]
     assert c["in_contract"]["policy"] == "bf16_exact" and c["grouped"]["roofline"]["bound"] == "hbm"
     assert c["value"] == full["value"] and c["roofline"]["frac"] == full["roofline"]["frac"]   # numbers copied, never recomputed
+
+
+# ---- --dump-outputs: what the last timed step returned, for comparing two builds output for output
+
+def test_dump_outputs_writes_the_last_step_as_float32(tmp_path):
+    import numpy as np
+    dump = tmp_path / "dump"
+    r = _run(["--stub", "--steps", "3", "--warmup", "1", "--detail-out", str(tmp_path / "d.json"), "--dump-outputs", str(dump)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(p.name for p in dump.iterdir()) == ["out.npy"]
+    out = np.load(dump / "out.npy")
+    assert out.dtype == np.float32 and out.shape == (64, 64) and (out == 64.0).all()   # ones(64, 64) @ ones(64, 64)
+    full = json.loads((tmp_path / "d.json").read_text())
+    assert full["dumped_outputs"]["arrays"] == {"out": [64, 64]}
+
+
+def test_dump_rows_samples_a_large_output_the_same_way_every_time():
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    big = np.arange(4096 * 4096, dtype=np.float32).reshape(4096, 4096)
+    s1, s2 = bench.dump_rows(big), bench.dump_rows(big.copy())
+    assert s1.nbytes <= bench.DUMP_BYTES and s1.shape == (2048, 4096) and np.array_equal(s1, s2)
+    rows = s1[:, 0] / 4096
+    assert (np.diff(rows) > 0).all() and np.array_equal(s1, big[rows.astype(np.int64)])
+    small = np.ones((4096, 2048), np.float32)
+    assert bench.dump_rows(small).shape == (4096, 2048)     # fits: dumped whole
+
+
+def test_steps_below_one_is_an_error():
+    r = _run(["--stub", "--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr

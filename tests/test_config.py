@@ -27,19 +27,22 @@ def test_survey_probe_values(dga):
 
 
 def test_against_reference_binary_when_present(dga, oracle):
-    import random
+    """60 seeded random cases against the reference binary's answers (committed: config_random_vectors.json, written by
+    make_golden.py config_random) and, where oracle/_ref/ref_config is built, against the binary itself."""
+    cases = json.loads((G / "config_random_vectors.json").read_text())["cases"]
+    assert len(cases) == 60
     try:
         oracle.ref_config("best", 1, 16, 16, 16)
+        have_binary = True
     except FileNotFoundError:
-        pytest.skip("oracle/_ref/ref_config not built (reference tree absent)")
-    rnd = random.Random(7)
-    for _ in range(60):
-        m, n, k = rnd.randint(1, 9000), rnd.randint(1, 9000), rnd.randint(1, 20000)
-        assert dga.get_best_config(rnd.randint(1, 4), m, n, k)[2:] == oracle.ref_config("best", 1, m, n, k)[2:]
-        knobs = [rnd.randint(1, 6), rnd.randint(1, 6), rnd.randint(1, 16), rnd.randint(1, 16)]
-        db = rnd.randint(1, 12)
-        knobs += [db * rnd.randint(1, 4), db]
-        assert dga.get_bench_config(m, n, k, *knobs) == oracle.ref_config("bench", m, n, k, *knobs)
+        have_binary = False
+    for c in cases:
+        m, n, k = c["mnk"]
+        assert dga.get_best_config(c["batch"], m, n, k)[2:] == c["best"][2:], c
+        assert dga.get_bench_config(m, n, k, *c["knobs"]) == c["bench"], c
+        if have_binary:
+            assert oracle.ref_config("best", 1, m, n, k) == c["best"], c
+            assert oracle.ref_config("bench", m, n, k, *c["knobs"]) == c["bench"], c
 
 
 def test_param_orders(dga):

@@ -28,6 +28,7 @@ def test_host_entry_points_under_asan_and_ubsan(tmp_path):
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, DGA_SAN_TMP=str(tmp_path), UBSAN_OPTIONS="print_stacktrace=1", ASAN_OPTIONS="detect_leaks=1",
+               LSAN_OPTIONS="suppressions=" + str(ROOT / "tests" / "sanitize" / "lsan.supp"),   # the ROCm runtime's own leaks
                DGA_SAN_PREDICTOR=str(ROOT / "deepgemm_ascend_amd" / "tuned" / "predictor_mi355x.txt"))
     env.pop("DGA_CACHE_FILE_PATH", None); env.pop("CACHE_FILE_PATH", None)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=900, env=env)
