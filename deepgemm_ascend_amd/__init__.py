@@ -14,6 +14,9 @@ from .api import (  # noqa: F401
     copy_rows,
     copy_rows2,
     gemm_fp8_fp8_bf16_nt,
+    gemm_fp8_fp8_fp32_nt,
+    tiling_check_fp32_out,
+    tiling_fp32_out,
     gemm_fp8_loop_clock,
     get_bench_config,
     get_best_config,

@@ -178,6 +178,10 @@ SIGNATURES = {
     "dga_sharded_events_destroy": (c_int, [c_int, POINTER(c_void_p)]),
     "dga_mfma_ceiling": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "dga_tiling_check": (c_int, [POINTER(Tiling)]),
+    "dga_tiling_check_fp32_out": (c_int, [POINTER(Tiling)]),
+    "dga_tiling_fp32_out": (c_int, [POINTER(Problem), POINTER(Tiling)]),
+    "dga_gemm_fp8_fp8_fp32_nt": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                         c_int, c_int, POINTER(Tiling), c_void_p, c_size_t, c_void_p]),
     "dga_default_policy": (c_int, [ctypes.c_char_p, c_int]),
     "dga_status_string": (c_char_p, [c_int]),
     "dga_last_hip_error": (c_int, []),

@@ -422,6 +422,35 @@ def bench_params_fill(m: int, n: int, k: int, params6: Sequence[int]) -> list:
 
 # ----------------------------------------------------------------------------- the hot path
 
+def _dense_fp8_operands(a, sfa, b, sfb, out, out_dtype, out_name: str):
+    """The dense fp8 GEMM's argument checks (shapes, dtypes, strides); (m, n, k, lda, ldb)."""
+    _fp8_bytes(a); _fp8_bytes(b)
+    if a.dim() != 2 or b.dim() != 2 or out.dim() != 2:
+        _fail("rank must be 2")
+    m, k = a.shape
+    n, k2 = b.shape
+    if k != k2:
+        _fail("self dimk is not equal with mat2 dimk")
+    if out.shape[0] != m or out.shape[1] != n:
+        _fail(f"out must be [{m},{n}]")
+    if out.dtype != out_dtype:
+        _fail(f"out must be {out_name}")
+    kb, nb = (k + 127) // 128, (n + 127) // 128
+    if sfa.dtype != torch.float32 or sfb.dtype != torch.float32:
+        _fail("scales must be float32")
+    if sfa.dim() != 2 or sfa.shape[0] != m or sfa.shape[1] != kb:
+        _fail(f"sfa must be [{m},{kb}]")
+    if sfb.dim() != 2 or sfb.shape[0] != nb or sfb.shape[1] != kb:
+        _fail(f"sfb must be [{nb},{kb}]")
+    if not (sfa.is_contiguous() and sfb.is_contiguous() and out.is_contiguous()):
+        _fail("scales and out must be contiguous")
+    if (k > 1 and (a.stride(1) != 1 or b.stride(1) != 1)) or (m > 1 and a.stride(0) < k) or (n > 1 and b.stride(0) < k):
+        _fail("operands must be row-major with unit inner stride (row-strided views are accepted)")
+    lda = a.stride(0) if m > 1 else k
+    ldb = b.stride(0) if n > 1 else k
+    return m, n, k, lda, ldb
+
+
 def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torch.Tensor, torch.Tensor],
                          out: torch.Tensor, tiling_: Optional[Tiling] = None, sync: bool = False,
                          strict: bool = False, policy: Optional[str] = None,
@@ -444,30 +473,7 @@ def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
     pass sync=True for that behaviour)."""
     a, sfa = lhs
     b, sfb = rhs
-    _fp8_bytes(a); _fp8_bytes(b)
-    if a.dim() != 2 or b.dim() != 2 or out.dim() != 2:
-        _fail("rank must be 2")
-    m, k = a.shape
-    n, k2 = b.shape
-    if k != k2:
-        _fail("self dimk is not equal with mat2 dimk")
-    if out.shape[0] != m or out.shape[1] != n:
-        _fail(f"out must be [{m},{n}]")
-    if out.dtype != torch.bfloat16:
-        _fail("out must be bfloat16")
-    kb, nb = (k + 127) // 128, (n + 127) // 128
-    if sfa.dtype != torch.float32 or sfb.dtype != torch.float32:
-        _fail("scales must be float32")
-    if sfa.dim() != 2 or sfa.shape[0] != m or sfa.shape[1] != kb:
-        _fail(f"sfa must be [{m},{kb}]")
-    if sfb.dim() != 2 or sfb.shape[0] != nb or sfb.shape[1] != kb:
-        _fail(f"sfb must be [{nb},{kb}]")
-    if not (sfa.is_contiguous() and sfb.is_contiguous() and out.is_contiguous()):
-        _fail("scales and out must be contiguous")
-    if (k > 1 and (a.stride(1) != 1 or b.stride(1) != 1)) or (m > 1 and a.stride(0) < k) or (n > 1 and b.stride(0) < k):
-        _fail("operands must be row-major with unit inner stride (row-strided views are accepted)")
-    lda = a.stride(0) if m > 1 else k
-    ldb = b.stride(0) if n > 1 else k
+    m, n, k, lda, ldb = _dense_fp8_operands(a, sfa, b, sfb, out, torch.bfloat16, "bfloat16")
     strided = lda != k or ldb != k
     if zero_padded is None:
         zero_padded = (bool(getattr(a, "_dga_zero_padded", False)), bool(getattr(b, "_dga_zero_padded", False)))
@@ -489,6 +495,83 @@ def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
                                                      out.data_ptr(), m, n, k, ctypes.byref(tiling_), ws_ptr, ws_bytes, stream)
         if rc:
             _lib.check(rc, "gemm_fp8_fp8_bf16_nt")
+        if sync:
+            torch.cuda.current_stream(out.device).synchronize()
+
+
+def tiling_fp32_out(m: int, n: int, k: int) -> Tiling:
+    """dga_tiling_fp32_out: the default tiling of gemm_fp8_fp8_fp32_nt -- the bf16-exact pick, with names of builds that have no fp32
+    epilogue mapped onto the in-register build of the same tile; the strict tag under $DGA_DEFAULT_POLICY=strict."""
+    t = Tiling()
+    p = _problem(m, n, k, 1, 0)
+    _lib.check(_lib.lib().dga_tiling_fp32_out(ctypes.byref(p), ctypes.byref(t)), "tiling_fp32_out")
+    return t
+
+
+def tiling_check_fp32_out(t: Tiling) -> int:
+    """dga_tiling_check_fp32_out: 0 if gemm_fp8_fp8_fp32_nt takes this tiling, else the status it returns before any launch."""
+    return int(_lib.lib().dga_tiling_check_fp32_out(ctypes.byref(t)))
+
+
+_FP32_OUT_POLICIES = ("bf16_exact", "strict")   # the arithmetic policies with an fp32 epilogue
+
+
+def gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torch.Tensor, torch.Tensor], out: torch.Tensor,
+                         c: Optional[torch.Tensor] = None, tiling_: Optional[Tiling] = None, sync: bool = False,
+                         strict: bool = False, policy: Optional[str] = None,
+                         zero_padded: Optional[Tuple[bool, bool]] = None) -> None:
+    """out[M,N] (fp32, written in place) = c[M,N] (fp32, optional) + (A[M,K] fp8, sfa) x (B[N,K] fp8, sfb)^T -- the fp32 result the
+    reference's run_mmad_rtc writes (python_api.cpp:18), with upstream DeepGEMM's fp32-output accumulation.
+
+    Operands, scales, row-strided views and zero_padded exactly as in gemm_fp8_fp8_bf16_nt.  out and c: contiguous [M,N] float32 on
+    the operands' device; c may be out itself (in-place accumulation), a c that partially overlaps out is refused.  c is added once
+    to the finished product, out = fl(acc + c); c=None writes every element of out without reading it.
+
+    Arithmetic: "bf16_exact" (the default: the accumulator gemm_fp8_fp8_bf16_nt rounds, bit for bit) or "strict" (strict=True: the
+    oracle's fp32 result, bit for bit).  "fast", "auto" and the _ue8m0 policies have no fp32 epilogue and raise; a process default
+    ($DGA_DEFAULT_POLICY) of "strict" gives strict, any other gives bf16_exact."""
+    a, sfa = lhs
+    b, sfb = rhs
+    _require(policy is None or policy in _FP32_OUT_POLICIES, f"gemm_fp8_fp8_fp32_nt: policy must be one of {list(_FP32_OUT_POLICIES)}")
+    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r" % (policy,))
+    m, n, k, lda, ldb = _dense_fp8_operands(a, sfa, b, sfb, out, torch.float32, "float32")
+    if k == 0:
+        lda = ldb = 0   # (a zero-width view has no meaningful row stride: nothing is read, out = c)
+    if c is not None:
+        if c.dtype != torch.float32:
+            _fail("c must be float32")
+        if c.dim() != 2 or c.shape[0] != m or c.shape[1] != n:
+            _fail(f"c must be [{m},{n}]")
+        if not c.is_contiguous():
+            _fail("c must be contiguous")
+        if c.data_ptr() != out.data_ptr() and c.device == out.device and m * n > 0:
+            lo, hi = c.data_ptr(), out.data_ptr()
+            if lo < hi + 4 * m * n and hi < lo + 4 * m * n:
+                _fail("c must be out itself or not overlap it")
+    strided = lda != k or ldb != k
+    if zero_padded is None:
+        zero_padded = (bool(getattr(a, "_dga_zero_padded", False)), bool(getattr(b, "_dga_zero_padded", False)))
+    with _device_guard(a, b, sfa, sfb, out, *(() if c is None else (c,))):
+        index = out.device.index
+        if tiling_ is None:
+            key = ("fp32_out", index, m, n, k, strict, policy)   # (the output kind is part of the key: never a bf16 call's plan)
+            tiling_ = _PLANS.get(key)
+            if tiling_ is None:
+                if len(_PLANS) > 4096:
+                    _PLANS.clear()
+                tiling_ = _PLANS[key] = _with_policy(tiling_fp32_out(m, n, k), strict, policy)
+        else:
+            tiling_ = _with_policy(tiling_, strict, policy)
+        stream = _stream_of(index)
+        ws_ptr, ws_bytes = _workspace(tiling_, out.device, stream)
+        flags = 0
+        if strided:
+            flags = (_lib.ROWS_A_ZERO_PADDED if zero_padded[0] else 0) | (_lib.ROWS_B_ZERO_PADDED if zero_padded[1] else 0)
+        rc = _lib.lib().dga_gemm_fp8_fp8_fp32_nt(a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(),
+                                                 None if c is None else c.data_ptr(), out.data_ptr(), m, n, k, flags,
+                                                 ctypes.byref(tiling_), ws_ptr, ws_bytes, stream)
+        if rc:
+            _lib.check(rc, "gemm_fp8_fp8_fp32_nt")
         if sync:
             torch.cuda.current_stream(out.device).synchronize()
 

@@ -100,11 +100,12 @@ static constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 struct Bf16xVariant {
     int bm, bn;
     int (*launch)(const GemmParams &, hipStream_t);
+    int (*launch_f32)(const GemmParams &, hipStream_t);   // the same build with fp32 rows (+ C): dga_gemm_fp8_fp8_fp32_nt
 };
+#define DGA_BX_VARIANT(BM, BN, WM, WN) {BM, BN, &launch_bf16x<GemmCfg<BM, BN, WM, WN, 3>>, &launch_bf16x_f32<GemmCfg<BM, BN, WM, WN, 3>>}
 static const Bf16xVariant kBf16xVariants[] = {
-    {128, 256, &launch_bf16x<GemmCfg<128, 256, 2, 4, 3>>}, {128, 128, &launch_bf16x<GemmCfg<128, 128, 2, 2, 3>>},
-    {64, 256, &launch_bf16x<GemmCfg<64, 256, 1, 4, 3>>},   {64, 128, &launch_bf16x<GemmCfg<64, 128, 1, 4, 3>>},
-    {32, 128, &launch_bf16x<GemmCfg<32, 128, 1, 4, 3>>},
+    DGA_BX_VARIANT(128, 256, 2, 4), DGA_BX_VARIANT(128, 128, 2, 2), DGA_BX_VARIANT(64, 256, 1, 4), DGA_BX_VARIANT(64, 128, 1, 4),
+    DGA_BX_VARIANT(32, 128, 1, 4),
 };
 // the tiling's (m1, n1) mapped onto that menu: the tile height rounded into {32, 64, 128}, the width kept where the height
 // has a build of that width
@@ -223,11 +224,14 @@ static int (*find_clock_build(const Variant *v, int policy))(const GemmParams &,
 // clock_stamps != nullptr (dga_gemm_fp8_loop_clock only): run the loop-clock build of the chosen variant, two words per
 // wave go to clock_stamps.
 // ix != nullptr: indexed masked-grouped form (a / sfa / out are flat row buffers addressed through ix->row_index).
+// out_f32: fp32 rows (dense only; dga_gemm_fp8_fp8_fp32_nt), c_in the optional fp32 addend (may be out)
 int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, void *out,
             const int32_t *masked_m, const int32_t *m_indices, int b_groups, int groups, int m, int n, int k,
             int expected_m, const dga_tiling_t *tiling, void *workspace, size_t workspace_bytes,
-            hipStream_t stream, unsigned long long *clock_stamps, const Fp8Indexed *ix, const Fp8Strided *sd)
+            hipStream_t stream, unsigned long long *clock_stamps, const Fp8Indexed *ix, const Fp8Strided *sd, bool out_f32,
+            const float *c_in)
 {
+    if (out_f32 && (groups != 1 || b_groups != 1 || masked_m || m_indices || ix || clock_stamps)) return DGA_E_SHAPE;
     if (m < 0 || n < 0 || k < 0 || groups < 0 || b_groups < 0) return DGA_E_SHAPE;
     if (groups == 0 || m == 0 || n == 0) return DGA_OK;  // empty problem: nothing to write
     if (!a || !b || !sfa || !sfb || !out) {
@@ -241,6 +245,10 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         pr.layoutTagA = DGA_LAYOUT_ROW_MAJOR; pr.layoutTagB = DGA_LAYOUT_COLUMN_MAJOR;
         pr.layoutTagC = DGA_LAYOUT_ROW_MAJOR; pr.dtype = DGA_DT_FP8_E4M3FN;
         pr.flags = m_indices ? DGA_PROBLEM_CONTIGUOUS_M : 0;
+        if (out_f32) {   // the fp32 entry's own selector: the bf16-exact pick (strict under a strict process default)
+            if (int rc = dga_tiling_fp32_out(&pr, &local)) return rc;
+            tiling = &local;
+        } else {
         // A call that names no tiling runs the policy whose outputs stay inside the operator's contract (within 2 bf16 ULP of the
         // fp32-accumulate result: bf16-exact, dispatchPolicyTag 7) unless $DGA_DEFAULT_POLICY says "fast" (the fp8 matrix
         // instruction: twice the rate, product bits ~13 below each octet's largest dropped) or "strict".  $DGA_BF16_EXACT=1
@@ -257,8 +265,9 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         if (rc == DGA_OK && (default_policy == 3 || default_policy == 4)) local.dispatchPolicyTag |= DGA_POLICY_UE8M0_SCALES;
         if (rc != DGA_OK) return rc;
         tiling = &local;
+        }
     }
-    if (int rc = check_tiling(*tiling)) return rc;
+    if (int rc = out_f32 ? dga_tiling_check_fp32_out(tiling) : check_tiling(*tiling)) return rc;
     // DGA_POLICY_UE8M0_SCALES: a flag beside the schedule -- the caller promises power-of-two scales; the tile builds that carry
     // the scales in the matrix instruction's E8M0 operands run where they exist (launch_ue8m0), everything else reads the tag
     // without the flag
@@ -333,6 +342,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     // ---- strict policy: the exact-arithmetic kernel takes every shape as it is (no workspace, no padding pass)
     static const int strict_env = [] { const char *e = std::getenv("DGA_STRICT"); return e ? std::atoi(e) : 0; }();
     if (clock_stamps && (tiling->dispatchPolicyTag == DGA_POLICY_STRICT || strict_env || (k % 16) != 0)) return DGA_E_TILING;
+    if (out_f32) p.c_in = c_in;   // (the split-K block below writes its slabs with the bf16 build and hands C to the combine instead)
     if (tiling->dispatchPolicyTag == DGA_POLICY_STRICT || strict_env) {
         // tile height: 64 rows (two 16-row chains per wave: 105-109 TFLOP/s at 4096^3 where 128 rows -- one wave per SIMD,
         // its two barriers per k block exposed -- reached 91), 32 rows where 64-row tiles would leave CUs idle
@@ -349,7 +359,12 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         const int64_t tiles128 = static_cast<int64_t>((m + 127) / 128) * ((n + 127) / 128);
         if (groups == 1 && !masked_m && !m_indices && !ix && tiles128 >= 2 * static_cast<int64_t>(device_cus())) {
             p.tiles_m = (m + 127) / 128;
-            hipLaunchKernelGGL(gemm_fp8_strict_nt_kernel<4>, dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
+            if (out_f32) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<4, 1>), dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
+            else hipLaunchKernelGGL(gemm_fp8_strict_nt_kernel<4>, dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
+        } else
+        if (out_f32) {
+            if (bm == 64) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<2, 1>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<1, 1>), grid, block, 0, stream, p);
         } else
         if (bm == 64) hipLaunchKernelGGL(gemm_fp8_strict_nt_kernel<2>, grid, block, 0, stream, p);
         else hipLaunchKernelGGL(gemm_fp8_strict_nt_kernel<1>, grid, block, 0, stream, p);
@@ -442,7 +457,8 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     if (!fast_ok) {
         // K not a multiple of the 16-byte DMA chunk and no workspace to pad into (or k == 0): element-wise kernel
         dim3 grid((n + 15) / 16, (m + 15) / 16, groups);
-        hipLaunchKernelGGL(gemm_fp8_blockscaled_nt_generic_kernel, grid, dim3(256), 0, stream, p);
+        if (out_f32) hipLaunchKernelGGL(gemm_fp8_blockscaled_nt_generic_kernel<1>, grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(gemm_fp8_blockscaled_nt_generic_kernel<>, grid, dim3(256), 0, stream, p);
         DGA_HIP_TRY(hipGetLastError());
         return DGA_OK;
     }
@@ -458,7 +474,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     // grouped call of the policy.)
     static const int bx_image_env = [] { const char *e = std::getenv("DGA_BX_IMAGE"); return e ? std::atoi(e) : -1; }();
     int bx_image = 0;
-    if (vx && vx->bm == 128 && vx->bn == 256 && !m_indices && !ix) {
+    if (vx && vx->bm == 128 && vx->bn == 256 && !m_indices && !ix && !out_f32) {   // (no fp32-output image build)
         if (bx_image_env >= 0) bx_image = bx_image_env == 4 ? 4 : (bx_image_env == 1 ? 1 : (bx_image_env ? 8 : 0));
         else if (tiling->build == DGA_BUILD_BX_AIMAGE) bx_image = 1;
         else if (tiling->build == DGA_BUILD_BX_IMAGE8) bx_image = 8;
@@ -479,7 +495,9 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     // Dense rasters of at most two rounds: every CU stores its tile at the same moment, and rows written "sc0 sc1" (write-through)
     // do not wait in the XCD's L2 for the kernel-end write-back -- 4096^3: fast 60.3 -> 58.9 us, hardware-scale 55.6 -> 54.1,
     // bf16-exact 121.3 -> 119.3; the nt policy is 2 % SLOWER there, longer rasters are level (profiles/r05_out_store_policy.txt)
-    if (out_nt_env < 0 && groups == 1 && !masked_m && !m_indices && !ix &&
+    // (fp32 rows keep plain stores: there the write-through form is 6-19 % SLOWER -- 4096^3 137.0 -> 129.0 us warm, 147.5 -> 127.8 cold,
+    //  with C 156.9 -> 128.4; profiles/fp32_out_timing.txt)
+    if (out_nt_env < 0 && groups == 1 && !masked_m && !m_indices && !ix && !out_f32 &&
         static_cast<int64_t>(p.tiles_m) * p.tiles_n <= 2 * static_cast<int64_t>(device_cus()))
         p.out_nt = 2;
     p.raster_group = tiling->swizzleOffset ? tiling->swizzleOffset : 1;
@@ -499,13 +517,13 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         const size_t need = s > 0 ? bx_dsk_workspace_bytes(dsk_tiles, s) : 0;
         uint8_t *dsk_ws = need ? carve(need) : nullptr;
         if (s > 0 && (need == 0 || dsk_ws)) {
-            const int rc = launch_bf16x_dsk(p, s, dsk_ws, need, stream);
+            const int rc = launch_bf16x_dsk(p, s, dsk_ws, need, stream, out_f32);
             if (rc != DGA_E_TILING) return rc;
         }
     }
     if (bf16x && !clock_stamps && groups == 1 && !masked_m && !m_indices && !ix && tiling->build != DGA_BUILD_BX_DECODE &&
         (wsk_env >= 0 ? wsk_env != 0 : tiling->kernelSerial == DGA_KERNEL_SPLITK_WORKGROUP)) {
-        const int rc = launch_wsk_dma(p, stream, 1);   // the bf16-exact policy has the LDS-DMA build only (M <= 32)
+        const int rc = launch_wsk_dma(p, stream, 1, out_f32);   // the bf16-exact policy has the LDS-DMA build only (M <= 32)
         if (rc != DGA_E_TILING) return rc;
     }
     if (!bf16x && !clock_stamps && groups == 1 && !masked_m && !m_indices && !ix &&
@@ -529,12 +547,23 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         s = (p.kb_n + kbps - 1) / kbps;  // no empty split
         float *slabs = s > 1 ? reinterpret_cast<float *>(carve(static_cast<size_t>(s) * m * n * sizeof(float))) : nullptr;
         if (slabs) {
-            p.splitk = s;
-            p.kb_per_split = kbps;
-            p.partial = slabs;
+            // (the slab pointer goes into the slab launch's own copy: in p it shares its storage with c_in, which the fp32 path still
+            //  hands to the combine -- see GemmParams)
             GemmParams pk = p;
+            pk.splitk = s;
+            pk.kb_per_split = kbps;
+            pk.partial = slabs;
             pk.groups = s;  // grid = splitk x tiles
             int rc = DGA_E_TILING;
+            if (out_f32) {   // the slabs are the bf16 build's (its split-K store path); the fp32 combine adds C once
+                rc = vx->launch(pk, stream);
+                if (rc != DGA_OK) return rc;
+                const int64_t mn = static_cast<int64_t>(m) * n;
+                hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3(static_cast<unsigned>((mn / 8 + 255) / 256 + 1)), dim3(256), 0, stream,
+                                   slabs, p.c_in, static_cast<float *>(out), mn, s);
+                DGA_HIP_TRY(hipGetLastError());
+                return DGA_OK;
+            }
             if (vx && bx_ue8m0 && !bx_image) rc = launch_bf16u(vx->bm, vx->bn, pk, stream);
             if (rc == DGA_E_TILING)
                 rc = vx ? (bx_image ? launch_bf16x_image(pk, bx_image, stream) : vx->launch(pk, stream)) : v->launch(pk, stream);
@@ -565,14 +594,14 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
             if (tail > 0 && tail * 2 <= cus && main_tiles > 0 && vq && vq->bm == 64 && vq->bn == 128) {
                 GemmParams pm = p;
                 pm.launch_tiles = main_tiles;
-                int rc = launch_bf16x_persistent(pm, stream);    // (DGA_E_TILING: a launch it does not take -- one k block)
-                if (rc == DGA_E_TILING) rc = vx->launch(pm, stream);
+                int rc = out_f32 ? launch_bf16x_persistent_f32(pm, stream) : launch_bf16x_persistent(pm, stream);    // (DGA_E_TILING: a launch it does not take -- one k block)
+                if (rc == DGA_E_TILING) rc = out_f32 ? vx->launch_f32(pm, stream) : vx->launch(pm, stream);
                 if (rc != DGA_OK) return rc;
                 GemmParams pt = p;  // tiles_m / tiles_n / raster_group stay those of the parent raster
                 pt.tail_begin = main_tiles;
                 pt.tail_sub = 2;
                 pt.launch_tiles = tail * 4;
-                return vq->launch(pt, stream);
+                return out_f32 ? vq->launch_f32(pt, stream) : vq->launch(pt, stream);
             }
         }
         // the 128 x 256 tile's persistent form (gemm_fp8_bf16x_persistent_kernel.hpp; same bits).  The dispatcher hides most of a tile
@@ -591,7 +620,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
             !masked_m && !m_indices && !ix) {
             const size_t need = bx_streamk_workspace_bytes();
             if (uint8_t *sk_ws = carve(need)) {
-                const int rc = launch_bf16x_streamk(p, sk_ws, need, stream);
+                const int rc = launch_bf16x_streamk(p, sk_ws, need, stream, out_f32);
                 if (rc != DGA_E_TILING) return rc;
             }
         }
@@ -599,7 +628,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         // the loop unrolled for the m-tiles that hold rows.  tiling.build = DGA_BUILD_BX_GROUPED names it (dga_tiling_bf16_exact does), $DGA_BX_GROUPED = 0 / 1 overrides.
         static const int bxg_env = [] { const char *e = std::getenv("DGA_BX_GROUPED"); return e ? std::atoi(e) : -1; }();
         // (a dense raster runs it too when the tiling names it: the loop is the same, every tile has all its rows)
-        if (vx->bm == 128 && vx->bn == 256 && !clock_stamps && !m_indices &&
+        if (vx->bm == 128 && vx->bn == 256 && !clock_stamps && !m_indices && !out_f32 &&
             (bxg_env >= 0 ? (bxg_env != 0 && masked_m) : tiling->build == DGA_BUILD_BX_GROUPED)) {
             const int rc = launch_bf16x_grouped(p, stream);
             if (rc != DGA_E_TILING) return rc;
@@ -607,10 +636,10 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         const bool pays = tiles > cus;
         if (vx->bm == 128 && vx->bn == 256 && !clock_stamps &&
             (bxp_env >= 0 ? bxp_env != 0 : (tiling->build == DGA_BUILD_BX_PERSISTENT || (tiling->build != DGA_BUILD_BX_ONE_TILE && pays)))) {
-            const int rc = launch_bf16x_persistent(p, stream);
+            const int rc = out_f32 ? launch_bf16x_persistent_f32(p, stream) : launch_bf16x_persistent(p, stream);
             if (rc != DGA_E_TILING) return rc;
         }
-        return vx->launch(p, stream);
+        return out_f32 ? vx->launch_f32(p, stream) : vx->launch(p, stream);
     }
     auto launch_main = [&](const GemmParams &q) -> int {
         // (the persistent loader-wave form has no hardware-scale build: on the grouped weight stream -- bound by HBM, not by the
@@ -706,6 +735,39 @@ int dga_tiling_check(const dga_tiling_t *tiling)
 {
     if (!tiling) return DGA_E_NULL;
     return dga::check_tiling(*tiling);
+}
+
+int dga_tiling_check_fp32_out(const dga_tiling_t *tiling)
+{
+    if (!tiling) return DGA_E_NULL;
+    if (int rc = dga::check_tiling(*tiling)) return rc;
+    const int tag = tiling->dispatchPolicyTag;   // (UE8M0_SCALES set: neither value below)
+    if (tag != DGA_POLICY_BF16_EXACT && tag != DGA_POLICY_STRICT) return DGA_E_TILING;
+    if (tag == DGA_POLICY_STRICT) return DGA_OK;   // (takes every build name: the strict kernel picks its own)
+    switch (tiling->build) {
+        case DGA_BUILD_BX_AIMAGE: case DGA_BUILD_BX_IMAGE8: case DGA_BUILD_BX_IMAGE4: case DGA_BUILD_BX_GROUPED: return DGA_E_TILING;
+        default: return DGA_OK;
+    }
+}
+
+int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb, const float *c,
+                             float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    if (m < 0 || n < 0 || k < 0) return DGA_E_SHAPE;
+    if (m == 0 || n == 0) return DGA_OK;
+    if (!out) return DGA_E_NULL;
+    if (c && c != out) {   // in place or apart: a partial overlap would read outputs other lanes have already written
+        const uintptr_t bytes = static_cast<uintptr_t>(m) * static_cast<uintptr_t>(n) * sizeof(float);
+        const uintptr_t co = reinterpret_cast<uintptr_t>(c), oo = reinterpret_cast<uintptr_t>(out);
+        if (co < oo + bytes && oo < co + bytes) return DGA_E_SHAPE;
+    }
+    if (tiling)
+        if (int rc = dga_tiling_check_fp32_out(tiling)) return rc;
+    const dga::Fp8Strided sd{lda, ldb, flags};
+    const bool strided = lda != k || ldb != k;   // (contiguous rows: the path of dga_gemm_fp8_fp8_bf16_nt)
+    return dga::run_fp8(a, sfa, b, sfb, out, nullptr, nullptr, 1, 1, m, n, k, 0, tiling, workspace, workspace_bytes,
+                        static_cast<hipStream_t>(stream), nullptr, nullptr, strided ? &sd : nullptr, true, c);
 }
 
 int dga_gemm_fp8_fp8_bf16_nt(const void *a, const float *sfa, const void *b, const float *sfb, void *out, int m,

@@ -35,11 +35,11 @@ int coresident_workgroups(hipStream_t stream)
 
 size_t bx_streamk_workspace_bytes() { return static_cast<size_t>(device_cus()) * (128 * 256 * 4 + 8) + 256; }
 
-template <bool KTAIL>
+template <bool KTAIL, int OUT = 0>
 static int launch_bx_streamk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
     typedef GemmCfg<128, 256, 2, 4, 3> Cfg;
-    auto kfn = gemm_fp8_bf16x_streamk_kernel<KTAIL>;
+    auto kfn = gemm_fp8_bf16x_streamk_kernel<KTAIL, OUT>;
     static std::once_flag once[64];
     static hipError_t attr_err[64];
     int dev = 0;
@@ -55,7 +55,7 @@ static int launch_bx_streamk_one(const GemmParams &p, const StreamKArgs &sk, uns
 
 // ws: the caller's workspace, at least bx_streamk_workspace_bytes().  DGA_E_TILING: not a launch this kernel takes (no partial round to
 // cut, a layout it does not have, co-residency not guaranteed, no or too small a workspace): the caller runs the tiling's tile kernel.
-int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream)
+int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, bool f32)
 {
     if (p.groups != 1 || p.masked_m || p.m_indices || p.row_index || p.splitk > 1 || p.tail_sub || p.stamps || p.launch_tiles) return DGA_E_TILING;
     if (p.kb_n < 2) return DGA_E_TILING;
@@ -78,9 +78,13 @@ int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStre
 #ifdef DGA_BXSK_KNOBS
     GemmParams q = p;
     if (const char *e = std::getenv("DGA_BXSK_KNOB")) q.tail_begin = std::atoi(e);
+    if (f32) return DGA_E_TILING;   // (the diagnostic knobs ride on the bf16 build only)
     return (p.k % 128) ? launch_bx_streamk_one<true>(q, sk, static_cast<unsigned>(grid), stream)
                        : launch_bx_streamk_one<false>(q, sk, static_cast<unsigned>(grid), stream);
 #endif
+    if (f32)
+        return (p.k % 128) ? launch_bx_streamk_one<true, 1>(p, sk, static_cast<unsigned>(grid), stream)
+                           : launch_bx_streamk_one<false, 1>(p, sk, static_cast<unsigned>(grid), stream);
     return (p.k % 128) ? launch_bx_streamk_one<true>(p, sk, static_cast<unsigned>(grid), stream)
                        : launch_bx_streamk_one<false>(p, sk, static_cast<unsigned>(grid), stream);
 }

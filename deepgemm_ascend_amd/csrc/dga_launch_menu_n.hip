@@ -27,10 +27,10 @@ size_t bx_dsk_workspace_bytes(int64_t tiles, int splits)
     return static_cast<size_t>(tiles) * (splits - 1) * (DskCfg::SLOT_FLOATS * 4 + 8) + 256;
 }
 
-template <bool KTAIL, bool IMG = true>
+template <bool KTAIL, bool IMG = true, int OUT = 0>
 static int launch_bx_dsk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
-    auto kfn = gemm_fp8_bf16x_dsk_kernel<KTAIL, IMG>;
+    auto kfn = gemm_fp8_bf16x_dsk_kernel<KTAIL, IMG, OUT>;
     constexpr int kLds = IMG ? DskCfg::IMG_LDS_BYTES : DskCfg::LDS_BYTES;
     static std::once_flag once[64];
     static hipError_t attr_err[64];
@@ -48,7 +48,7 @@ static int launch_bx_dsk_one(const GemmParams &p, const StreamKArgs &sk, unsigne
 // splits: the tiling's splitkFactor (clamped by bx_dsk_splits).  ws: the caller's workspace, bx_dsk_workspace_bytes() at least where the
 // launch splits across workgroups.  DGA_E_TILING: not a launch this kernel takes (a layout it does not have, more tiles than CUs, fewer
 // than four k blocks, co-residency not guaranteed, no or too small a workspace): the caller runs the tiling's tile kernel.
-int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream)
+int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, bool f32)
 {
     if (p.groups != 1 || p.masked_m || p.m_indices || p.row_index || p.splitk > 1 || p.tail_sub || p.stamps || p.launch_tiles) return DGA_E_TILING;
     const int cus = coresident_workgroups(stream);
@@ -99,6 +99,7 @@ int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes,
     if (q.tail_begin & 64)
         return (p.k % 128) ? launch_bx_dsk_one<true, false>(q, sk, grid, stream) : launch_bx_dsk_one<false, false>(q, sk, grid, stream);
 #endif
+    if (f32) return (p.k % 128) ? launch_bx_dsk_one<true, true, 1>(q, sk, grid, stream) : launch_bx_dsk_one<false, true, 1>(q, sk, grid, stream);
     return (p.k % 128) ? launch_bx_dsk_one<true>(q, sk, grid, stream) : launch_bx_dsk_one<false>(q, sk, grid, stream);
 }
 

@@ -1226,6 +1226,26 @@ int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out)
     return DGA_OK;
 }
 
+int dga_tiling_fp32_out(const dga_problem_t *problem, dga_tiling_t *out)
+{
+    if (!problem || !out) return DGA_E_NULL;
+    const int policy = dga::default_policy();
+    if (policy < 0) return DGA_E_RANGE;
+    if (int rc = dga_tiling_bf16_exact(problem, out)) return rc;
+    if (policy == 2) {   // a strict process default: strict here too
+        out->dispatchPolicyTag = DGA_POLICY_STRICT;
+        return DGA_OK;
+    }
+    // builds without an fp32 epilogue (a cache row may name them): the same tile on the in-register bf16-exact builds
+    const bool no_f32 = out->dispatchPolicyTag != DGA_POLICY_BF16_EXACT || out->build == DGA_BUILD_BX_AIMAGE ||
+                        out->build == DGA_BUILD_BX_IMAGE8 || out->build == DGA_BUILD_BX_IMAGE4 || out->build == DGA_BUILD_BX_GROUPED;
+    if (no_f32) {
+        out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+        out->build = DGA_BUILD_DEFAULT;
+    }
+    return DGA_OK;
+}
+
 int dga_tiling_cache_open(const char *csv_path) { return Cache::instance().open(csv_path); }
 int dga_tiling_cache_clear(void) { Cache::instance().clear(); return DGA_OK; }
 int dga_tiling_cache_size(void) { return Cache::instance().size(); }

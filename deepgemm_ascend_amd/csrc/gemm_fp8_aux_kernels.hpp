@@ -18,6 +18,8 @@ __device__ __forceinline__ float e4m3fn_to_f32(uint8_t v)
     return (v & 0x80) ? -r : r;
 }
 
+// OUT = 1: fp32 rows, + C (K = 0: out = C exactly)
+template <int OUT = 0>
 __global__ void __launch_bounds__(256) gemm_fp8_blockscaled_nt_generic_kernel(const GemmParams p)
 {
     __shared__ float lut[256];
@@ -44,6 +46,11 @@ __global__ void __launch_bounds__(256) gemm_fp8_blockscaled_nt_generic_kernel(co
         float part = 0.f;
         for (int k = k0; k < k1; ++k) part += lut[ar[k]] * lut[br[k]];
         acc += part * (sa[kb] * sb[kb]);
+    }
+    if constexpr (OUT == 1) {
+        const int64_t at = (int64_t)g * p.c_gs + mrow * p.ldc + n;
+        reinterpret_cast<float *>(p.out)[at] = p.c_in ? (p.kb_n ? add_c_no_fma(acc, p.c_in[at]) : p.c_in[at]) : acc;
+        return;
     }
     const v2bf h = __builtin_convertvector(v2f{acc, 0.f}, v2bf);
     p.out[(int64_t)g * p.c_gs + mrow * p.ldc + n] = (uint16_t)(__builtin_bit_cast(uint32_t, h) & 0xFFFFu);
@@ -72,6 +79,33 @@ __global__ void __launch_bounds__(256) splitk_reduce_bf16_kernel(const float *pa
             for (int s = 1; s < splitk; ++s) acc += partial[(int64_t)s * mn + i + q];
             const v2bf h = __builtin_convertvector(v2f{acc, 0.f}, v2bf);
             out[i + q] = (uint16_t)(__builtin_bit_cast(uint32_t, h) & 0xFFFFu);
+        }
+    }
+}
+
+// ... with fp32 output: out[i] = fl(sum_s slab[s][i] + c[i]) (c == nullptr: the sum), the addend read once, after the sum is complete.
+// c may be out itself.
+__global__ void __launch_bounds__(256) splitk_reduce_f32_kernel(const float *partial, const float *c, float *out, int64_t mn, int splitk)
+{
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i >= mn) return;
+    if (((mn & 7) == 0) && ((((uintptr_t)out) | ((uintptr_t)c)) & 15) == 0) {
+        v4f a0 = *(const v4f *)(partial + i), a1 = *(const v4f *)(partial + i + 4);
+        for (int s = 1; s < splitk; ++s) {
+            a0 += *(const v4f *)(partial + (int64_t)s * mn + i);
+            a1 += *(const v4f *)(partial + (int64_t)s * mn + i + 4);
+        }
+        if (c) {
+            a0 = add_c_no_fma(a0, *(const v4f *)(c + i));
+            a1 = add_c_no_fma(a1, *(const v4f *)(c + i + 4));
+        }
+        *(v4f *)(out + i) = a0;
+        *(v4f *)(out + i + 4) = a1;
+    } else {
+        for (int q = 0; q < 8 && i + q < mn; ++q) {
+            float acc = partial[i + q];
+            for (int s = 1; s < splitk; ++s) acc += partial[(int64_t)s * mn + i + q];
+            out[i + q] = c ? add_c_no_fma(acc, c[i + q]) : acc;
         }
     }
 }

@@ -45,7 +45,7 @@ struct DskCfg {
 // IMG: the A tile of a k block is converted ONCE per k group -- wave w its m-tile w, into a bf16 image in LDS behind a second barrier --
 // instead of once per wave: 16 + 32 conversions per wave and k block instead of 64 + 32 (the loop is bound by the vector port: two waves
 // per SIMD take twice one wave's time), and the raw stage is dead at that barrier, so two stages carry the refill as far ahead as three.
-template <bool KTAIL, bool IMG = true>
+template <bool KTAIL, bool IMG = true, int OUT = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
 {
@@ -365,6 +365,13 @@ gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
     const bool vec_ok = ((p.ldc & 7) == 0) && ((((uintptr_t)Cout) & 15) == 0);
     auto store_row = [&](int m, int n, const v4f &lo, const v4f &hi) {
         if (m >= M) return;
+        if constexpr (OUT == 1) {   // (the workgroup that writes the tile: C goes in once, after the last partial)
+            float *const Cf = reinterpret_cast<float *>(p.out);
+            const v4f v[2] = {lo, hi};
+            store_row_f32<8>(Cf + (int64_t)m * p.ldc, p.c_in ? p.c_in + (int64_t)m * p.ldc : nullptr, n, p.n,
+                             f32_rows_vec(Cf, p.c_in, p.ldc), 0, v);
+            return;
+        }
         uint16_t *crow = Cout + (int64_t)m * p.ldc;
         const v2bf h0 = __builtin_convertvector(v2f{lo.x, lo.y}, v2bf);
         const v2bf h1 = __builtin_convertvector(v2f{lo.z, lo.w}, v2bf);

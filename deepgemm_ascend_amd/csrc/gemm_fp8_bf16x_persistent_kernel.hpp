@@ -23,7 +23,7 @@
 
 namespace dga {
 
-template <bool KTAIL>
+template <bool KTAIL, int OUT = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
 {
@@ -303,6 +303,23 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
             uint16_t *C = p.out + (int64_t)T.g * p.c_gs;
             const int m_row = T.m0 + wm * (BM / Cfg::kWM) + li;
             const int n_base = T.n0 + wn * (BN / WN) + 8 * kg;
+            if constexpr (OUT == 1) {
+                float *const Cf = reinterpret_cast<float *>(p.out) + (int64_t)T.g * p.c_gs;
+                const float *const Ci = p.c_in ? p.c_in + (int64_t)T.g * p.c_gs : nullptr;
+                const bool vec = f32_rows_vec(Cf, Ci, p.ldc);
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) {
+                    const int m = m_row + mt * 16;
+                    if (m >= T.M) continue;
+                    float *orow = Cf + (int64_t)m * p.ldc;
+                    const float *crow = Ci ? Ci + (int64_t)m * p.ldc : nullptr;
+#pragma unroll
+                    for (int j = 0; j < TN / 2; ++j) {
+                        const v4f v[2] = {acc[mt][2 * j], acc[mt][2 * j + 1]};
+                        store_row_f32<8>(orow, crow, n_base + 32 * j, p.n, vec, p.out_nt, v);
+                    }
+                }
+            } else {
             const bool vec_ok = ((p.ldc & 7) == 0) && ((((uintptr_t)C) & 15) == 0);
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt) {
@@ -331,6 +348,7 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
                             if (n + q < p.n) crow[n + q] = e[q];
                     }
                 }
+            }
             }
         }
         if (!has_next) break;

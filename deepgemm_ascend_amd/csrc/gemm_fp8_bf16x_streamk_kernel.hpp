@@ -57,7 +57,7 @@ __host__ __device__ inline BxStreamKPlan bx_streamk_plan(int tiles, int P, int K
     return pl;
 }
 
-template <bool KTAIL>
+template <bool KTAIL, int OUT = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 gemm_fp8_bf16x_streamk_kernel(const GemmParams p, const StreamKArgs sk)
 {
@@ -366,6 +366,23 @@ gemm_fp8_bf16x_streamk_kernel(const GemmParams p, const StreamKArgs sk)
         uint16_t *C = p.out;
         const int m_row = T.m0 + wm * (BM / Cfg::kWM) + li;
         const int n_base = T.n0 + wn * (BN / WN) + 8 * kg;
+        if constexpr (OUT == 1) {   // full tiles and the adding piece: C goes in once, after the last partial
+            float *const Cf = reinterpret_cast<float *>(p.out);
+            const bool vec = f32_rows_vec(Cf, p.c_in, p.ldc);
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) {
+                const int m = m_row + mt * 16;
+                if (m >= p.m) continue;
+                float *orow = Cf + (int64_t)m * p.ldc;
+                const float *crow = p.c_in ? p.c_in + (int64_t)m * p.ldc : nullptr;
+#pragma unroll
+                for (int j = 0; j < TN / 2; ++j) {
+                    const v4f v[2] = {acc[mt][2 * j], acc[mt][2 * j + 1]};
+                    store_row_f32<8>(orow, crow, n_base + 32 * j, p.n, vec, p.out_nt == 2 ? 2 : 0, v);
+                }
+            }
+            return;
+        }
         const bool vec_ok = ((p.ldc & 7) == 0) && ((((uintptr_t)C) & 15) == 0);
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt) {

@@ -48,7 +48,12 @@ struct GemmParams {
     int tiles_m, tiles_n, groups;
     int raster_group;            // tile-rows walked together (swizzleOffset analogue, tiling_params.h:63)
     int xcd_remap;               // 1: contiguous tile chunk per XCD (blocks b, b+8, ... share an XCD)
-    float *partial;              // split-K: fp32 slabs [splitk][m][n] in the caller's workspace (dense only)
+    union {
+        float *partial;          // split-K: fp32 slabs [splitk][m][n] in the caller's workspace (dense only)
+        const float *c_in;       // fp32-output builds (OUT = 1, never split-K themselves): the addend C, fp32 rows of ldc like out (may be
+                                 // out itself); nullptr: none.  One storage: a launcher that writes `partial` does so in a copy of the
+                                 // params it launches the slab pass with, never in the params it still reads c_in from (run_fp8)
+    };
     int splitk, kb_per_split;    // splitk > 1: block -> (split, tile); split s covers k blocks [s*kb_per_split, +kb_per_split)
     int b_nt;                    // persistent builds: B fetched with the non-temporal policy: 0 never, 1 always, 2 per tile
                                  // by its row count (the masked grouped stream: weights read once by one CU)
@@ -59,6 +64,49 @@ struct GemmParams {
     unsigned long long *stamps;  // diagnostics only: per-wave segment cycle sums (-DDGA_STAMPS builds, 8 words per wave) or the
                                  // loop clock of the CLK = true instantiations (2 words per wave); nullptr in product calls
 };
+
+// fp32-output epilogue (the OUT = 1 builds behind dga_gemm_fp8_fp8_fp32_nt): out is then fp32 rows, and C, when given, is added once to
+// the finished accumulator -- out = fl(acc + c), never folded into a partial sum.  A lane's 8 consecutive outputs leave as two 16-byte
+// stores (the bf16 epilogue's one), C is read 16 bytes at a time right before them, one m-tile row at a time; the same store flavours
+// as the bf16 rows (out_nt).  Ragged N, a row stride that is not a multiple of 4 or a misaligned out / C take the scalar path.
+__device__ __forceinline__ float add_c_no_fma(float v, float c)
+{
+#pragma clang fp contract(off)
+    return v + c;
+}
+__device__ __forceinline__ v4f add_c_no_fma(v4f v, v4f c)
+{
+#pragma clang fp contract(off)
+    return v + c;
+}
+__device__ __forceinline__ void store_f32x4(float *dst, v4f v, int out_nt)
+{
+    if (out_nt == 1) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(dst), "v"(v) : "memory");
+    else if (out_nt == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(v) : "memory");
+    else if (out_nt == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" :: "v"(dst), "v"(v) : "memory");
+    else *(v4f *)dst = v;
+}
+// W (4 or 8) consecutive outputs of one row from column n: v[0] = columns n..n+3, v[1] = n+4..n+7; crow: the addend's row or nullptr
+template <int W>
+__device__ __forceinline__ void store_row_f32(float *orow, const float *crow, int n, int N, bool vec, int out_nt, const v4f (&v)[W / 4])
+{
+    if (vec && n + W <= N) {
+#pragma unroll
+        for (int h = 0; h < W / 4; ++h) {
+            const v4f r = crow ? add_c_no_fma(v[h], *(const v4f *)(crow + n + 4 * h)) : v[h];
+            store_f32x4(orow + n + 4 * h, r, out_nt);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < W; ++q)
+            if (n + q < N) orow[n + q] = crow ? add_c_no_fma(v[q >> 2][q & 3], crow[n + q]) : v[q >> 2][q & 3];
+    }
+}
+// 16-byte vector rows of out and C
+__device__ __forceinline__ bool f32_rows_vec(const float *out, const float *c, int64_t ldc)
+{
+    return (ldc & 3) == 0 && ((((uintptr_t)out) | ((uintptr_t)c)) & 15) == 0;
+}
 
 // In-kernel stamps (diagnostic build only; cdna_hip_programming.md section 7 "In-kernel stamps").
 #ifdef DGA_STAMPS
@@ -158,9 +206,10 @@ struct LoopClock {
 //         swizzled image the LDS-DMA would have written -- the computing waves are unchanged.  The counterpart of the reference's
 //         PaddingCommon kernel, which fuses the re-layout with the matmul
 //         (/root/reference/aclnn_catlass_dynamic_matmul/op_kernel/kernel/padding_common_matmul_kernel.h:33-107).
-template <class Cfg, int PP, bool KTAIL, bool CLK = false, int MATH = 0, bool UNAL = false>
+template <class Cfg, int PP, bool KTAIL, bool CLK = false, int MATH = 0, bool UNAL = false, int OUT = 0>
 __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const GemmParams p)
 {
+    static_assert(OUT == 0 || (MATH == 1 && PP == 0 && !CLK && !UNAL), "fp32 output: the bf16-exact builds");
     static_assert(!UNAL || (Cfg::kLC && PP == 0 && MATH == 0 && KTAIL), "unaligned rows: loader waves, plain loop, fp8 matrix instruction");
     static_assert(MATH != 2 || PP != 1, "hardware-scale builds: plain or continuous loop");
     static_assert(MATH != 3 || PP == 0, "bf16-exact builds: plain loop");
@@ -396,6 +445,25 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
                         for (int q = 0; q < 4; ++q)
                             if (n + q < p.n) prow[n + q] = acc[mt][nt][q];
                     }
+                }
+            }
+            return;
+        }
+        if constexpr (OUT == 1) {
+            float *const Cf = reinterpret_cast<float *>(p.out) + (int64_t)g * p.c_gs;
+            const float *const Ci = p.c_in ? p.c_in + (int64_t)g * p.c_gs : nullptr;
+            const bool vec = f32_rows_vec(Cf, Ci, p.ldc);
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) {
+                const int m = m_row + mt * 16;
+                if (m >= M) continue;
+                if (p.m_indices && p.m_indices[m] != bg) continue;
+                float *orow = Cf + out_row[mt] * p.ldc;
+                const float *crow = Ci ? Ci + out_row[mt] * p.ldc : nullptr;
+#pragma unroll
+                for (int j = 0; j < TN / 2; ++j) {
+                    const v4f v[2] = {acc[mt][2 * j], acc[mt][2 * j + 1]};
+                    store_row_f32<8>(orow, crow, n_base + 32 * j, p.n, vec, p.out_nt, v);
                 }
             }
             return;

@@ -47,7 +47,7 @@ __device__ __forceinline__ v4i transpose_bytes_4x4(v4i w)
 // TM = m-tiles (16 rows) per wave; workgroup = 2 x 2 waves, tile (32*TM) x 128, one LDS stage, register prefetch.
 // The launcher uses TM = 2 (two workgroups per CU cover each other's barriers: 110 TFLOP/s at 4096^3 against 91 for TM = 4)
 // and TM = 1 where 64-row tiles would leave CUs idle.
-template <int TM>
+template <int TM, int OUT = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
 __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParams p)
 {
     constexpr int BM = 32 * TM, BN = 128, TN = 4;
@@ -219,6 +219,24 @@ __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParam
     }
 
     // epilogue: D[i][j] with i = n (4q + t), j = m (r): a lane owns 4 consecutive n of one row
+    if constexpr (OUT == 1) {
+        float *const Cf = reinterpret_cast<float *>(p.out) + (int64_t)g * p.c_gs;
+        const float *const Ci = p.c_in ? p.c_in + (int64_t)g * p.c_gs : nullptr;
+        const bool vec = f32_rows_vec(Cf, Ci, p.ldc);
+#pragma unroll
+        for (int mt = 0; mt < TM; ++mt) {
+            const int m = m0 + a_row + 16 * mt;
+            if (m >= M) continue;
+            if (p.m_indices && p.m_indices[m] != bg) continue;
+            const int64_t row = (ridx ? ridx[m] : (int64_t)m) * p.ldc;
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt) {
+                const v4f v[1] = {acc[mt][nt]};
+                store_row_f32<4>(Cf + row, Ci ? Ci + row : nullptr, n0 + wn * 64 + 16 * nt + 4 * q, p.n, vec, 0, v);
+            }
+        }
+        return;
+    }
     const bool vec_st = ((p.ldc & 3) == 0) && ((((uintptr_t)C) & 7) == 0);
 #pragma unroll
     for (int mt = 0; mt < TM; ++mt) {

@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(512) gemm_fp8_wsk_kernel(const GemmParams p)
 // registers (v_cvt_scalef32_pk_bf16_fp8, exact) and a scale block is four chained v_mfma_f32_16x16x32_bf16 with the k placement of
 // the tile kernel's MATH = 1 loop (gemm_fp8_kernel.hpp): bit-identical to that policy's two-launch split-K.  The stream pays for
 // neither the conversions nor the second matrix rate.
-template <int TM, int TN, int D, bool KTAIL, int WAVES = 8, int MATH = 0>
+template <int TM, int TN, int D, bool KTAIL, int WAVES = 8, int MATH = 0, int OUT = 0>   // OUT = 1: fp32 rows (+ C)
 __global__ void __launch_bounds__(WAVES * 64) gemm_fp8_wskd_kernel(const GemmParams p)
 {
     constexpr int BM = TM * 16, BNW = TN * 16, ROWS = BM + BNW, NT = WAVES * 64;
@@ -370,6 +370,13 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_fp8_wskd_kernel(const GemmPar
             if (m >= M || nl >= cnt * 16) continue;
             v4f v = *(const v4f *)((const float *)smem + m * BNW + nl);
             for (int s = 1; s < s_eff; ++s) v += *(const v4f *)((const float *)(smem + s * RING) + m * BNW + nl);
+            if constexpr (OUT == 1) {   // (the combined tile: C goes in once, after the slices' sum)
+                float *const Cf = reinterpret_cast<float *>(p.out);
+                const v4f vv[1] = {v};
+                store_row_f32<4>(Cf + (int64_t)m * p.ldc, p.c_in ? p.c_in + (int64_t)m * p.ldc : nullptr, n0 + nl, p.n,
+                                 f32_rows_vec(Cf, p.c_in, p.ldc), 0, vv);
+                continue;
+            }
             const v2bf h0 = __builtin_convertvector(v2f{v.x, v.y}, v2bf), h1 = __builtin_convertvector(v2f{v.z, v.w}, v2bf);
             uint16_t *dst = p.out + (int64_t)m * p.ldc + n0 + nl;
             if (vec_ok && n0 + nl + 4 <= p.n) {
@@ -398,7 +405,7 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_fp8_wskd_kernel(const GemmPar
 // pass or the next -- and a pass boundary costs the two barriers around the combine, not a round trip.  Everything else (image,
 // hand-counted vmcnt, slices, arithmetic, combine order) is gemm_fp8_wskd_kernel's: the same bits.  The global stores of a combine
 // are counted in vmcnt like the DMA; they only make the next waits stricter (vector-memory operations retire in order).
-template <int TM, int TN, int D, bool KTAIL, int MATH = 0>
+template <int TM, int TN, int D, bool KTAIL, int MATH = 0, int OUT = 0>   // OUT = 1: fp32 rows (+ C)
 __global__ void __launch_bounds__(512) gemm_fp8_wskc_kernel(const GemmParams p)
 {
     constexpr int WAVES = 8, BM = TM * 16, BNW = TN * 16, ROWS = BM + BNW, NT = WAVES * 64;
@@ -573,6 +580,13 @@ __global__ void __launch_bounds__(512) gemm_fp8_wskc_kernel(const GemmParams p)
             if (m >= M || nl >= cnt * 16) continue;
             v4f v = *(const v4f *)(slab + m * BNW + nl);
             for (int s = 1; s < s_eff; ++s) v += *(const v4f *)(slab + (size_t)s * BM * BNW + m * BNW + nl);
+            if constexpr (OUT == 1) {   // (the combined tile: C goes in once, after the slices' sum)
+                float *const Cf = reinterpret_cast<float *>(p.out);
+                const v4f vv[1] = {v};
+                store_row_f32<4>(Cf + (int64_t)m * p.ldc, p.c_in ? p.c_in + (int64_t)m * p.ldc : nullptr, n0 + nl, p.n,
+                                 f32_rows_vec(Cf, p.c_in, p.ldc), 0, vv);
+                continue;
+            }
             const v2bf h0 = __builtin_convertvector(v2f{v.x, v.y}, v2bf), h1 = __builtin_convertvector(v2f{v.z, v.w}, v2bf);
             uint16_t *dst = p.out + (int64_t)m * p.ldc + n0 + nl;
             if (vec_ok && n0 + nl + 4 <= p.n) {

@@ -207,6 +207,17 @@ int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out);
  *     (DGA_BUILD_WSK_REGISTER only with kernelSerial 6); policy 1 and kernelSerial 5 / 7: 256 x 256 only. */
 int dga_tiling_check(const dga_tiling_t *tiling);
 
+/* TilingFunc of dga_gemm_fp8_fp8_fp32_nt (host only): what dga_tiling_bf16_exact returns, except that a tiling naming a build without
+ * an fp32 epilogue -- a bf16 image build (DGA_BUILD_BX_AIMAGE / _IMAGE8 / _IMAGE4), DGA_BUILD_BX_GROUPED, DGA_POLICY_UE8M0_SCALES or a
+ * fast-path tag (a cache row) -- comes back as the same tile with build = DGA_BUILD_DEFAULT and dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+ * with $DGA_DEFAULT_POLICY = "strict" the strict tag.  DGA_E_RANGE: $DGA_DEFAULT_POLICY names no policy.  No reference counterpart. */
+int dga_tiling_fp32_out(const dga_problem_t *problem, dga_tiling_t *out);
+/* dga_tiling_check plus the fp32 entry's refusals (host only): DGA_E_TILING for a dispatchPolicyTag other than DGA_POLICY_BF16_EXACT or
+ * DGA_POLICY_STRICT (the fast schedules), DGA_POLICY_UE8M0_SCALES, and the builds DGA_BUILD_BX_AIMAGE / _IMAGE8 / _IMAGE4 / _GROUPED.
+ * Every other bf16-exact build -- the one-tile and persistent tiles, the two-launch split-K, the quarter-tile tail, the one-launch decode
+ * split-K, Stream-K and workgroup split-K -- has an fp32 epilogue. */
+int dga_tiling_check_fp32_out(const dga_tiling_t *tiling);
+
 /* The arithmetic of an fp8 call that names neither a policy nor a tiling: $DGA_DEFAULT_POLICY, parsed and validated ONCE per process,
  * here, for every front end (the C entry points with tiling == NULL, deepgemm_ascend_amd/api.py, the deep_gemm_cpp extension).
  * Names: "bf16_exact" (the default: inside the operator's 2-ULP contract), "fast", "strict", "fast_ue8m0", "bf16_exact_ue8m0" (the
@@ -289,6 +300,22 @@ int dga_gemm_fp8_fp8_bf16_nt(const void *a, const float *sfa, const void *b, con
 int dga_gemm_fp8_fp8_bf16_nt_strided(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb,
                                      void *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
                                      size_t workspace_bytes, void *stream);
+
+/* gemm_fp8_fp8_fp32_nt: out[M,N] (fp32) = C[M,N] (fp32, optional) + dequant(A) . dequant(B)^T -- the fp32 result the reference's
+ * run_mmad_rtc writes into its caller-allocated z[B,M,N] (deep_gemm_ascend/framework/csrc/python_api.cpp:18,
+ * jit_kernels/impls/gemm.hpp:68-111; its golden is the fp32 np.matmul, scripts/gen_golden.py:14-15), with upstream DeepGEMM's fp32-output
+ * accumulation on top.  Operands, scales, strides and flags exactly as in dga_gemm_fp8_fp8_bf16_nt_strided (lda = ldb = K: contiguous
+ * rows).  out and c are contiguous [M,N] fp32 (ldc = N).
+ *   c == NULL: no addend; every element of out is written and its old contents are never read.  c == out: in-place accumulation;
+ *   a c that partially overlaps out: DGA_E_SHAPE.  The addend goes in with one fp32 add after the product is complete,
+ *   out = fl(acc + c) -- never into a partial sum (split-K adds it once, in its combine).  K = 0: out = c (or zeros).
+ *   Arithmetic: bf16-exact (dispatchPolicyTag 7: the accumulator the bf16 entry rounds, bit for bit) or strict (3: the oracle's fp32).
+ *   tiling == NULL -> dga_tiling_fp32_out(): bf16-exact, or strict when $DGA_DEFAULT_POLICY is "strict"; any other process default
+ *   ("fast", "auto", the _ue8m0 forms) gives bf16-exact for this entry.  A tiling is checked by dga_tiling_check_fp32_out before
+ *   anything is launched.  The workspace is what the bf16 call on the same tiling needs.  Asynchronous on `stream`. */
+int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb, const float *c,
+                             float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* m_grouped_gemm_fp8_fp8_bf16_nt_masked: G independent problems
  *   a [G,m_max,K], sfa [G,m_max,KB], b [G,N,K], sfb [G,NB,KB], out [G,m_max,N];
