@@ -17,6 +17,9 @@ from .api import (  # noqa: F401
     gemm_fp8_fp8_fp32_nt,
     tiling_check_fp32_out,
     tiling_fp32_out,
+    tiling_check_wgrad,
+    tiling_wgrad,
+    wgrad_gemm_fp8_fp8_fp32_nt,
     gemm_fp8_loop_clock,
     get_bench_config,
     get_best_config,

@@ -422,8 +422,9 @@ def bench_params_fill(m: int, n: int, k: int, params6: Sequence[int]) -> list:
 
 # ----------------------------------------------------------------------------- the hot path
 
-def _dense_fp8_operands(a, sfa, b, sfb, out, out_dtype, out_name: str):
-    """The dense fp8 GEMM's argument checks (shapes, dtypes, strides); (m, n, k, lda, ldb)."""
+def _dense_fp8_operands(a, sfa, b, sfb, out, out_dtype, out_name: str, sfb_rows: bool = False):
+    """The dense fp8 GEMM's argument checks (shapes, dtypes, strides); (m, n, k, lda, ldb).  sfb_rows: sfb is [N, KB] (one scale per
+    row of B), not [ceil(N/128), KB]."""
     _fp8_bytes(a); _fp8_bytes(b)
     if a.dim() != 2 or b.dim() != 2 or out.dim() != 2:
         _fail("rank must be 2")
@@ -435,7 +436,7 @@ def _dense_fp8_operands(a, sfa, b, sfb, out, out_dtype, out_name: str):
         _fail(f"out must be [{m},{n}]")
     if out.dtype != out_dtype:
         _fail(f"out must be {out_name}")
-    kb, nb = (k + 127) // 128, (n + 127) // 128
+    kb, nb = (k + 127) // 128, (n if sfb_rows else (n + 127) // 128)
     if sfa.dtype != torch.float32 or sfb.dtype != torch.float32:
         _fail("scales must be float32")
     if sfa.dim() != 2 or sfa.shape[0] != m or sfa.shape[1] != kb:
@@ -530,11 +531,46 @@ def gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
     Arithmetic: "bf16_exact" (the default: the accumulator gemm_fp8_fp8_bf16_nt rounds, bit for bit) or "strict" (strict=True: the
     oracle's fp32 result, bit for bit).  "fast", "auto" and the _ue8m0 policies have no fp32 epilogue and raise; a process default
     ($DGA_DEFAULT_POLICY) of "strict" gives strict, any other gives bf16_exact."""
+    _fp32_out_call("gemm_fp8_fp8_fp32_nt", lhs, rhs, out, c, tiling_, sync, strict, policy, zero_padded, sfb_rows=False)
+
+
+def tiling_wgrad(m: int, n: int, k: int) -> Tiling:
+    """dga_tiling_wgrad: the default tiling of wgrad_gemm_fp8_fp8_fp32_nt -- tiling_fp32_out's pick, with the builds that have no
+    per-row-sfb form (workgroup split-K and its decode / register builds, one-launch Stream-K) mapped onto the same tile's two-launch
+    split-K or plain raster; the strict tag under $DGA_DEFAULT_POLICY=strict."""
+    t = Tiling()
+    p = _problem(m, n, k, 1, 0)
+    _lib.check(_lib.lib().dga_tiling_wgrad(ctypes.byref(p), ctypes.byref(t)), "tiling_wgrad")
+    return t
+
+
+def tiling_check_wgrad(t: Tiling) -> int:
+    """dga_tiling_check_wgrad: 0 if wgrad_gemm_fp8_fp8_fp32_nt takes this tiling, else the status it returns before any launch."""
+    return int(_lib.lib().dga_tiling_check_wgrad(ctypes.byref(t)))
+
+
+def wgrad_gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torch.Tensor, torch.Tensor], out: torch.Tensor,
+                               c: Optional[torch.Tensor] = None, tiling_: Optional[Tiling] = None, sync: bool = False,
+                               strict: bool = False, policy: Optional[str] = None,
+                               zero_padded: Optional[Tuple[bool, bool]] = None) -> None:
+    """Upstream DeepGEMM's weight-gradient GEMM: out[M,N] (fp32, written in place) = c[M,N] (fp32, optional) + (A[M,K] fp8,
+    sfa[M,ceil(K/128)]) x (B[N,K] fp8, sfb[N,ceil(K/128)])^T, with per-1x128 scales on BOTH operands -- one sfb per row of B per
+    128-wide k block, what per_token_cast_to_fp8 returns for an activation.  For dW = dY^T . X: lhs = per_token_cast_to_fp8(dY^T),
+    rhs = per_token_cast_to_fp8(X^T), K = tokens, c=out to accumulate micro-batches.
+
+    Everything else -- row-strided views, zero_padded, c, in-place use, policies ("bf16_exact" default, "strict") -- is
+    gemm_fp8_fp8_fp32_nt's; "fast", "auto" and the _ue8m0 policies raise.  The promotion scale of an output is fl(sfa[m] * sfb[n]):
+    with every row of a 128-row block of B on one scale the result is gemm_fp8_fp8_fp32_nt's on the same tiling, bit for bit."""
+    _fp32_out_call("wgrad_gemm_fp8_fp8_fp32_nt", lhs, rhs, out, c, tiling_, sync, strict, policy, zero_padded, sfb_rows=True)
+
+
+def _fp32_out_call(name: str, lhs, rhs, out, c, tiling_, sync, strict, policy, zero_padded, sfb_rows: bool) -> None:
+    """gemm_fp8_fp8_fp32_nt (sfb_rows=False) and wgrad_gemm_fp8_fp8_fp32_nt (sfb_rows=True): checks, plan, launch."""
     a, sfa = lhs
     b, sfb = rhs
-    _require(policy is None or policy in _FP32_OUT_POLICIES, f"gemm_fp8_fp8_fp32_nt: policy must be one of {list(_FP32_OUT_POLICIES)}")
+    _require(policy is None or policy in _FP32_OUT_POLICIES, f"{name}: policy must be one of {list(_FP32_OUT_POLICIES)}")
     _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r" % (policy,))
-    m, n, k, lda, ldb = _dense_fp8_operands(a, sfa, b, sfb, out, torch.float32, "float32")
+    m, n, k, lda, ldb = _dense_fp8_operands(a, sfa, b, sfb, out, torch.float32, "float32", sfb_rows)
     if k == 0:
         lda = ldb = 0   # (a zero-width view has no meaningful row stride: nothing is read, out = c)
     if c is not None:
@@ -554,12 +590,13 @@ def gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
     with _device_guard(a, b, sfa, sfb, out, *(() if c is None else (c,))):
         index = out.device.index
         if tiling_ is None:
-            key = ("fp32_out", index, m, n, k, strict, policy)   # (the output kind is part of the key: never a bf16 call's plan)
+            # (the output kind and the scale layout are part of the key: never a bf16 call's plan, nor the other fp32 entry's)
+            key = ("wgrad" if sfb_rows else "fp32_out", index, m, n, k, strict, policy)
             tiling_ = _PLANS.get(key)
             if tiling_ is None:
                 if len(_PLANS) > 4096:
                     _PLANS.clear()
-                tiling_ = _PLANS[key] = _with_policy(tiling_fp32_out(m, n, k), strict, policy)
+                tiling_ = _PLANS[key] = _with_policy((tiling_wgrad if sfb_rows else tiling_fp32_out)(m, n, k), strict, policy)
         else:
             tiling_ = _with_policy(tiling_, strict, policy)
         stream = _stream_of(index)
@@ -567,11 +604,11 @@ def gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
         flags = 0
         if strided:
             flags = (_lib.ROWS_A_ZERO_PADDED if zero_padded[0] else 0) | (_lib.ROWS_B_ZERO_PADDED if zero_padded[1] else 0)
-        rc = _lib.lib().dga_gemm_fp8_fp8_fp32_nt(a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(),
-                                                 None if c is None else c.data_ptr(), out.data_ptr(), m, n, k, flags,
-                                                 ctypes.byref(tiling_), ws_ptr, ws_bytes, stream)
+        entry = _lib.lib().dga_wgrad_gemm_fp8_fp8_fp32_nt if sfb_rows else _lib.lib().dga_gemm_fp8_fp8_fp32_nt
+        rc = entry(a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(), None if c is None else c.data_ptr(),
+                   out.data_ptr(), m, n, k, flags, ctypes.byref(tiling_), ws_ptr, ws_bytes, stream)
         if rc:
-            _lib.check(rc, "gemm_fp8_fp8_fp32_nt")
+            _lib.check(rc, name)
         if sync:
             torch.cuda.current_stream(out.device).synchronize()
 

@@ -20,6 +20,7 @@ template <int BM, int BN, int WM, int WN, int ST = 2, int LCW = 0>
 struct GemmCfg {
     static constexpr int kBM = BM, kBN = BN, kWM = WM, kWN = WN;
     static constexpr bool kLC = LCW > 0;
+    static constexpr bool kSfbRows = false;   // SfbRowsCfg below: one sfb per row of B
     static constexpr int NT = (WM * WN + LCW) * 64;
     static constexpr int TM = BM / WM / 16;  // m-tiles (16 rows) per wave
     static constexpr int TN = BN / WN / 16;  // n-tiles per wave (even)
@@ -44,6 +45,21 @@ struct GemmCfg {
     static_assert((A_ROWS * 8) % DNT == 0 && (BN * 8) % DNT == 0, "whole wave-instructions per tile");
     static_assert(BN / 128 + (BN % 128 != 0) <= 8, "sfb slots");
 };
+
+// The same tile with per-row B scales (sfb [N, KB], the weight-gradient entry): the scale piece of a stage carries the BM sfa rows and
+// then the BN sfb rows of the tile's columns, padded to whole wave-instructions
+template <class Cfg>
+struct SfbRowsCfg : Cfg {
+    static constexpr bool kSfbRows = true;
+    static constexpr int SC_SLOTS = ((Cfg::kBM + Cfg::kBN + Cfg::DNT - 1) / Cfg::DNT) * Cfg::DNT;
+    static constexpr int SC_BYTES = SC_SLOTS * 4;
+    static constexpr int STAGE_BYTES = Cfg::A_BYTES + Cfg::B_BYTES + SC_BYTES;
+    static constexpr int LDS_BYTES = Cfg::STAGES * STAGE_BYTES;
+    static constexpr int SC_ITERS = SC_SLOTS / Cfg::DNT;
+    static constexpr int LOADS_PER_STAGE = Cfg::A_ITERS + Cfg::B_ITERS + SC_ITERS;
+};
+template <class Cfg, int SFB_ROWS>
+using StageCfg = typename std::conditional<SFB_ROWS == 1, SfbRowsCfg<Cfg>, Cfg>::type;
 
 // LDS image: row r of a tile is 128 bytes = 8 chunks of 16 B; chunk c is stored at
 // chunk position c ^ x(r).  x is chosen per operand so that the 16-lane groups of

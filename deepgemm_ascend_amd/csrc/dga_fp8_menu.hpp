@@ -68,6 +68,12 @@ int launch_bf16x_f32(const GemmParams &p, hipStream_t stream);
 #define DGA_MENU_EXTERN_BX_F32(BM, BN, WM, WN, ST, PP) \
     extern template int launch_bf16x_f32<GemmCfg<BM, BN, WM, WN, ST>>(const GemmParams &, hipStream_t);
 DGA_MENU_BX(DGA_MENU_EXTERN_BX_F32)
+// ... with fp32 rows and per-row sfb (SFB_ROWS = 1; dga_wgrad_gemm_fp8_fp8_fp32_nt): dense rasters, split-K slab pass, quarter tiles
+template <class Cfg>
+int launch_bf16x_rows(const GemmParams &p, hipStream_t stream);
+#define DGA_MENU_EXTERN_BX_ROWS(BM, BN, WM, WN, ST, PP) \
+    extern template int launch_bf16x_rows<GemmCfg<BM, BN, WM, WN, ST>>(const GemmParams &, hipStream_t);
+DGA_MENU_BX(DGA_MENU_EXTERN_BX_ROWS)
 
 // image builds of the bf16-exact policy (gemm_fp8_bf16x_image_kernel.hpp; dga_launch_menu_f.hip): 128 x 256 tile, both operands
 // converted once per workgroup into a bf16 LDS image; waves = 8 (two per SIMD, 64 x 64 wave tiles) or 4 (one per SIMD, 64 x 128).  Dense and masked-grouped rasters (split-K too);
@@ -76,6 +82,7 @@ int launch_bf16x_image(const GemmParams &p, int waves, hipStream_t stream);
 // the persistent form of the 128 x 256 in-register build (dense / masked grouped rasters); DGA_E_TILING: not a launch it takes
 int launch_bf16x_persistent(const GemmParams &p, hipStream_t stream);
 int launch_bf16x_persistent_f32(const GemmParams &p, hipStream_t stream);   // ... its fp32-output form (dense)
+int launch_bf16x_persistent_rows(const GemmParams &p, hipStream_t stream);  // ... and that with per-row sfb (dense)
 // the masked grouped layout's kernel (gemm_fp8_bf16x_grouped_kernel.hpp; dga_launch_menu_l.hip): two k blocks in flight, per-m-tile row skipping
 int launch_bf16x_grouped(const GemmParams &p, hipStream_t stream);
 

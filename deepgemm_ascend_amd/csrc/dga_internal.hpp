@@ -30,7 +30,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
             const int32_t *m_indices, int b_groups, int groups, int m, int n, int k, int expected_m,
             const dga_tiling_t *tiling, void *workspace, size_t workspace_bytes, hipStream_t stream,
             unsigned long long *clock_stamps, const Fp8Indexed *ix, const Fp8Strided *sd = nullptr, bool out_f32 = false,
-            const float *c_in = nullptr);
+            const float *c_in = nullptr, bool sfb_rows = false);
 // compiled fp8 kernel menu (dga_launch.hip)
 int variant_count();
 void variant_info(int i, int *bm, int *bn, int *wm, int *wn, int *lds);

@@ -101,8 +101,10 @@ struct Bf16xVariant {
     int bm, bn;
     int (*launch)(const GemmParams &, hipStream_t);
     int (*launch_f32)(const GemmParams &, hipStream_t);   // the same build with fp32 rows (+ C): dga_gemm_fp8_fp8_fp32_nt
+    int (*launch_rows)(const GemmParams &, hipStream_t);  // ... and with per-row sfb: dga_wgrad_gemm_fp8_fp8_fp32_nt
 };
-#define DGA_BX_VARIANT(BM, BN, WM, WN) {BM, BN, &launch_bf16x<GemmCfg<BM, BN, WM, WN, 3>>, &launch_bf16x_f32<GemmCfg<BM, BN, WM, WN, 3>>}
+#define DGA_BX_VARIANT(BM, BN, WM, WN) {BM, BN, &launch_bf16x<GemmCfg<BM, BN, WM, WN, 3>>, &launch_bf16x_f32<GemmCfg<BM, BN, WM, WN, 3>>, \
+                                        &launch_bf16x_rows<GemmCfg<BM, BN, WM, WN, 3>>}
 static const Bf16xVariant kBf16xVariants[] = {
     DGA_BX_VARIANT(128, 256, 2, 4), DGA_BX_VARIANT(128, 128, 2, 2), DGA_BX_VARIANT(64, 256, 1, 4), DGA_BX_VARIANT(64, 128, 1, 4),
     DGA_BX_VARIANT(32, 128, 1, 4),
@@ -225,12 +227,14 @@ static int (*find_clock_build(const Variant *v, int policy))(const GemmParams &,
 // wave go to clock_stamps.
 // ix != nullptr: indexed masked-grouped form (a / sfa / out are flat row buffers addressed through ix->row_index).
 // out_f32: fp32 rows (dense only; dga_gemm_fp8_fp8_fp32_nt), c_in the optional fp32 addend (may be out)
+// sfb_rows (with out_f32; dga_wgrad_gemm_fp8_fp8_fp32_nt): sfb is [N, KB], one scale per row of B -- the SFB_ROWS builds
 int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, void *out,
             const int32_t *masked_m, const int32_t *m_indices, int b_groups, int groups, int m, int n, int k,
             int expected_m, const dga_tiling_t *tiling, void *workspace, size_t workspace_bytes,
             hipStream_t stream, unsigned long long *clock_stamps, const Fp8Indexed *ix, const Fp8Strided *sd, bool out_f32,
-            const float *c_in)
+            const float *c_in, bool sfb_rows)
 {
+    if (sfb_rows && !out_f32) return DGA_E_SHAPE;
     if (out_f32 && (groups != 1 || b_groups != 1 || masked_m || m_indices || ix || clock_stamps)) return DGA_E_SHAPE;
     if (m < 0 || n < 0 || k < 0 || groups < 0 || b_groups < 0) return DGA_E_SHAPE;
     if (groups == 0 || m == 0 || n == 0) return DGA_OK;  // empty problem: nothing to write
@@ -246,7 +250,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         pr.layoutTagC = DGA_LAYOUT_ROW_MAJOR; pr.dtype = DGA_DT_FP8_E4M3FN;
         pr.flags = m_indices ? DGA_PROBLEM_CONTIGUOUS_M : 0;
         if (out_f32) {   // the fp32 entry's own selector: the bf16-exact pick (strict under a strict process default)
-            if (int rc = dga_tiling_fp32_out(&pr, &local)) return rc;
+            if (int rc = sfb_rows ? dga_tiling_wgrad(&pr, &local) : dga_tiling_fp32_out(&pr, &local)) return rc;
             tiling = &local;
         } else {
         // A call that names no tiling runs the policy whose outputs stay inside the operator's contract (within 2 bf16 ULP of the
@@ -267,7 +271,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         tiling = &local;
         }
     }
-    if (int rc = out_f32 ? dga_tiling_check_fp32_out(tiling) : check_tiling(*tiling)) return rc;
+    if (int rc = sfb_rows ? dga_tiling_check_wgrad(tiling) : out_f32 ? dga_tiling_check_fp32_out(tiling) : check_tiling(*tiling)) return rc;
     // DGA_POLICY_UE8M0_SCALES: a flag beside the schedule -- the caller promises power-of-two scales; the tile builds that carry
     // the scales in the matrix instruction's E8M0 operands run where they exist (launch_ue8m0), everything else reads the tag
     // without the flag
@@ -300,7 +304,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     p.b_groups = b_groups;
     p.m = m; p.n = n; p.k = k;
     p.kb_n = (k + 127) / 128;
-    p.nb_n = (n + 127) / 128;
+    p.nb_n = sfb_rows ? n : (n + 127) / 128;   // (rows of sfb)
     p.lda = k; p.ldb = k; p.ldc = n;
     p.a_gs = static_cast<int64_t>(m) * k;
     p.b_gs = static_cast<int64_t>(n) * k;
@@ -359,8 +363,13 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         const int64_t tiles128 = static_cast<int64_t>((m + 127) / 128) * ((n + 127) / 128);
         if (groups == 1 && !masked_m && !m_indices && !ix && tiles128 >= 2 * static_cast<int64_t>(device_cus())) {
             p.tiles_m = (m + 127) / 128;
-            if (out_f32) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<4, 1>), dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
+            if (sfb_rows) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<4, 1, 1>), dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
+            else if (out_f32) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<4, 1>), dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
             else hipLaunchKernelGGL(gemm_fp8_strict_nt_kernel<4>, dim3(static_cast<unsigned>(tiles128)), block, 0, stream, p);
+        } else
+        if (sfb_rows) {
+            if (bm == 64) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<2, 1, 1>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<1, 1, 1>), grid, block, 0, stream, p);
         } else
         if (out_f32) {
             if (bm == 64) hipLaunchKernelGGL((gemm_fp8_strict_nt_kernel<2, 1>), grid, block, 0, stream, p);
@@ -457,7 +466,8 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     if (!fast_ok) {
         // K not a multiple of the 16-byte DMA chunk and no workspace to pad into (or k == 0): element-wise kernel
         dim3 grid((n + 15) / 16, (m + 15) / 16, groups);
-        if (out_f32) hipLaunchKernelGGL(gemm_fp8_blockscaled_nt_generic_kernel<1>, grid, dim3(256), 0, stream, p);
+        if (sfb_rows) hipLaunchKernelGGL((gemm_fp8_blockscaled_nt_generic_kernel<1, 1>), grid, dim3(256), 0, stream, p);
+        else if (out_f32) hipLaunchKernelGGL(gemm_fp8_blockscaled_nt_generic_kernel<1>, grid, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(gemm_fp8_blockscaled_nt_generic_kernel<>, grid, dim3(256), 0, stream, p);
         DGA_HIP_TRY(hipGetLastError());
         return DGA_OK;
@@ -510,8 +520,9 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
     // ... and, under the bf16-exact policy, its form for up to a few 64-row tiles (tiling.build = DGA_BUILD_BX_DECODE;
     // gemm_fp8_bf16x_dsk_kernel.hpp): two k groups per workgroup, splitkFactor workgroups per tile through the workspace.  What it does
     // not take runs the two-launch split-K of the same tiling below.
-    if (bf16x && !bx_ue8m0 && !clock_stamps && groups == 1 && !masked_m && !m_indices && !ix && tiling->kernelSerial == DGA_KERNEL_SPLITK_WORKGROUP &&
-        tiling->build == DGA_BUILD_BX_DECODE) {
+    // (no per-row-sfb form of the builds in this block or of Stream-K: dga_tiling_check_wgrad refuses tilings that name them)
+    if (bf16x && !bx_ue8m0 && !clock_stamps && groups == 1 && !masked_m && !m_indices && !ix && !sfb_rows &&
+        tiling->kernelSerial == DGA_KERNEL_SPLITK_WORKGROUP && tiling->build == DGA_BUILD_BX_DECODE) {
         const int64_t dsk_tiles = static_cast<int64_t>((m + 63) / 64) * ((n + 127) / 128);
         const int s = bx_dsk_splits(dsk_tiles, p.kb_n, tiling->splitkFactor, static_cast<int>(device_cus()));
         const size_t need = s > 0 ? bx_dsk_workspace_bytes(dsk_tiles, s) : 0;
@@ -521,7 +532,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
             if (rc != DGA_E_TILING) return rc;
         }
     }
-    if (bf16x && !clock_stamps && groups == 1 && !masked_m && !m_indices && !ix && tiling->build != DGA_BUILD_BX_DECODE &&
+    if (bf16x && !clock_stamps && groups == 1 && !masked_m && !m_indices && !ix && !sfb_rows && tiling->build != DGA_BUILD_BX_DECODE &&
         (wsk_env >= 0 ? wsk_env != 0 : tiling->kernelSerial == DGA_KERNEL_SPLITK_WORKGROUP)) {
         const int rc = launch_wsk_dma(p, stream, 1, out_f32);   // the bf16-exact policy has the LDS-DMA build only (M <= 32)
         if (rc != DGA_E_TILING) return rc;
@@ -556,7 +567,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
             pk.groups = s;  // grid = splitk x tiles
             int rc = DGA_E_TILING;
             if (out_f32) {   // the slabs are the bf16 build's (its split-K store path); the fp32 combine adds C once
-                rc = vx->launch(pk, stream);
+                rc = sfb_rows ? vx->launch_rows(pk, stream) : vx->launch(pk, stream);
                 if (rc != DGA_OK) return rc;
                 const int64_t mn = static_cast<int64_t>(m) * n;
                 hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3(static_cast<unsigned>((mn / 8 + 255) / 256 + 1)), dim3(256), 0, stream,
@@ -594,14 +605,15 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
             if (tail > 0 && tail * 2 <= cus && main_tiles > 0 && vq && vq->bm == 64 && vq->bn == 128) {
                 GemmParams pm = p;
                 pm.launch_tiles = main_tiles;
-                int rc = out_f32 ? launch_bf16x_persistent_f32(pm, stream) : launch_bf16x_persistent(pm, stream);    // (DGA_E_TILING: a launch it does not take -- one k block)
-                if (rc == DGA_E_TILING) rc = out_f32 ? vx->launch_f32(pm, stream) : vx->launch(pm, stream);
+                int rc = sfb_rows ? launch_bf16x_persistent_rows(pm, stream)
+                         : out_f32 ? launch_bf16x_persistent_f32(pm, stream) : launch_bf16x_persistent(pm, stream);    // (DGA_E_TILING: a launch it does not take -- one k block)
+                if (rc == DGA_E_TILING) rc = sfb_rows ? vx->launch_rows(pm, stream) : out_f32 ? vx->launch_f32(pm, stream) : vx->launch(pm, stream);
                 if (rc != DGA_OK) return rc;
                 GemmParams pt = p;  // tiles_m / tiles_n / raster_group stay those of the parent raster
                 pt.tail_begin = main_tiles;
                 pt.tail_sub = 2;
                 pt.launch_tiles = tail * 4;
-                return out_f32 ? vq->launch_f32(pt, stream) : vq->launch(pt, stream);
+                return sfb_rows ? vq->launch_rows(pt, stream) : out_f32 ? vq->launch_f32(pt, stream) : vq->launch(pt, stream);
             }
         }
         // the 128 x 256 tile's persistent form (gemm_fp8_bf16x_persistent_kernel.hpp; same bits).  The dispatcher hides most of a tile
@@ -617,7 +629,7 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         // runs them, the last partial round cut along K with fp32 partial tiles through the workspace.  What it does not take (no partial
         // round, no workspace, a CU mask) runs the builds below.
         if (tiling->kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH && vx->bm == 128 && vx->bn == 256 && !clock_stamps && groups == 1 &&
-            !masked_m && !m_indices && !ix) {
+            !masked_m && !m_indices && !ix && !sfb_rows) {
             const size_t need = bx_streamk_workspace_bytes();
             if (uint8_t *sk_ws = carve(need)) {
                 const int rc = launch_bf16x_streamk(p, sk_ws, need, stream, out_f32);
@@ -636,10 +648,11 @@ int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, vo
         const bool pays = tiles > cus;
         if (vx->bm == 128 && vx->bn == 256 && !clock_stamps &&
             (bxp_env >= 0 ? bxp_env != 0 : (tiling->build == DGA_BUILD_BX_PERSISTENT || (tiling->build != DGA_BUILD_BX_ONE_TILE && pays)))) {
-            const int rc = out_f32 ? launch_bf16x_persistent_f32(p, stream) : launch_bf16x_persistent(p, stream);
+            const int rc = sfb_rows ? launch_bf16x_persistent_rows(p, stream)
+                         : out_f32 ? launch_bf16x_persistent_f32(p, stream) : launch_bf16x_persistent(p, stream);
             if (rc != DGA_E_TILING) return rc;
         }
-        return out_f32 ? vx->launch_f32(p, stream) : vx->launch(p, stream);
+        return sfb_rows ? vx->launch_rows(p, stream) : out_f32 ? vx->launch_f32(p, stream) : vx->launch(p, stream);
     }
     auto launch_main = [&](const GemmParams &q) -> int {
         // (the persistent loader-wave form has no hardware-scale build: on the grouped weight stream -- bound by HBM, not by the
@@ -750,9 +763,21 @@ int dga_tiling_check_fp32_out(const dga_tiling_t *tiling)
     }
 }
 
-int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb, const float *c,
-                             float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
-                             size_t workspace_bytes, void *stream)
+int dga_tiling_check_wgrad(const dga_tiling_t *tiling)
+{
+    if (int rc = dga_tiling_check_fp32_out(tiling)) return rc;
+    if (tiling->dispatchPolicyTag == DGA_POLICY_STRICT) return DGA_OK;
+    // no per-row-sfb form: the workgroup split-K (and its decode / register builds) and the one-launch Stream-K
+    if (tiling->kernelSerial == DGA_KERNEL_SPLITK_WORKGROUP || tiling->kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH ||
+        tiling->build == DGA_BUILD_BX_DECODE || tiling->build == DGA_BUILD_WSK_REGISTER)
+        return DGA_E_TILING;
+    return DGA_OK;
+}
+
+// the fp32-output entries: sfb_rows = false -> dga_gemm_fp8_fp8_fp32_nt, true -> dga_wgrad_gemm_fp8_fp8_fp32_nt
+static int fp32_out_entry(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb, const float *c,
+                          float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
+                          size_t workspace_bytes, void *stream, bool sfb_rows)
 {
     if (m < 0 || n < 0 || k < 0) return DGA_E_SHAPE;
     if (m == 0 || n == 0) return DGA_OK;
@@ -763,11 +788,25 @@ int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const
         if (co < oo + bytes && oo < co + bytes) return DGA_E_SHAPE;
     }
     if (tiling)
-        if (int rc = dga_tiling_check_fp32_out(tiling)) return rc;
+        if (int rc = sfb_rows ? dga_tiling_check_wgrad(tiling) : dga_tiling_check_fp32_out(tiling)) return rc;
     const dga::Fp8Strided sd{lda, ldb, flags};
     const bool strided = lda != k || ldb != k;   // (contiguous rows: the path of dga_gemm_fp8_fp8_bf16_nt)
     return dga::run_fp8(a, sfa, b, sfb, out, nullptr, nullptr, 1, 1, m, n, k, 0, tiling, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream), nullptr, nullptr, strided ? &sd : nullptr, true, c);
+                        static_cast<hipStream_t>(stream), nullptr, nullptr, strided ? &sd : nullptr, true, c, sfb_rows);
+}
+
+int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb, const float *c,
+                             float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    return fp32_out_entry(a, lda, sfa, b, ldb, sfb, c, out, m, n, k, flags, tiling, workspace, workspace_bytes, stream, false);
+}
+
+int dga_wgrad_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb,
+                                   const float *c, float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    return fp32_out_entry(a, lda, sfa, b, ldb, sfb, c, out, m, n, k, flags, tiling, workspace, workspace_bytes, stream, true);
 }
 
 int dga_gemm_fp8_fp8_bf16_nt(const void *a, const float *sfa, const void *b, const float *sfb, void *out, int m,

@@ -4,11 +4,11 @@
 #include "gemm_fp8_bf16x_persistent_kernel.hpp"
 namespace dga {
 
-template <bool KTAIL, int OUT>
+template <bool KTAIL, int OUT, int SFB_ROWS = 0>
 static int launch_bf16x_persistent_one(const GemmParams &p, hipStream_t stream)
 {
     typedef GemmCfg<128, 256, 2, 4, 3> Cfg;
-    auto kfn = gemm_fp8_bf16x_persistent_kernel<KTAIL, OUT>;
+    auto kfn = gemm_fp8_bf16x_persistent_kernel<KTAIL, OUT, SFB_ROWS>;
     static std::once_flag once[64];
     static hipError_t attr_err[64];
     int dev = 0;
@@ -39,5 +39,12 @@ int launch_bf16x_persistent_f32(const GemmParams &p, hipStream_t stream)
 {
     if (p.tail_sub || p.m_indices || p.row_index || p.masked_m || p.groups != 1 || p.splitk > 1 || p.kb_n < 2) return DGA_E_TILING;
     return (p.k % 128) ? launch_bf16x_persistent_one<true, 1>(p, stream) : launch_bf16x_persistent_one<false, 1>(p, stream);
+}
+
+// fp32 rows (+ C) with per-row sfb: dense rasters, as above
+int launch_bf16x_persistent_rows(const GemmParams &p, hipStream_t stream)
+{
+    if (p.tail_sub || p.m_indices || p.row_index || p.masked_m || p.groups != 1 || p.splitk > 1 || p.kb_n < 2) return DGA_E_TILING;
+    return (p.k % 128) ? launch_bf16x_persistent_one<true, 1, 1>(p, stream) : launch_bf16x_persistent_one<false, 1, 1>(p, stream);
 }
 }

@@ -1246,6 +1246,19 @@ int dga_tiling_fp32_out(const dga_problem_t *problem, dga_tiling_t *out)
     return DGA_OK;
 }
 
+int dga_tiling_wgrad(const dga_problem_t *problem, dga_tiling_t *out)
+{
+    if (int rc = dga_tiling_fp32_out(problem, out)) return rc;
+    if (out->dispatchPolicyTag == DGA_POLICY_STRICT) return DGA_OK;
+    // builds without a per-row-sfb path: the workgroup split-K (the decode and register builds are its names) becomes the two-launch
+    // split-K of the same tile and factor, the one-launch Stream-K the tile's plain raster (persistent where it pays)
+    if (out->kernelSerial == DGA_KERNEL_SPLITK_WORKGROUP || out->kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH) {
+        out->kernelSerial = out->splitkFactor > 1 ? DGA_KERNEL_STREAMK : DGA_KERNEL_COMMON;
+    }
+    if (out->build == DGA_BUILD_BX_DECODE || out->build == DGA_BUILD_WSK_REGISTER) out->build = DGA_BUILD_DEFAULT;
+    return DGA_OK;
+}
+
 int dga_tiling_cache_open(const char *csv_path) { return Cache::instance().open(csv_path); }
 int dga_tiling_cache_clear(void) { Cache::instance().clear(); return DGA_OK; }
 int dga_tiling_cache_size(void) { return Cache::instance().size(); }

@@ -18,8 +18,8 @@ __device__ __forceinline__ float e4m3fn_to_f32(uint8_t v)
     return (v & 0x80) ? -r : r;
 }
 
-// OUT = 1: fp32 rows, + C (K = 0: out = C exactly)
-template <int OUT = 0>
+// OUT = 1: fp32 rows, + C (K = 0: out = C exactly).  SFB_ROWS = 1 (with OUT = 1): sfb is [N, KB], one scale per row of B
+template <int OUT = 0, int SFB_ROWS = 0>
 __global__ void __launch_bounds__(256) gemm_fp8_blockscaled_nt_generic_kernel(const GemmParams p)
 {
     __shared__ float lut[256];
@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(256) gemm_fp8_blockscaled_nt_generic_kernel(co
     const uint8_t *ar = p.a + (int64_t)g * p.a_gs + mrow * p.lda;
     const uint8_t *br = p.b + (int64_t)bg * p.b_gs + (int64_t)n * p.ldb;
     const float *sa = p.sfa + (int64_t)g * p.sfa_gs + mrow * p.sfa_ld;
-    const float *sb = p.sfb + (int64_t)bg * p.sfb_gs + (int64_t)(n / 128) * p.kb_n;
+    const float *sb = p.sfb + (int64_t)bg * p.sfb_gs + (int64_t)(SFB_ROWS ? n : n / 128) * p.kb_n;
     float acc = 0.f;
     for (int kb = 0; kb < p.kb_n; ++kb) {
         const int k0 = kb * 128, k1 = min(p.k, k0 + 128);

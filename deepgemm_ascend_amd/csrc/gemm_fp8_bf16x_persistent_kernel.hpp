@@ -23,7 +23,9 @@
 
 namespace dga {
 
-template <bool KTAIL, int OUT = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
+// OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32.  SFB_ROWS = 1 (with OUT = 1): per-row sfb [N, KB], as gemm_fp8_kernel.hpp's
+// SFB_ROWS -- the scale piece (512 slots) carries the BM sfa rows and the BN sfb rows, the promotion scale is fl(sfa[m] * sfb[n])
+template <bool KTAIL, int OUT = 0, int SFB_ROWS = 0>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
 {
@@ -31,6 +33,7 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
     constexpr int BM = Cfg::kBM, BN = Cfg::kBN, WN = Cfg::kWN, TM = Cfg::TM, TN = Cfg::TN, DNT = Cfg::DNT;
     constexpr int NL = Cfg::LOADS_PER_STAGE, TILES = TM * TN, G = 4 * TM, LAGT = 2, RING = 4;
     static_assert(Cfg::NT == 512 && DNT == 512 && TILES % RING == 0 && 4 * TILES >= 4 + NL && 16 % G == 0, "the MATH = 1 schedule");
+    static_assert(SFB_ROWS == 0 || (OUT == 1 && BM + BN <= DNT && TM >= LAGT), "per-row sfb: fp32 rows, one scale piece");
     typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
@@ -90,8 +93,11 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
         const int row = (it * DNT + tid) >> 3;
         return (uint32_t)min(row, p.n - 1 - t.n0) * (uint32_t)p.ldb + b_col;
     };
-    auto sc_ptr = [&](const Tile &t) -> const float * {   // slot tid: [0, BM) sfa rows of the tile, then its sfb blocks
+    auto sc_ptr = [&](const Tile &t) -> const float * {   // slot tid: [0, BM) sfa rows of the tile, then its sfb blocks (SFB_ROWS: rows)
         const float *SFA = p.sfa + (int64_t)t.g * p.sfa_gs, *SFB = p.sfb + (int64_t)t.g * p.sfb_gs;
+        if constexpr (SFB_ROWS == 1)
+            return tid < BM ? SFA + (int64_t)min(t.m0 + tid, t.M - 1) * p.sfa_ld
+                            : SFB + (int64_t)min(t.n0 + min(tid - BM, BN - 1), p.nb_n - 1) * p.kb_n;
         return tid < BM ? SFA + (int64_t)min(t.m0 + tid, t.M - 1) * p.sfa_ld
                         : SFB + (int64_t)min(t.n0 / 128 + min(tid - BM, 7), p.nb_n - 1) * p.kb_n;
     };
@@ -159,12 +165,18 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
     const int b_off1 = Cfg::A_BYTES + b_row * 128 + (((kg + 4) ^ swz_b(b_row)) * 16);
     const int sa_off = Cfg::A_BYTES + Cfg::B_BYTES + (wm * (BM / Cfg::kWM) + li) * 4;
     const int sb_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + (wn * (BN / WN)) / 128) * 4;
+    const int sbr_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + wn * (BN / WN) + 8 * kg) * 4;   // SFB_ROWS: gemm_fp8_kernel.hpp
+    auto sbr_nt = [](int nt) { return (32 * (nt >> 1) + 4 * (nt & 1)) * 4; };
 
     v4f acc[TM][TN];
     v4f part[RING];
     v4i afx[TM][4], bfx[2][4];      // bf16 fragments: [q] = the 8 bf16 of MFMA q of the chain
     v4i braw[2], araw[2][2];         // raw e4m3 bytes: [0] = bytes [16 kg, +16), [1] = bytes [64 + 16 kg, +16)
     float s_cur[TM], s_old[TM], s_nxt[TM];
+    v4f sbv[TN];   // SFB_ROWS: the sfb of the lane's columns per n-tile (gemm_fp8_kernel.hpp); finite from the start: 0 * sbv
+    if constexpr (SFB_ROWS == 1)   // (only there: an initialised array nobody reads still moves the other builds' schedule)
+#pragma unroll
+        for (int i = 0; i < TN; ++i) sbv[i] = v4f{0.f, 0.f, 0.f, 0.f};
     auto clear_tile = [&]() {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -191,6 +203,8 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
             araw[mt & 1][1] = *(const v4i *)(st + a_off1 + mt * 2048);
 #pragma unroll
             for (int c = 0; c < 16; ++c) convert(araw[mt & 1], afx[mt], c);
+            if constexpr (SFB_ROWS == 1) s_cur[mt] = *(const float *)(st + sa_off + mt * 64);
+            else
             s_cur[mt] = *(const float *)(st + sa_off + mt * 64) * sfb0;
             s_nxt[mt] = 0.f;
         }
@@ -262,13 +276,22 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
                     for (int c = 0; c < 4; ++c) convert(araw[(TM - 1) & 1], afx[TM - 1], 4 * q + c);
                 }
                 if (u == 4 * TILES - 8) {
+                    if constexpr (SFB_ROWS == 1) {
+#pragma unroll
+                        for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64);
+                    } else {
                     const float sfbn = *(const float *)(sn + sb_off);
 #pragma unroll
                     for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64) * sfbn;
+                    }
                 }
                 {
                     const int j = t >= LAGT ? t - LAGT : TILES + t - LAGT, jn = j / TM, jm = j % TM;
-                    const float sv = t >= LAGT ? s_cur[jm] : s_old[jm];
+                    float sv = t >= LAGT ? s_cur[jm] : s_old[jm];
+                    if constexpr (SFB_ROWS == 1) {
+                        if (mt == 0 && q == 0) sbv[nt] = *(const v4f *)(sc + sbr_off + sbr_nt(nt));
+                        sv = sv * sbv[jn][q];   // fl(sfa[m] * sfb[n])
+                    }
                     acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], sv, acc[jm][jn][q]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -298,7 +321,8 @@ gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
             for (int t = 0; t < LAGT; ++t) {
                 const int j = TILES + t - LAGT, jn = j / TM, jm = j % TM;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], s_old[jm], acc[jm][jn][q]);
+                for (int q = 0; q < 4; ++q)
+                    acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], SFB_ROWS == 1 ? s_old[jm] * sbv[jn][q] : s_old[jm], acc[jm][jn][q]);
             }
             uint16_t *C = p.out + (int64_t)T.g * p.c_gs;
             const int m_row = T.m0 + wm * (BM / Cfg::kWM) + li;

@@ -206,10 +206,16 @@ struct LoopClock {
 //         swizzled image the LDS-DMA would have written -- the computing waves are unchanged.  The counterpart of the reference's
 //         PaddingCommon kernel, which fuses the re-layout with the matmul
 //         (/root/reference/aclnn_catlass_dynamic_matmul/op_kernel/kernel/padding_common_matmul_kernel.h:33-107).
-template <class Cfg, int PP, bool KTAIL, bool CLK = false, int MATH = 0, bool UNAL = false, int OUT = 0>
-__global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const GemmParams p)
+// SFB_ROWS = 1 (OUT = 1, MATH = 1 only; dga_wgrad_gemm_fp8_fp8_fp32_nt): sfb holds one scale per ROW of B, [N, KB], and the scale
+//         piece of a stage carries the tile's BN of them (SfbRowsCfg).  The promotion scale becomes per element, fl(sfa[m] * sfb[n]),
+//         formed right at the promotion FMA where the per-row value fl(sfa[m] * sfb[n / 128]) is used otherwise: with every row of a
+//         128-row block of B on one scale the bits are those of SFB_ROWS = 0.
+template <class Cfg0, int PP, bool KTAIL, bool CLK = false, int MATH = 0, bool UNAL = false, int OUT = 0, int SFB_ROWS = 0>
+__global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const GemmParams p)
 {
+    typedef StageCfg<Cfg0, SFB_ROWS> Cfg;
     static_assert(OUT == 0 || (MATH == 1 && PP == 0 && !CLK && !UNAL), "fp32 output: the bf16-exact builds");
+    static_assert(SFB_ROWS == 0 || (OUT == 1 && MATH == 1), "per-row sfb: the fp32-output bf16-exact builds");
     static_assert(!UNAL || (Cfg::kLC && PP == 0 && MATH == 0 && KTAIL), "unaligned rows: loader waves, plain loop, fp8 matrix instruction");
     static_assert(MATH != 2 || PP != 1, "hardware-scale builds: plain or continuous loop");
     static_assert(MATH != 3 || PP == 0, "bf16-exact builds: plain loop");
@@ -351,6 +357,8 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
 #else
             sc_src[it] = SFA + (ridx ? ridx[mr] : (int64_t)mr) * p.sfa_ld;
 #endif
+        } else if constexpr (SFB_ROWS == 1) {   // [BM, BM + BN): the sfb rows of the tile's columns (p.nb_n = N), then padding
+            sc_src[it] = SFB + (int64_t)min(n0 + min(s - BM, BN - 1), p.nb_n - 1) * p.kb_n;
         } else {
             const int nb = min(n0 / 128 + min(s - BM, 7), p.nb_n - 1);
             sc_src[it] = SFB + (int64_t)nb * p.kb_n;
@@ -406,6 +414,9 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
     const int b_off1 = Cfg::A_BYTES + b_row * 128 + (((kg + 4) ^ swz_b(b_row)) * 16);
     const int sa_off = Cfg::A_BYTES + Cfg::B_BYTES + (wm * (BM / Cfg::kWM) + li) * 4;
     const int sb_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + (wn * (BN / WN)) / 128) * 4;
+    // SFB_ROWS: the sfb slots of this lane's columns in n-tile nt, n_local(nt, 4 kg + 0..3) -- one 16-byte read
+    const int sbr_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + wn * (BN / WN) + 8 * kg) * 4;
+    auto sbr_nt = [](int nt) { return (32 * (nt >> 1) + 4 * (nt & 1)) * 4; };
 
     // ---- epilogue (a lambda so that each wave-group path of the ping-pong loop ends in its own copy: no register
     //      assignment has to agree across the two paths): lane owns row m, columns n0w + 32*j + 8*(lane>>4) + [0,8)
@@ -921,7 +932,15 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
         for (int i = 0; i < RING; ++i) part[i] = v4f{0.f, 0.f, 0.f, 0.f};
         v4i afx[TM][4], bfx[2][4];      // bf16 fragments: [q] = the 8 bf16 of MFMA q of the chain
         v4i braw[2], araw[2][2];         // raw e4m3 bytes: [0] = bytes [16 kg, +16), [1] = bytes [64 + 16 kg, +16)
-        float s_cur[TM], s_old[TM], s_nxt[TM];
+        float s_cur[TM], s_old[TM], s_nxt[TM];   // fl(sfa * sfb) of the lane's m-tiles (SFB_ROWS: sfa alone)
+        // SFB_ROWS: the sfb of this lane's four columns of n-tile nt, read from the stage being consumed at the n-tile's first gap and
+        // used by the promotions LAGT tiles behind (the first LAGT tiles of a block promote the previous block's n-tile TN - 1, whose
+        // values are still here: n-tile TN - 1 is read again only at tile (TN - 1) TM >= LAGT)
+        v4f sbv[TN];
+        if constexpr (SFB_ROWS == 1)   // (only there: an initialised array nobody reads still moves the other builds' schedule)
+#pragma unroll
+            for (int i = 0; i < TN; ++i) sbv[i] = v4f{0.f, 0.f, 0.f, 0.f};
+        static_assert(SFB_ROWS == 0 || TM >= LAGT, "the lagged promotions are those of n-tile TN - 1");
         // conversion c (0..15) of a fragment: dword c >> 1 of the 32 raw bytes, half c & 1 -> dword c & 3 of MFMA (c >> 2).
         // (c is a constant after unrolling; the builtin's half selector must be an immediate)
         auto convert = [](const v4i (&raw)[2], v4i (&dst)[4], int c, float scale = 1.0f) {
@@ -949,6 +968,8 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
                 // (buffer mt & 1: block 0's first tile converts A[TM - 1] once more from the buffer it was read into)
                 araw[mt & 1][0] = *(const v4i *)(smem + a_off0 + mt * 2048);
                 araw[mt & 1][1] = *(const v4i *)(smem + a_off1 + mt * 2048);
+                if constexpr (SFB_ROWS == 1) s_cur[mt] = *(const float *)(smem + sa_off + mt * 64);
+                else
                 s_cur[mt] = *(const float *)(smem + sa_off + mt * 64) * sfb0;
 #pragma unroll
                 for (int c = 0; c < 16; ++c) convert(araw[mt & 1], afx[mt], c, UE ? s_cur[mt] : 1.0f);
@@ -1039,14 +1060,23 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
                 // the next block's scales: needed from its first promotions, LAGT tiles into it -- or (UE) by the conversions of its A
                 // fragments, which start in this block's last n-tile: read at the block's first gap (the stage has landed)
                 if (u == (UE ? 0 : 4 * TILES - 8)) {
+                    if constexpr (SFB_ROWS == 1) {
+#pragma unroll
+                        for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64);
+                    } else {
                     const float sfbn = *(const float *)(sn + sb_off);
 #pragma unroll
                     for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64) * sfbn;
+                    }
                 }
                 // promotion of tile t - LAGT, one accumulator element per gap
                 if constexpr (!UE) {
                     const int j = t >= LAGT ? t - LAGT : TILES + t - LAGT, jn = j / TM, jm = j % TM;
-                    const float sv = t >= LAGT ? s_cur[jm] : s_old[jm];
+                    float sv = t >= LAGT ? s_cur[jm] : s_old[jm];
+                    if constexpr (SFB_ROWS == 1) {
+                        if (mt == 0 && q == 0) sbv[nt] = *(const v4f *)(sc + sbr_off + sbr_nt(nt));
+                        sv = sv * sbv[jn][q];   // fl(sfa[m] * sfb[n])
+                    }
 #ifdef DGA_ABL_BX_NOFMA   // diagnostic (results are garbage): no promotion
                     asm volatile("" :: "v"(part[j % RING][q]), "v"(sv));
 #else
@@ -1070,7 +1100,8 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_kernel(const 
         for (int t = 0; t < LAGT; ++t) {
             const int j = TILES + t - LAGT, jn = j / TM, jm = j % TM;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], s_old[jm], acc[jm][jn][q]);
+            for (int q = 0; q < 4; ++q)
+                acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], SFB_ROWS == 1 ? s_old[jm] * sbv[jn][q] : s_old[jm], acc[jm][jn][q]);
         }
         }
         wait_vmcnt<0>();   // the refills past the last k block land in LDS nobody reads: drain them before the stores / exit

@@ -47,14 +47,18 @@ __device__ __forceinline__ v4i transpose_bytes_4x4(v4i w)
 // TM = m-tiles (16 rows) per wave; workgroup = 2 x 2 waves, tile (32*TM) x 128, one LDS stage, register prefetch.
 // The launcher uses TM = 2 (two workgroups per CU cover each other's barriers: 110 TFLOP/s at 4096^3 against 91 for TM = 4)
 // and TM = 1 where 64-row tiles would leave CUs idle.
-template <int TM, int OUT = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
+// SFB_ROWS = 1 (with OUT = 1; dga_wgrad_gemm_fp8_fp8_fp32_nt): sfb is [N, KB], one scale per row of B; the k block's BN of them are
+// staged beside the sfa rows and every output takes its own column's: s = fl(sfa[m] * sfb[n]), in the oracle's order as above.
+template <int TM, int OUT = 0, int SFB_ROWS = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
 __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParams p)
 {
     constexpr int BM = 32 * TM, BN = 128, TN = 4;
+    static_assert(SFB_ROWS == 0 || (OUT == 1 && BM + BN <= 256), "per-row sfb: fp32 rows, one scale per thread");
     constexpr int A_CH = BM * 8 / 256, B_CH = BN * 8 / 256;  // 16-byte chunks per thread per k block
-    __shared__ __attribute__((aligned(16))) uint8_t smem[(BM + BN) * 128 + (BM + 4) * 4];
+    constexpr int SC = SFB_ROWS ? BM + BN : BM + 4;          // scale slots
+    __shared__ __attribute__((aligned(16))) uint8_t smem[(BM + BN) * 128 + SC * 4];
     uint8_t *lds_a = smem, *lds_b = smem + BM * 128;
-    float *lds_s = (float *)(smem + (BM + BN) * 128);  // [0,BM) sfa rows, [BM] sfb
+    float *lds_s = (float *)(smem + (BM + BN) * 128);  // [0,BM) sfa rows, [BM] sfb (SFB_ROWS: [BM, BM + BN) the sfb rows of the tile's columns)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -115,6 +119,8 @@ __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParam
     if (tid < BM) {
         const int mr = min(m0 + tid, M - 1);
         s_ptr = SFA + (ridx ? ridx[mr] : (int64_t)mr) * p.sfa_ld;
+    } else if (SFB_ROWS == 1 && tid < BM + BN) {
+        s_ptr = p.sfb + (int64_t)bg * p.sfb_gs + (int64_t)min(n0 + tid - BM, p.n - 1) * p.kb_n;
     } else if (tid == BM) {
         s_ptr = SFB;   // BM <= 128 < 256 threads
     }
@@ -137,7 +143,7 @@ __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParam
             const int c = it * 256 + tid, row = c >> 3, ch = c & 7;
             *(v4i *)(lds_b + row * 128 + ((ch ^ swz_a(row)) * 16)) = transpose_bytes_4x4(rb[it]);
         }
-        if (tid <= BM) lds_s[tid] = rs;
+        if (tid <= BM || (SFB_ROWS == 1 && tid < BM + BN)) lds_s[tid] = rs;
     };
 
     v4f acc[TM][TN];
@@ -203,6 +209,19 @@ __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParam
             __builtin_amdgcn_sched_barrier(0);
         }
         // two-level dequant in the oracle's order: s = sfa * sfb (rounded), acc = acc + partial * s (two roundings)
+        if constexpr (SFB_ROWS == 1) {   // the lane's outputs are columns n0 + wn 64 + 16 nt + 4 q + 0..3
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) {
+                const float sa = lds_s[a_row + 16 * mt];
+#pragma unroll
+                for (int nt = 0; nt < TN; ++nt) {
+                    const v4f sb = *(const v4f *)(lds_s + BM + wn * 64 + 16 * nt + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[mt][nt][e] = promote_no_fma(acc[mt][nt][e], part[mt][nt][e], mul_no_fma(sa, sb[e]));
+                }
+            }
+            continue;
+        }
         const float sfb_v = lds_s[BM];
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt) {

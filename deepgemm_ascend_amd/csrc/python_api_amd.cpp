@@ -196,6 +196,38 @@ void gemm_fp8_fp8_fp32_nt(const at::Tensor &a, const at::Tensor &sfa, const at::
                                    wsb ? ws.data_ptr() : nullptr, wsb, cur_stream()), "gemm_fp8_fp8_fp32_nt");
 }
 
+// fp32 rows with per-row sfb [N, KB] (both operands per-1x128, the weight gradient), optional addend c (may be out itself):
+// dga_wgrad_gemm_fp8_fp8_fp32_nt, default tiling (dga_tiling_wgrad)
+void wgrad_gemm_fp8_fp8_fp32_nt(const at::Tensor &a, const at::Tensor &sfa, const at::Tensor &b, const at::Tensor &sfb, at::Tensor &out,
+                                const c10::optional<at::Tensor> &c)
+{
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2, "a [M,K], b [N,K]");
+    const int64_t m = a.size(0), n = b.size(0), k = a.size(1), kb = (k + 127) / 128;
+    want_fp8(a, "a"); want_fp8(b, "b");
+    want_shape(b, {n, k}, "b");
+    want_shape(out, {m, n}, "out"); want_dtype(out, at::kFloat, "out");
+    want_shape(sfa, {m, kb}, "sfa"); want_dtype(sfa, at::kFloat, "sfa");
+    want_shape(sfb, {n, kb}, "sfb"); want_dtype(sfb, at::kFloat, "sfb");
+    if (c.has_value()) {
+        want_shape(*c, {m, n}, "c"); want_dtype(*c, at::kFloat, "c");
+        same_device({&a, &sfa, &b, &sfb, &out, &*c});
+    } else {
+        same_device({&a, &sfa, &b, &sfb, &out});
+    }
+    const c10::OptionalDeviceGuard guard(at::device_of(out));
+    dga_problem_t p{};
+    p.m = m; p.n = n; p.k = k; p.groups = 1;
+    p.layoutTagA = DGA_LAYOUT_ROW_MAJOR; p.layoutTagB = DGA_LAYOUT_COLUMN_MAJOR; p.layoutTagC = DGA_LAYOUT_ROW_MAJOR;
+    p.dtype = DGA_DT_FP8_E4M3FN;
+    dga_tiling_t t{};
+    check(dga_tiling_wgrad(&p, &t), "tiling_wgrad");
+    const size_t wsb = dga_workspace_bytes(&t);
+    at::Tensor ws = scratch(out, wsb);
+    check(dga_wgrad_gemm_fp8_fp8_fp32_nt(a.data_ptr(), k, sfa.data_ptr<float>(), b.data_ptr(), k, sfb.data_ptr<float>(),
+                                         c.has_value() ? c->data_ptr<float>() : nullptr, out.data_ptr<float>(), m, n, k, 0, &t,
+                                         wsb ? ws.data_ptr() : nullptr, wsb, cur_stream()), "wgrad_gemm_fp8_fp8_fp32_nt");
+}
+
 void m_grouped_gemm_fp8_fp8_bf16_nt_masked(const at::Tensor &a, const at::Tensor &sfa, const at::Tensor &b,
                                            const at::Tensor &sfb, at::Tensor &out, const at::Tensor &masked_m,
                                            int64_t expected_m, bool strict, const std::string &policy)
@@ -271,6 +303,8 @@ PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.c
           py::arg("out"), py::arg("strict") = false, py::arg("policy") = "");
     m.def("gemm_fp8_fp8_fp32_nt", &gemm_fp8_fp8_fp32_nt, py::arg("a"), py::arg("sfa"), py::arg("b"), py::arg("sfb"), py::arg("out"),
           py::arg("c") = py::none());
+    m.def("wgrad_gemm_fp8_fp8_fp32_nt", &wgrad_gemm_fp8_fp8_fp32_nt, py::arg("a"), py::arg("sfa"), py::arg("b"), py::arg("sfb"),
+          py::arg("out"), py::arg("c") = py::none());
     m.def("m_grouped_gemm_fp8_fp8_bf16_nt_masked", &m_grouped_gemm_fp8_fp8_bf16_nt_masked, py::arg("a"), py::arg("sfa"),
           py::arg("b"), py::arg("sfb"), py::arg("out"), py::arg("masked_m"), py::arg("expected_m"), py::arg("strict") = false,
           py::arg("policy") = "");

@@ -218,6 +218,17 @@ int dga_tiling_fp32_out(const dga_problem_t *problem, dga_tiling_t *out);
  * split-K, Stream-K and workgroup split-K -- has an fp32 epilogue. */
 int dga_tiling_check_fp32_out(const dga_tiling_t *tiling);
 
+/* TilingFunc of dga_wgrad_gemm_fp8_fp8_fp32_nt (host only): what dga_tiling_fp32_out returns, with every build that has no per-row-sfb
+ * form mapped onto the same tile: kernelSerial 6 (the workgroup split-K, and with it DGA_BUILD_BX_DECODE / DGA_BUILD_WSK_REGISTER)
+ * becomes the two-launch split-K of the same splitkFactor (kernelSerial 4; 0 where splitkFactor is 1), kernelSerial 7 (one-launch
+ * Stream-K) kernelSerial 0, those build names DGA_BUILD_DEFAULT.  With $DGA_DEFAULT_POLICY = "strict" the strict tag.  No reference
+ * counterpart. */
+int dga_tiling_wgrad(const dga_problem_t *problem, dga_tiling_t *out);
+/* dga_tiling_check_fp32_out plus the weight-gradient entry's refusals (host only): DGA_E_TILING for kernelSerial 6 or 7 and the builds
+ * DGA_BUILD_BX_DECODE / DGA_BUILD_WSK_REGISTER under the bf16-exact tag.  The one-tile and persistent tiles, the two-launch split-K, the
+ * quarter-tile tail and the strict kernel have a per-row-sfb form. */
+int dga_tiling_check_wgrad(const dga_tiling_t *tiling);
+
 /* The arithmetic of an fp8 call that names neither a policy nor a tiling: $DGA_DEFAULT_POLICY, parsed and validated ONCE per process,
  * here, for every front end (the C entry points with tiling == NULL, deepgemm_ascend_amd/api.py, the deep_gemm_cpp extension).
  * Names: "bf16_exact" (the default: inside the operator's 2-ULP contract), "fast", "strict", "fast_ue8m0", "bf16_exact_ue8m0" (the
@@ -316,6 +327,19 @@ int dga_gemm_fp8_fp8_bf16_nt_strided(const void *a, int64_t lda, const float *sf
 int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb, const float *c,
                              float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/* wgrad_gemm_fp8_fp8_fp32_nt: upstream DeepGEMM's weight-gradient GEMM, out[M,N] (fp32) = C[M,N] (fp32, optional) +
+ * dequant(A) . dequant(B)^T with per-1x128 scales on BOTH operands ("1D1D"): sfa [M, ceil(K/128)] and sfb [N, ceil(K/128)], row-major --
+ * one scale per row of B per 128-wide k block, what per_token_cast_to_fp8 writes for an activation.  For dW = dY^T . X: A = dY^T
+ * [out_features, tokens], B = X^T [in_features, tokens], K = tokens, and out accumulated across micro-batches with c == out.
+ * Everything else -- strides, DGA_ROWS_*_ZERO_PADDED, c == NULL / c == out / partial overlap (DGA_E_SHAPE), K = 0 (out = c),
+ * workspace, asynchrony -- is dga_gemm_fp8_fp8_fp32_nt's.  The promotion scale of an output is fl(sfa[m, kb] * sfb[n, kb]); with every
+ * row of a 128-row block of B on one scale the result is that of dga_gemm_fp8_fp8_fp32_nt on the same tiling, bit for bit.
+ * tiling == NULL -> dga_tiling_wgrad(); a tiling is checked by dga_tiling_check_wgrad before anything is launched.  No reference
+ * counterpart: the Ascend reference has no weight-gradient path. */
+int dga_wgrad_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb,
+                                   const float *c, float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* m_grouped_gemm_fp8_fp8_bf16_nt_masked: G independent problems
  *   a [G,m_max,K], sfa [G,m_max,KB], b [G,N,K], sfb [G,NB,KB], out [G,m_max,N];
