@@ -564,6 +564,19 @@ def wgrad_gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tupl
     _fp32_out_call("wgrad_gemm_fp8_fp8_fp32_nt", lhs, rhs, out, c, tiling_, sync, strict, policy, zero_padded, sfb_rows=True)
 
 
+def _planned_fp32_out(index: int, m: int, n: int, k: int, strict: bool, policy: Optional[str], sfb_rows: bool) -> Tiling:
+    """What gemm_fp8_fp8_fp32_nt (sfb_rows=False) or wgrad_gemm_fp8_fp8_fp32_nt (True) runs without an explicit tiling, remembered
+    per problem as _planned does."""
+    # (the output kind and the scale layout are part of the key: never a bf16 call's plan, nor the other fp32 entry's)
+    key = ("wgrad" if sfb_rows else "fp32_out", index, m, n, k, strict, policy)
+    t = _PLANS.get(key)
+    if t is None:
+        if len(_PLANS) > 4096:
+            _PLANS.clear()
+        t = _PLANS[key] = _with_policy((tiling_wgrad if sfb_rows else tiling_fp32_out)(m, n, k), strict, policy)
+    return t
+
+
 def _fp32_out_call(name: str, lhs, rhs, out, c, tiling_, sync, strict, policy, zero_padded, sfb_rows: bool) -> None:
     """gemm_fp8_fp8_fp32_nt (sfb_rows=False) and wgrad_gemm_fp8_fp8_fp32_nt (sfb_rows=True): checks, plan, launch."""
     a, sfa = lhs
@@ -590,13 +603,7 @@ def _fp32_out_call(name: str, lhs, rhs, out, c, tiling_, sync, strict, policy, z
     with _device_guard(a, b, sfa, sfb, out, *(() if c is None else (c,))):
         index = out.device.index
         if tiling_ is None:
-            # (the output kind and the scale layout are part of the key: never a bf16 call's plan, nor the other fp32 entry's)
-            key = ("wgrad" if sfb_rows else "fp32_out", index, m, n, k, strict, policy)
-            tiling_ = _PLANS.get(key)
-            if tiling_ is None:
-                if len(_PLANS) > 4096:
-                    _PLANS.clear()
-                tiling_ = _PLANS[key] = _with_policy((tiling_wgrad if sfb_rows else tiling_fp32_out)(m, n, k), strict, policy)
+            tiling_ = _planned_fp32_out(index, m, n, k, strict, policy, sfb_rows)
         else:
             tiling_ = _with_policy(tiling_, strict, policy)
         stream = _stream_of(index)

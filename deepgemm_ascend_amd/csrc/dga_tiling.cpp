@@ -1027,6 +1027,9 @@ int dga_tiling(const dga_problem_t *problem, dga_tiling_t *out)
             case DGA_KERNEL_STREAMK_TAIL: case DGA_KERNEL_SPLITK_WORKGROUP: case DGA_KERNEL_STREAMK_ONE_LAUNCH: break;
             default: out->kernelSerial = DGA_KERNEL_COMMON;
         }
+        // (the power-of-two-scales flag is the caller's promise about its scales -- a fast_ue8m0 process default or policy adds it to
+        //  the tiling -- never a row's: a call on general scales must not run the E8M0-operand builds)
+        out->dispatchPolicyTag &= static_cast<uint8_t>(~DGA_POLICY_UE8M0_SCALES);
         if (out->contiguous)   // a bucketed key: the workgroup count follows this call's row count
             out->blockDim = static_cast<uint32_t>(static_cast<uint64_t>((out->m + out->m1 - 1) / std::max<uint32_t>(1, out->m1)) *
                                                   ((out->n + out->n1 - 1) / std::max<uint32_t>(1, out->n1)) *
@@ -1078,12 +1081,20 @@ int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out)
             if (!out->splitkFactor) out->splitkFactor = 1;
             out->wavesM = out->wavesN = 0;      // (this policy's builds are named by tile and `build`)
             if (!out->blockDim) out->blockDim = std::max<uint32_t>(1, out->groups) * ((out->m + out->m1 - 1) / out->m1) * ((out->n + out->n1 - 1) / out->n1) * out->splitkFactor;
-            return DGA_OK;
+            // The row's class is this policy, its tag is not the arithmetic: the power-of-two-scales flag is the caller's promise about
+            // its scales, added where the process default makes it (run_fp8 under bf16_exact_ue8m0, api._with_policy), never a row's.
+            out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+            // A row the menu does not hold (a hand-written file: the decode build off its 64 x 128 tile, the tail pair off 128 x 256, a
+            // stage count or build no kernel has) is no answer: the rules below pick instead of the launch refusing the call.
+            if (dga_tiling_check(out) == DGA_OK) return DGA_OK;
         }
     }
     int rc = dga_tiling(problem, out);
     if (rc != DGA_OK) return rc;
     out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+    // The fast tiling's build name is not this policy's (a fast sweep row of the register workgroup split-K carries build 1, or the
+    // legacy `stages` 1); the branches below that name a build set it themselves.
+    out->build = DGA_BUILD_DEFAULT;
     // Masked grouped layout: this policy's loop multiplies every row of its tile (no per-m-tile skipping as in the fast kernels), so the
     // tile height follows the caller's hint where it says the experts are nearly empty -- rows present 0..16: 832 -> 597 us on
     // 256 x (128, 7168, 2048) with 32 x 128 tiles, 0..32: 886 -> 628, 0..64: 938 -> 734 with 64 x 256 (scripts/grouped_decode_bf16x.py,
@@ -1115,6 +1126,12 @@ int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out)
         // grouped layouts keep the fast tiling's tile -- but not its wave layout: 2 x 2 waves would name this policy's 4-wave IMAGE build
         // (dga_launch.hip), 4-10 % behind the in-register build on the grouped stream and without its row skipping
         out->wavesM = out->wavesN = 0;
+        // (a fast-class cache row whose schedule this policy's menu lacks -- written by hand -- gives way to the selector's own tile)
+        if (out->m1 && dga_tiling_check(out) != DGA_OK && dga_select_kernel_with_predictor(problem, out, nullptr, nullptr) == DGA_OK) {
+            out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+            out->build = DGA_BUILD_DEFAULT;
+            out->wavesM = out->wavesN = 0;
+        }
         return DGA_OK;
     }
     using namespace dga::tiling;

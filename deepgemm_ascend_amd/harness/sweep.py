@@ -494,9 +494,30 @@ def benchmark_grouped(shape, out_dir: Path, iters=10, prewarm_s=0.15):
     return prob, best
 
 
-GROUPED_CSV_HEAD = ("m,n,k,m1,n1,k1,kernelSerial,paddingTagA,paddingTagB,paddingTagC,blockDim,"
-                    "splitkFactor,stages,swizzleOffset,wavesM,wavesN,dispatchPolicyTag,groups,contiguous\n")
+# the reference's 11 columns (csv.cpp:23-26) + the CDNA4 columns the cache reads when present
+FAST_CSV_HEAD = ("m,n,k,m1,n1,k1,kernelSerial,paddingTagA,paddingTagB,paddingTagC,blockDim,"
+                 "splitkFactor,stages,swizzleOffset,wavesM,wavesN,dispatchPolicyTag\n")
+GROUPED_CSV_HEAD = FAST_CSV_HEAD.strip() + ",groups,contiguous\n"
 FULL_CSV_HEAD = GROUPED_CSV_HEAD.strip() + ",build\n"      # + dga_tiling_t.build (ABI 7)
+
+
+def fast_row(m, n, k, p):
+    """The cache row (FAST_CSV_HEAD) of a fast-path winner of candidates(): a register workgroup split-K keeps its build name in
+    `stages` = 1, the name ABI <= 6 read from that column."""
+    serial = 6 if p.get("wsk") else (5 if p.get("tail") else (4 if p["splitk"] > 1 else 0))
+    blocks = -(-m // p["m1"]) * -(-n // p["n1"]) * p["splitk"]
+    if p.get("tail"):   # whole waves + the last partial wave in quarter tiles
+        blocks = blocks - blocks % 256 + 4 * (blocks % 256)
+    return f"{m},{n},{k},{p['m1']},{p['n1']},128,{serial},0,0,0,{blocks},{p['splitk']},{p['stages']},{p['raster']},0,0,{p['policy']}\n"
+
+
+def grouped_row(prob, c):
+    """The cache row (GROUPED_CSV_HEAD) of a grouped winner of grouped_candidates(); prob as check_candidate takes it."""
+    tiles = -(-prob["m"] // c["m1"]) * -(-prob["n"] // c["n1"])
+    contiguous = 1 if prob["layout"] == "contiguous" else 0
+    block_dim = tiles * (1 if contiguous else prob["groups"]) * (2 if contiguous and c["m1"] == 256 else 1)
+    return (f"{prob['m']},{prob['n']},{prob['k']},{c['m1']},{c['n1']},128,0,0,0,0,{block_dim},1,{c['stages']},"
+            f"{c['raster']},{c['wavesM']},{c['wavesN']},{c['policy']},{prob['groups']},{contiguous}\n")
 
 
 def bx_row(m, n, k, p, cus=256):
@@ -570,11 +591,7 @@ def main(argv=None):
             if best:
                 us, c = best
                 print(json.dumps({"shape": list(shape), "best_us": round(us, 2), **c}), flush=True)
-                tiles = -(-prob["m"] // c["m1"]) * -(-prob["n"] // c["n1"])
-                contiguous = 1 if prob["layout"] == "contiguous" else 0
-                block_dim = tiles * (1 if contiguous else prob["groups"]) * (2 if contiguous and c["m1"] == 256 else 1)
-                rows_out.append(f"{prob['m']},{prob['n']},{prob['k']},{c['m1']},{c['n1']},128,0,0,0,0,{block_dim},1,{c['stages']},"
-                                f"{c['raster']},{c['wavesM']},{c['wavesN']},{c['policy']},{prob['groups']},{contiguous}\n")
+                rows_out.append(grouped_row(prob, c))
         if a.cache_csv and rows_out:
             new = not Path(a.cache_csv).exists()
             with open(a.cache_csv, "a") as f:
@@ -599,15 +616,9 @@ def main(argv=None):
     elif a.cache_csv and winners:
         new = not Path(a.cache_csv).exists()
         with open(a.cache_csv, "a") as f:
-            if new:   # the reference's 11 columns (csv.cpp:23-26) + the CDNA4 columns the cache reads when present
-                f.write("m,n,k,m1,n1,k1,kernelSerial,paddingTagA,paddingTagB,paddingTagC,blockDim,"
-                        "splitkFactor,stages,swizzleOffset,wavesM,wavesN,dispatchPolicyTag\n")
-            for (m, n, k), p in winners:
-                blocks = -(-m // p["m1"]) * -(-n // p["n1"]) * p["splitk"]
-                if p.get("tail"):   # whole waves + the last partial wave in quarter tiles
-                    blocks = blocks - blocks % 256 + 4 * (blocks % 256)
-                f.write(f"{m},{n},{k},{p['m1']},{p['n1']},128,{6 if p.get('wsk') else (5 if p.get('tail') else (4 if p['splitk'] > 1 else 0))},0,0,0,{blocks},"
-                        f"{p['splitk']},{p['stages']},{p['raster']},0,0,{p['policy']}\n")
+            if new:
+                f.write(FAST_CSV_HEAD)
+            f.writelines(fast_row(m, n, k, p) for (m, n, k), p in winners)
 
 
 if __name__ == "__main__":

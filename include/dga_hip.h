@@ -186,12 +186,17 @@ int dga_infer_dtype(int self_dtype, int mat2_dtype, int *out_dtype);
 
 /* TilingFunc: catlass_dynamic_matmul_tiling.cpp:77-122 = shape checks + TilingParams ctor +
  * SelectKernelWithCache (select_kernel.cpp:371-378).  Consults the (m,n,k)-keyed tiling cache,
- * optionally CSV-backed through $CACHE_FILE_PATH / $DGA_CACHE_FILE_PATH (cache.cpp:22-101). */
+ * optionally CSV-backed through $CACHE_FILE_PATH / $DGA_CACHE_FILE_PATH (cache.cpp:22-101).  A cached row's
+ * DGA_POLICY_UE8M0_SCALES flag is dropped: the flag is the caller's promise about its scales, not a row's. */
 int dga_tiling(const dga_problem_t *problem, dga_tiling_t *out);
 
 /* TilingFunc of the bf16-exact arithmetic policy (dispatchPolicyTag 7): dga_tiling, then -- for dense problems -- the tile and
  * split-K factor picked from that policy's own menu by its own cost model (wave tiles <= 64 x 64, one 8-wave build; the fast path's
- * tuned tile is 10-40 % off there on mid-M shapes).  out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT.  No reference counterpart. */
+ * tuned tile is 10-40 % off there on mid-M shapes).  A tiling-cache row of this policy's class (dispatchPolicyTag 7, with or without
+ * DGA_POLICY_UE8M0_SCALES) is taken first if dga_tiling_check accepts it, and passed over for the rules otherwise; no build name of a
+ * fast-class row survives.  Whatever any cache row says, the result for M, N > 0 passes dga_tiling_check and carries
+ * dispatchPolicyTag = DGA_POLICY_BF16_EXACT exactly: never DGA_POLICY_UE8M0_SCALES, which only the caller's policy (or process
+ * default) adds.  No reference counterpart. */
 int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out);
 
 /* Does the compiled kernel menu hold this tiling?  DGA_OK, or the error every fp8 GEMM entry returns for it BEFORE any launch
@@ -208,8 +213,8 @@ int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out);
 int dga_tiling_check(const dga_tiling_t *tiling);
 
 /* TilingFunc of dga_gemm_fp8_fp8_fp32_nt (host only): what dga_tiling_bf16_exact returns, except that a tiling naming a build without
- * an fp32 epilogue -- a bf16 image build (DGA_BUILD_BX_AIMAGE / _IMAGE8 / _IMAGE4), DGA_BUILD_BX_GROUPED, DGA_POLICY_UE8M0_SCALES or a
- * fast-path tag (a cache row) -- comes back as the same tile with build = DGA_BUILD_DEFAULT and dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+ * an fp32 epilogue -- a bf16 image build (DGA_BUILD_BX_AIMAGE / _IMAGE8 / _IMAGE4) or DGA_BUILD_BX_GROUPED (a cache row) -- comes back
+ * as the same tile with build = DGA_BUILD_DEFAULT and dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
  * with $DGA_DEFAULT_POLICY = "strict" the strict tag.  DGA_E_RANGE: $DGA_DEFAULT_POLICY names no policy.  No reference counterpart. */
 int dga_tiling_fp32_out(const dga_problem_t *problem, dga_tiling_t *out);
 /* dga_tiling_check plus the fp32 entry's refusals (host only): DGA_E_TILING for a dispatchPolicyTag other than DGA_POLICY_BF16_EXACT or

@@ -41,7 +41,7 @@ CSV_HEAD = ("m,n,k,m1,n1,k1,kernelSerial,paddingTagA,paddingTagB,paddingTagC,blo
             "dispatchPolicyTag,groups,contiguous,build\n")
 
 
-@pytest.mark.parametrize("tag,build", [(7, 4), (7, 5), (7, 6), (7 | 16, 0), (7 | 16, 8)])
+@pytest.mark.parametrize("tag,build", [(7, 4), (7, 5), (7, 6)])
 def test_a_cache_row_without_an_fp32_build_is_mapped(tmp_path, tag, build):
     m, n, k = 300, 520, 1024
     path = tmp_path / "rows.csv"
@@ -54,6 +54,29 @@ def test_a_cache_row_without_an_fp32_build_is_mapped(tmp_path, tag, build):
         assert (t.m1, t.n1, t.kernelSerial, t.build, t.dispatchPolicyTag) == (128, 256, tb.kernelSerial, 0, 7)
         assert dga.tiling_check_fp32_out(t) == 0
         tb.build, tb.dispatchPolicyTag = 0, 7
+        assert bytes(t) == bytes(tb)
+    finally:
+        dga.tiling_cache_open(None)
+        dga.tiling_cache_clear()
+        dga.api._PLANS.clear()
+
+
+@pytest.mark.parametrize("build", [0, 8])
+def test_a_ue8m0_cache_row_comes_back_on_tag_7(tmp_path, build):
+    """A bf16-exact row with the power-of-two-scales flag (tag 23): the bf16-exact entry keeps the row's tile and build but not the
+    flag -- only the caller's policy or process default adds it -- and the fp32 entry runs the same tiling, the one-tile build (8)
+    included, since it has an fp32 epilogue."""
+    m, n, k = 300, 520, 1024
+    path = tmp_path / "rows.csv"
+    path.write_text(CSV_HEAD + f"{m},{n},{k},128,256,128,0,0,0,0,6,1,3,1,0,0,23,1,0,{build}\n")
+    try:
+        dga.tiling_cache_open(str(path))
+        tb = dga.tiling(m, n, k, policy="bf16_exact")
+        assert (tb.m1, tb.n1, tb.build, tb.dispatchPolicyTag) == (128, 256, build, 7)
+        assert dga.tiling_check(tb) == 0
+        t = dga.tiling_fp32_out(m, n, k)
+        assert (t.m1, t.n1, t.kernelSerial, t.build, t.dispatchPolicyTag) == (128, 256, tb.kernelSerial, build, 7)
+        assert dga.tiling_check_fp32_out(t) == 0
         assert bytes(t) == bytes(tb)
     finally:
         dga.tiling_cache_open(None)
