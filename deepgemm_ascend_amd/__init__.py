@@ -20,6 +20,9 @@ from .api import (  # noqa: F401
     tiling_check_wgrad,
     tiling_wgrad,
     wgrad_gemm_fp8_fp8_fp32_nt,
+    k_grouped_wgrad_gemm_fp8_fp8_fp32_nt,
+    tiling_check_k_grouped_wgrad,
+    tiling_k_grouped_wgrad,
     gemm_fp8_loop_clock,
     get_bench_config,
     get_best_config,

@@ -186,6 +186,11 @@ SIGNATURES = {
     "dga_tiling_wgrad": (c_int, [POINTER(Problem), POINTER(Tiling)]),
     "dga_wgrad_gemm_fp8_fp8_fp32_nt": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                                c_int, c_int, c_int, POINTER(Tiling), c_void_p, c_size_t, c_void_p]),
+    "dga_tiling_check_k_grouped_wgrad": (c_int, [POINTER(Tiling)]),
+    "dga_tiling_k_grouped_wgrad": (c_int, [POINTER(Problem), POINTER(Tiling)]),
+    "dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(Tiling), c_void_p,
+                                                         c_size_t, c_void_p]),
     "dga_default_policy": (c_int, [ctypes.c_char_p, c_int]),
     "dga_status_string": (c_char_p, [c_int]),
     "dga_last_hip_error": (c_int, []),

@@ -620,6 +620,116 @@ def _fp32_out_call(name: str, lhs, rhs, out, c, tiling_, sync, strict, policy, z
             torch.cuda.current_stream(out.device).synchronize()
 
 
+def tiling_k_grouped_wgrad(m: int, n: int, k_total: int, groups: int) -> Tiling:
+    """dga_tiling_k_grouped_wgrad: the default tiling of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt -- a rule on the G x tiles(M, N) raster
+    (the persistent 128 x 256 build where it fills the CUs, else a one-tile build whose raster does), no split-K, no workspace, no
+    tiling-cache lookup; the strict tag under $DGA_DEFAULT_POLICY=strict."""
+    t = Tiling()
+    p = _problem(m, n, k_total, groups, 0)
+    _lib.check(_lib.lib().dga_tiling_k_grouped_wgrad(ctypes.byref(p), ctypes.byref(t)), "tiling_k_grouped_wgrad")
+    return t
+
+
+def tiling_check_k_grouped_wgrad(t: Tiling) -> int:
+    """dga_tiling_check_k_grouped_wgrad: 0 if k_grouped_wgrad_gemm_fp8_fp8_fp32_nt takes this tiling, else the status it returns
+    before any launch."""
+    return int(_lib.lib().dga_tiling_check_k_grouped_wgrad(ctypes.byref(t)))
+
+
+def k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torch.Tensor, torch.Tensor],
+                                         out: torch.Tensor, ks: Sequence[int], ks_tensor: Optional[torch.Tensor] = None,
+                                         c: Optional[torch.Tensor] = None, tiling_: Optional[Tiling] = None, sync: bool = False,
+                                         strict: bool = False, policy: Optional[str] = None) -> None:
+    """Upstream DeepGEMM's MoE weight-gradient GEMM, the groups along K (the tokens): for every expert g,
+    out[g] (fp32 [M,N], written in place) = c[g] (optional) + A[:, k0_g : k0_g + ks[g]] . B[:, k0_g : k0_g + ks[g]]^T, dequantised,
+    with k0_g = sum(ks[:g]).  lhs = (A [M, K_total] fp8, sfa [M, K_total/128]) = per_token_cast_to_fp8(dY^T), rhs = (B [N, K_total]
+    fp8, sfb [N, K_total/128]) = per_token_cast_to_fp8(X^T) of the token buffer in the contiguous forward layout; out and c are
+    [G, M, N] float32, contiguous (c may be out itself: accumulate).  A and B may be row-strided views (row stride >= K_total, a
+    multiple of 16 bytes).
+
+    ks: the tokens per expert, G host ints -- each a multiple of 128 (get_m_alignment_for_contiguous_layout()), 0 allowed, sum <=
+    K_total -- used to check the call only.  The kernel reads ks_tensor (device int32 [G], the same counts) while it executes, so a
+    captured graph replays with whatever ks_tensor holds then.  ks_tensor=None builds it from ks: a host-to-device copy, not
+    capture-safe.  An empty expert gets c[g] exactly, or zeros.
+
+    Arithmetic: "bf16_exact" (default) -- every group is wgrad_gemm_fp8_fp8_fp32_nt on contiguous copies of its slices with the
+    same tile and no split-K, bit for bit, then + c[g]; "strict" (strict=True) -- the oracle's fp32 result, bit for bit.  "fast",
+    "auto" and the _ue8m0 policies raise."""
+    name = "k_grouped_wgrad_gemm_fp8_fp8_fp32_nt"
+    a, sfa = lhs
+    b, sfb = rhs
+    _require(policy is None or policy in _FP32_OUT_POLICIES, f"{name}: policy must be one of {list(_FP32_OUT_POLICIES)}")
+    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r" % (policy,))
+    _fp8_bytes(a); _fp8_bytes(b)
+    if a.dim() != 2 or b.dim() != 2:
+        _fail("A and B must be rank 2")
+    if out.dim() != 3 or out.dtype != torch.float32 or not out.is_contiguous():
+        _fail("out must be a contiguous float32 [G, M, N]")
+    g, m, n = out.shape
+    k_total = a.shape[1]
+    if a.shape[0] != m or b.shape[0] != n or b.shape[1] != k_total:
+        _fail(f"A must be [{m}, K_total] and B [{n}, K_total] with out [{g}, {m}, {n}]")
+    if k_total % 128:
+        _fail("K_total must be a multiple of 128")
+    kb = k_total // 128
+    if sfa.dtype != torch.float32 or sfb.dtype != torch.float32:
+        _fail("scales must be float32")
+    if sfa.dim() != 2 or sfa.shape[0] != m or sfa.shape[1] != kb:
+        _fail(f"sfa must be [{m},{kb}]")
+    if sfb.dim() != 2 or sfb.shape[0] != n or sfb.shape[1] != kb:
+        _fail(f"sfb must be [{n},{kb}] (one scale per row of B: per_token_cast_to_fp8)")
+    if not (sfa.is_contiguous() and sfb.is_contiguous()):
+        _fail("scales must be contiguous")
+    if (k_total > 1 and (a.stride(1) != 1 or b.stride(1) != 1)) or (m > 1 and a.stride(0) < k_total) or (n > 1 and b.stride(0) < k_total):
+        _fail("operands must be row-major with unit inner stride (row-strided views are accepted)")
+    lda = a.stride(0) if m > 1 else k_total
+    ldb = b.stride(0) if n > 1 else k_total
+    if k_total == 0:
+        lda = ldb = 0
+    elif lda % 16 or ldb % 16:
+        _fail("row strides of A and B must be multiples of 16 bytes")
+    ks = [int(v) for v in ks]
+    if len(ks) != g:
+        _fail(f"ks must hold {g} counts, one per group")
+    if any(v < 0 or v % 128 for v in ks):
+        _fail("every ks[g] must be >= 0 and a multiple of 128")
+    if sum(ks) > k_total:
+        _fail(f"sum(ks) = {sum(ks)} exceeds K_total = {k_total}")
+    if ks_tensor is not None:
+        if ks_tensor.dtype != torch.int32 or ks_tensor.dim() != 1 or ks_tensor.shape[0] != g or not ks_tensor.is_contiguous():
+            _fail(f"ks_tensor must be a contiguous int32 [{g}]")
+        if ks_tensor.device != out.device:
+            _fail("ks_tensor must live on the operands' device")
+    if c is not None:
+        if c.dtype != torch.float32 or tuple(c.shape) != (g, m, n) or not c.is_contiguous():
+            _fail(f"c must be a contiguous float32 [{g}, {m}, {n}]")
+        if c.data_ptr() != out.data_ptr() and c.device == out.device and g * m * n > 0:
+            lo, hi, nbytes = c.data_ptr(), out.data_ptr(), 4 * g * m * n
+            if lo < hi + nbytes and hi < lo + nbytes:
+                _fail("c must be out itself or not overlap it")
+    with _device_guard(a, b, sfa, sfb, out, *(() if c is None else (c,)), *(() if ks_tensor is None else (ks_tensor,))):
+        index = out.device.index
+        if tiling_ is None:
+            # (the entry is part of the key: never a plan of the dense fp32 or wgrad entries)
+            key = ("k_grouped_wgrad", index, m, n, k_total, g, strict, policy)
+            tiling_ = _PLANS.get(key)
+            if tiling_ is None:
+                if len(_PLANS) > 4096:
+                    _PLANS.clear()
+                tiling_ = _PLANS[key] = _with_policy(tiling_k_grouped_wgrad(m, n, k_total, g), strict, policy)
+        else:
+            tiling_ = _with_policy(tiling_, strict, policy)
+        if ks_tensor is None:
+            ks_tensor = torch.tensor(ks, dtype=torch.int32, device=out.device)
+        rc = _lib.lib().dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(
+            a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(), None if c is None else c.data_ptr(),
+            out.data_ptr(), ks_tensor.data_ptr(), g, m, n, k_total, 0, ctypes.byref(tiling_), None, 0, _stream_of(index))
+        if rc:
+            _lib.check(rc, name)
+        if sync:
+            torch.cuda.current_stream(out.device).synchronize()
+
+
 def gemm_fp8_loop_clock(lhs, rhs, out: torch.Tensor, tiling_: Optional[Tiling] = None, launches: int = 50):
     """(clock_mhz, loop_us): the shader clock the chip holds inside the main loop of the dense kernel `tiling_` selects,
     and that loop's duration, from the loop-clock build (dga_gemm_fp8_loop_clock; a diagnostic: it synchronises)."""

@@ -83,6 +83,15 @@ int launch_bf16x_image(const GemmParams &p, int waves, hipStream_t stream);
 int launch_bf16x_persistent(const GemmParams &p, hipStream_t stream);
 int launch_bf16x_persistent_f32(const GemmParams &p, hipStream_t stream);   // ... its fp32-output form (dense)
 int launch_bf16x_persistent_rows(const GemmParams &p, hipStream_t stream);  // ... and that with per-row sfb (dense)
+// the k-grouped weight-gradient builds (KGROUP = 1; dga_launch_menu_p.hip): the one-tile tiles, the persistent 128 x 256 build and the
+// strict kernel (bm 64 or 32) on the G x tiles(M, N) raster whose groups lie along K; DGA_E_TILING for any other raster
+template <class Cfg>
+int launch_bf16x_kgroup(const GemmParams &p, hipStream_t stream);
+#define DGA_MENU_EXTERN_BX_KGROUP(BM, BN, WM, WN, ST, PP) \
+    extern template int launch_bf16x_kgroup<GemmCfg<BM, BN, WM, WN, ST>>(const GemmParams &, hipStream_t);
+DGA_MENU_BX(DGA_MENU_EXTERN_BX_KGROUP)
+int launch_bf16x_persistent_kgroup(const GemmParams &p, hipStream_t stream);
+int launch_strict_kgroup(const GemmParams &p, int bm, hipStream_t stream);
 // the masked grouped layout's kernel (gemm_fp8_bf16x_grouped_kernel.hpp; dga_launch_menu_l.hip): two k blocks in flight, per-m-tile row skipping
 int launch_bf16x_grouped(const GemmParams &p, hipStream_t stream);
 

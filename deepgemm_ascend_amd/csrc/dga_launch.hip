@@ -102,9 +102,10 @@ struct Bf16xVariant {
     int (*launch)(const GemmParams &, hipStream_t);
     int (*launch_f32)(const GemmParams &, hipStream_t);   // the same build with fp32 rows (+ C): dga_gemm_fp8_fp8_fp32_nt
     int (*launch_rows)(const GemmParams &, hipStream_t);  // ... and with per-row sfb: dga_wgrad_gemm_fp8_fp8_fp32_nt
+    int (*launch_kgroup)(const GemmParams &, hipStream_t);  // ... and k-grouped: dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt
 };
 #define DGA_BX_VARIANT(BM, BN, WM, WN) {BM, BN, &launch_bf16x<GemmCfg<BM, BN, WM, WN, 3>>, &launch_bf16x_f32<GemmCfg<BM, BN, WM, WN, 3>>, \
-                                        &launch_bf16x_rows<GemmCfg<BM, BN, WM, WN, 3>>}
+                                        &launch_bf16x_rows<GemmCfg<BM, BN, WM, WN, 3>>, &launch_bf16x_kgroup<GemmCfg<BM, BN, WM, WN, 3>>}
 static const Bf16xVariant kBf16xVariants[] = {
     DGA_BX_VARIANT(128, 256, 2, 4), DGA_BX_VARIANT(128, 128, 2, 2), DGA_BX_VARIANT(64, 256, 1, 4), DGA_BX_VARIANT(64, 128, 1, 4),
     DGA_BX_VARIANT(32, 128, 1, 4),
@@ -807,6 +808,93 @@ int dga_wgrad_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa,
                                    void *workspace, size_t workspace_bytes, void *stream)
 {
     return fp32_out_entry(a, lda, sfa, b, ldb, sfb, c, out, m, n, k, flags, tiling, workspace, workspace_bytes, stream, true);
+}
+
+int dga_tiling_check_k_grouped_wgrad(const dga_tiling_t *tiling)
+{
+    if (int rc = dga_tiling_check_wgrad(tiling)) return rc;
+    if (tiling->splitkFactor > 1) return DGA_E_TILING;   // (no split-K inside a group)
+    if (tiling->dispatchPolicyTag == DGA_POLICY_STRICT) return DGA_OK;
+    // a k-grouped form exists of the plain raster of the one-tile tiles and of the persistent 128 x 256 build only
+    if (tiling->kernelSerial != DGA_KERNEL_COMMON && tiling->kernelSerial != DGA_KERNEL_SMALL && tiling->kernelSerial != DGA_KERNEL_PADDING_COMMON)
+        return DGA_E_TILING;
+    if (tiling->build != DGA_BUILD_DEFAULT && tiling->build != DGA_BUILD_BX_PERSISTENT && tiling->build != DGA_BUILD_BX_ONE_TILE)
+        return DGA_E_TILING;
+    // the tile itself, not its nearest build: one of the five one-tile tiles, and the persistent build is the 128 x 256 one
+    const dga::Bf16xVariant *vx = dga::find_bf16x_variant(tiling->m1, tiling->n1);
+    if (!vx || vx->bm != tiling->m1 || vx->bn != tiling->n1) return DGA_E_TILING;
+    if (tiling->build == DGA_BUILD_BX_PERSISTENT && !(tiling->m1 == 128 && tiling->n1 == 256)) return DGA_E_TILING;
+    return DGA_OK;
+}
+
+int dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb,
+                                             const float *c, float *out, const int32_t *ks, int groups, int m, int n, int k_total,
+                                             int flags, const dga_tiling_t *tiling, void *workspace, size_t workspace_bytes,
+                                             void *stream)
+{
+    (void)workspace; (void)workspace_bytes;   // (no build of this entry uses one: dga_workspace_bytes of its tilings is 0)
+    if (m < 0 || n < 0 || k_total < 0 || groups < 0 || k_total % 128) return DGA_E_SHAPE;
+    if (flags & ~(DGA_ROWS_A_ZERO_PADDED | DGA_ROWS_B_ZERO_PADDED)) return DGA_E_SHAPE;   // (rows of whole k blocks: nothing to pad)
+    if (groups == 0 || m == 0 || n == 0) return DGA_OK;
+    if (k_total > 0) {
+        if (lda < k_total || ldb < k_total) return DGA_E_SHAPE;
+        if ((lda & 15) || (ldb & 15)) return DGA_E_ALIGN;
+        // (the DMA addresses a tile's rows with 32-bit offsets from its first row)
+        if (static_cast<int64_t>(m) * lda >= 0x7FFFFFFFll || static_cast<int64_t>(n) * ldb >= 0x7FFFFFFFll) return DGA_E_RANGE;
+    }
+    if (!out || !ks || (k_total > 0 && (!a || !b || !sfa || !sfb))) return DGA_E_NULL;
+    const int64_t elems = static_cast<int64_t>(groups) * m * n;
+    if (c && c != out) {   // C is out itself or apart from it
+        const uintptr_t co = reinterpret_cast<uintptr_t>(c), oo = reinterpret_cast<uintptr_t>(out);
+        const uintptr_t bytes = static_cast<uintptr_t>(elems) * sizeof(float);
+        if (co < oo + bytes && oo < co + bytes) return DGA_E_SHAPE;
+    }
+    dga_tiling_t local;
+    if (!tiling) {
+        dga_problem_t pr{};
+        pr.m = m; pr.n = n; pr.k = k_total; pr.groups = groups;
+        pr.layoutTagA = DGA_LAYOUT_ROW_MAJOR; pr.layoutTagB = DGA_LAYOUT_COLUMN_MAJOR;
+        pr.layoutTagC = DGA_LAYOUT_ROW_MAJOR; pr.dtype = DGA_DT_FP8_E4M3FN;
+        if (int rc = dga_tiling_k_grouped_wgrad(&pr, &local)) return rc;
+        tiling = &local;
+    }
+    if (int rc = dga_tiling_check_k_grouped_wgrad(tiling)) return rc;
+    dga::GemmParams p{};
+    p.a = static_cast<const uint8_t *>(a); p.sfa = sfa;
+    p.b = static_cast<const uint8_t *>(b); p.sfb = sfb;
+    p.out = reinterpret_cast<uint16_t *>(out);
+    p.c_in = c;
+    p.ks = ks;
+    p.m = m; p.n = n; p.k = k_total;
+    p.kb_n = k_total / 128;
+    p.nb_n = n;   // (rows of sfb)
+    p.lda = k_total ? lda : 0; p.ldb = k_total ? ldb : 0; p.ldc = n;
+    p.c_gs = static_cast<int64_t>(m) * n;   // (A, B and their scales: one matrix for every group, group strides 0)
+    p.sfa_ld = p.kb_n;
+    p.groups = groups;
+    p.splitk = 1;
+    p.raster_group = tiling->swizzleOffset ? tiling->swizzleOffset : 1;
+    p.xcd_remap = 1;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (tiling->dispatchPolicyTag == DGA_POLICY_STRICT) {   // 64-row tiles where they fill the CUs, else 32-row ones
+        const int64_t tiles64 = static_cast<int64_t>(groups) * ((m + 63) / 64) * ((n + 127) / 128);
+        const int bm = (m > 32 && tiles64 >= static_cast<int64_t>(dga::device_cus())) ? 64 : 32;
+        p.tiles_m = (m + bm - 1) / bm;
+        p.tiles_n = (n + 127) / 128;
+        if (static_cast<int64_t>(groups) * p.tiles_m * p.tiles_n > 0x7FFFFFFFll) return DGA_E_SHAPE;
+        return dga::launch_strict_kgroup(p, bm, st);
+    }
+    const dga::Bf16xVariant *vx = dga::find_bf16x_variant(tiling->m1, tiling->n1);
+    if (!vx) return DGA_E_TILING;
+    p.tiles_m = (m + vx->bm - 1) / vx->bm;
+    p.tiles_n = (n + vx->bn - 1) / vx->bn;
+    const int64_t tiles = static_cast<int64_t>(groups) * p.tiles_m * p.tiles_n;
+    if (tiles > 0x7FFFFFFFll) return DGA_E_SHAPE;
+    // the persistent form where the tiling names it, or (build 0) where the raster is more than one round
+    if (vx->bm == 128 && vx->bn == 256 &&
+        (tiling->build == DGA_BUILD_BX_PERSISTENT || (tiling->build == DGA_BUILD_DEFAULT && tiles > static_cast<int64_t>(dga::device_cus()))))
+        return dga::launch_bf16x_persistent_kgroup(p, st);
+    return vx->launch_kgroup(p, st);
 }
 
 int dga_gemm_fp8_fp8_bf16_nt(const void *a, const float *sfa, const void *b, const float *sfb, void *out, int m,

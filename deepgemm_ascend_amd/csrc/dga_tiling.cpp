@@ -1276,6 +1276,32 @@ int dga_tiling_wgrad(const dga_problem_t *problem, dga_tiling_t *out)
     return DGA_OK;
 }
 
+int dga_tiling_k_grouped_wgrad(const dga_problem_t *problem, dga_tiling_t *out)
+{
+    if (!problem || !out) return DGA_E_NULL;
+    const int policy = dga::default_policy();
+    if (policy < 0) return DGA_E_RANGE;
+    // rules only, no cache lookup: a row timed for one dense K says little about a list of groups of different K
+    init_params(*problem, *out);
+    out->k1 = 128; out->stages = 3; out->splitkFactor = 1; out->kernelSerial = DGA_KERNEL_COMMON;
+    out->dispatchPolicyTag = policy == 2 ? DGA_POLICY_STRICT : DGA_POLICY_BF16_EXACT;
+    const uint64_t groups = out->groups, cus = dga::device_cus();
+    auto tiles = [&](uint32_t bm, uint32_t bn) { return groups * ((out->m + bm - 1) / bm) * ((out->n + bn - 1) / bn); };
+    // the persistent 128 x 256 build where the raster fills the CUs and every group has a tile for each of the eight XCDs (its list
+    // gives XCD x chunk x of every group: with fewer tiles per group some XCDs would idle); otherwise the tallest, then widest one-tile
+    // build whose raster fills the CUs, or the smallest tile
+    static const uint16_t kTiles[][2] = {{128, 256}, {128, 128}, {64, 256}, {64, 128}, {32, 128}};
+    int pick = 4;
+    for (int i = 0; i < 5; ++i)
+        if (tiles(kTiles[i][0], kTiles[i][1]) >= cus && (i > 0 || tiles(128, 256) >= 8 * groups)) { pick = i; break; }
+    out->m1 = kTiles[pick][0]; out->n1 = kTiles[pick][1];
+    out->build = pick == 0 ? DGA_BUILD_BX_PERSISTENT : DGA_BUILD_BX_ONE_TILE;
+    const uint64_t t = tiles(out->m1, out->n1);
+    out->blockDim = static_cast<uint32_t>(pick == 0 ? std::min<uint64_t>(t, cus) : std::min<uint64_t>(t, 0xFFFFFFFFull));
+    out->swizzleOffset = 1;
+    return DGA_OK;
+}
+
 int dga_tiling_cache_open(const char *csv_path) { return Cache::instance().open(csv_path); }
 int dga_tiling_cache_clear(void) { Cache::instance().clear(); return DGA_OK; }
 int dga_tiling_cache_size(void) { return Cache::instance().size(); }

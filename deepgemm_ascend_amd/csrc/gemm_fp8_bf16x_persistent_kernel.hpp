@@ -23,12 +23,385 @@
 
 namespace dga {
 
+// The k-grouped form (KGROUP = 1, with OUT = 1 and SFB_ROWS = 1; dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt): the groups lie along K, as gemm_fp8_kernel.hpp's KGROUP, and a
+// tile carries its group's k blocks [kb0, kb0 + kb) (kgroup_span; the tile list walks groups in increasing order, so the prefix runs
+// along with it).  Tiles now differ in length, so the list is not one contiguous chunk of the raster per XCD: every group is cut into
+// eight chunks and XCD x walks chunk x of group 0, then of group 1, ... -- a heavy group is spread over all XCDs, and an XCD's
+// consecutive tiles still share A and B panels.  Tiles of empty groups copy C (or write zeros) before anything is fetched.  The ring
+// runs across a boundary only when both tiles have two k blocks or more; otherwise the tile ends with its refills zero-filled, the
+// waves meet, and the next tile starts afresh with its own prologue (a one-block tile fetches its block 0 beside a zero-filled stage).
+// (A body of its own: threaded through the body below, the per-tile k-block counts moved the register assignment and the
+//  schedule of the existing builds.  The k-block loop is the same, step for step.)
+__device__ __forceinline__ void bf16x_persistent_kgroup(const GemmParams &p)
+{
+    constexpr bool KTAIL = false;
+    constexpr int OUT = 1, SFB_ROWS = 1, KGROUP = 1;
+    typedef GemmCfg<128, 256, 2, 4, 3> Cfg;
+    constexpr int BM = Cfg::kBM, BN = Cfg::kBN, WN = Cfg::kWN, TM = Cfg::TM, TN = Cfg::TN, DNT = Cfg::DNT;
+    constexpr int NL = Cfg::LOADS_PER_STAGE, TILES = TM * TN, G = 4 * TM, LAGT = 2, RING = 4;
+    static_assert(Cfg::NT == 512 && DNT == 512 && TILES % RING == 0 && 4 * TILES >= 4 + NL && 16 % G == 0, "the MATH = 1 schedule");
+    static_assert(SFB_ROWS == 0 || (OUT == 1 && BM + BN <= DNT && TM >= LAGT), "per-row sfb: fp32 rows, one scale piece");
+    typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int li = lane & 15, kg = lane >> 4;
+
+    // ---- this workgroup's tile list: chunk x of every group's tiles for XCD x, walked together by the workgroups of that XCD, `step`
+    //      tiles per round
+    const int tiles_per_group = p.tiles_m * p.tiles_n;
+    const int xcd = blockIdx.x & 7, q = tiles_per_group >> 3, r = tiles_per_group & 7;
+    const int kg_first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, kg_len = q + (xcd < r ? 1 : 0);
+    const int count = p.groups * kg_len, step = ((int)gridDim.x - xcd + 7) >> 3, slot = blockIdx.x >> 3;
+    struct Tile { int g, M, m0, n0, kb0, kb; };   // + the group's k blocks [kb0, kb0 + kb)
+    // entry `local` of this XCD's list is tile kg_first + local % kg_len of group local / kg_len; (pre, h) the running prefix of
+    // kgroup_span along the list; EMPTY: the tiles of empty groups instead (the copy pass, with a prefix of its own)
+    int kg_pre = 0, kg_h = 0;
+    auto seek_k = [&](int &local, auto &t, int &pre, int &h, auto emptyc) -> bool {
+        constexpr bool EMPTY = decltype(emptyc)::value;
+        for (; local < count; local += step) {
+            const int g = local / kg_len;
+            const int t_in = kg_first + (local - g * kg_len);
+            int kb0, kbn;
+            kgroup_span(p, g, pre, h, kb0, kbn);
+            if ((kbn == 0) != EMPTY) continue;
+            const int gm = p.raster_group;
+            const int per = gm * p.tiles_n;
+            const int band = t_in / per;
+            const int row0 = band * gm;
+            const int rows = min(p.tiles_m - row0, gm);
+            const int loc = t_in - band * per;
+            const int tm = row0 + loc % rows, tn = loc / rows;
+            t.g = g; t.M = p.m; t.m0 = tm * BM; t.n0 = tn * BN; t.kb0 = kb0; t.kb = kbn;
+            return true;
+        }
+        return false;
+    };
+    auto next_tile = [&](int &local, Tile &t) -> bool { return seek_k(local, t, kg_pre, kg_h, std::false_type{}); };
+    {   // empty groups: out = C, before the first DMA (nothing of theirs is in any stage)
+        int pre = 0, h = 0;
+        Tile t{};
+        for (int l = slot; seek_k(l, t, pre, h, std::true_type{}); l += step) kgroup_copy_tile(p, t.g, t.m0, t.n0, BM, BN, tid, Cfg::NT);
+    }
+
+    // ---- LDS-DMA sources.  The tile being multiplied keeps its per-lane offsets in registers (every k block uses them); the
+    //      next tile's are computed where they are used -- fourteen instructions per tile, in its predecessor's last two k blocks.
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
+    constexpr uint32_t kOutOfRange = 0x80000000u;
+    const int a_col = ((tid & 7) ^ swz_a(tid >> 3)) * 16;
+    const int b_col = ((tid & 7) ^ swz_b(tid >> 3)) * 16;
+    auto a_off = [&](const Tile &t, int it) -> uint32_t {
+        const int row = (it * DNT + tid) >> 3;
+        return row < t.M - t.m0 ? (uint32_t)row * (uint32_t)p.lda + a_col : kOutOfRange;   // rows at or beyond M: zero-filled, not fetched
+    };
+    auto b_off = [&](const Tile &t, int it) -> uint32_t {
+        const int row = (it * DNT + tid) >> 3;
+        return (uint32_t)min(row, p.n - 1 - t.n0) * (uint32_t)p.ldb + b_col;
+    };
+    auto sc_ptr = [&](const Tile &t) -> const float * {   // slot tid: [0, BM) sfa rows of the tile, then its sfb blocks (SFB_ROWS: rows)
+        const float *SFA = p.sfa + (int64_t)t.g * p.sfa_gs, *SFB = p.sfb + (int64_t)t.g * p.sfb_gs;
+        return tid < BM ? SFA + (int64_t)min(t.m0 + tid, t.M - 1) * p.sfa_ld + t.kb0
+                        : SFB + (int64_t)min(t.n0 + min(tid - BM, BN - 1), p.nb_n - 1) * p.kb_n + t.kb0;
+    };
+    auto a_desc = [&](const Tile &t) { return make_rsrc(p.a + (int64_t)t.g * p.a_gs + (int64_t)t.m0 * p.lda, (int64_t)(t.M - t.m0) * p.lda); };
+    auto b_desc = [&](const Tile &t) { return make_rsrc(p.b + (int64_t)t.g * p.b_gs + (int64_t)t.n0 * p.ldb, (int64_t)(p.n - t.n0) * p.ldb); };
+    static_assert(Cfg::SC_ITERS == 1, "one scale piece per stage");
+
+    Tile T{}, Tn{};
+    int local = slot;
+    if (!next_tile(local, T)) return;
+    v4i a_rsrc = a_desc(T), b_rsrc = b_desc(T), a_rsrc_n = a_rsrc, b_rsrc_n = b_rsrc;
+    uint32_t a_voff[Cfg::A_ITERS], b_voff[Cfg::B_ITERS];
+    const float *sc_src;
+    auto load_offsets = [&](const Tile &t) {
+#pragma unroll
+        for (int it = 0; it < Cfg::A_ITERS; ++it) a_voff[it] = a_off(t, it);
+#pragma unroll
+        for (int it = 0; it < Cfg::B_ITERS; ++it) b_voff[it] = b_off(t, it);
+        sc_src = sc_ptr(t);
+    };
+    load_offsets(T);
+    // piece idx of a stage, from the current tile's k block kb
+    auto issue_cur = [&](int idx, int stage, int kb) {
+        const uint32_t sa = lds0 + stage * Cfg::STAGE_BYTES + wave * 1024;
+        const int k0 = (T.kb0 + kb) * 128;
+        if (idx < Cfg::A_ITERS) {
+            uint32_t voff = a_voff[idx];
+            if constexpr (KTAIL) voff = (k0 + a_col < p.k) ? voff : kOutOfRange;
+            dma16(voff, a_rsrc, (uint32_t)k0, sa + idx * DNT * 16);
+        } else if (idx < Cfg::A_ITERS + Cfg::B_ITERS) {
+            const int it = idx - Cfg::A_ITERS;
+            uint32_t voff = b_voff[it];
+            if constexpr (KTAIL) voff = (k0 + b_col < p.k) ? voff : kOutOfRange;
+            dma16(voff, b_rsrc, (uint32_t)k0, sa + Cfg::A_BYTES + it * DNT * 16);
+        } else {
+            dma4(sc_src + kb, lds0 + stage * Cfg::STAGE_BYTES + Cfg::A_BYTES + Cfg::B_BYTES + wave * 256);
+        }
+    };
+    // the same from the NEXT tile's k block kb (has_next == false: every lane out of range -- zeros land, nothing is fetched; the
+    // scale piece re-reads the current tile's last block)
+    bool has_next = false;
+    auto issue_next = [&](int idx, int stage, int kb) {
+        const uint32_t sa = lds0 + stage * Cfg::STAGE_BYTES + wave * 1024;
+        const int k0 = (Tn.kb0 + kb) * 128;
+        if (idx < Cfg::A_ITERS) {
+            uint32_t voff = has_next ? a_off(Tn, idx) : kOutOfRange;
+            if constexpr (KTAIL) voff = (k0 + a_col < p.k) ? voff : kOutOfRange;
+            dma16(voff, a_rsrc_n, (uint32_t)k0, sa + idx * DNT * 16);
+        } else if (idx < Cfg::A_ITERS + Cfg::B_ITERS) {
+            const int it = idx - Cfg::A_ITERS;
+            uint32_t voff = has_next ? b_off(Tn, it) : kOutOfRange;
+            if constexpr (KTAIL) voff = (k0 + b_col < p.k) ? voff : kOutOfRange;
+            dma16(voff, b_rsrc_n, (uint32_t)k0, sa + Cfg::A_BYTES + it * DNT * 16);
+        } else {
+            dma4(has_next ? sc_ptr(Tn) + kb : sc_src + (T.kb - 1), lds0 + stage * Cfg::STAGE_BYTES + Cfg::A_BYTES + Cfg::B_BYTES + wave * 256);
+        }
+    };
+
+    // ---- per-lane fragment read offsets (bytes inside a stage): gemm_fp8_kernel.hpp
+    const int a_row = wm * (BM / Cfg::kWM) + li;
+    const int a_off0 = a_row * 128 + ((kg ^ swz_a(a_row)) * 16);
+    const int a_off1 = a_row * 128 + (((kg + 4) ^ swz_a(a_row)) * 16);
+    const int b_row = wn * (BN / WN) + 8 * (li >> 2) + (li & 3);
+    const int b_off0 = Cfg::A_BYTES + b_row * 128 + ((kg ^ swz_b(b_row)) * 16);
+    const int b_off1 = Cfg::A_BYTES + b_row * 128 + (((kg + 4) ^ swz_b(b_row)) * 16);
+    const int sa_off = Cfg::A_BYTES + Cfg::B_BYTES + (wm * (BM / Cfg::kWM) + li) * 4;
+    const int sb_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + (wn * (BN / WN)) / 128) * 4;
+    const int sbr_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + wn * (BN / WN) + 8 * kg) * 4;   // SFB_ROWS: gemm_fp8_kernel.hpp
+    auto sbr_nt = [](int nt) { return (32 * (nt >> 1) + 4 * (nt & 1)) * 4; };
+
+    v4f acc[TM][TN];
+    v4f part[RING];
+    v4i afx[TM][4], bfx[2][4];      // bf16 fragments: [q] = the 8 bf16 of MFMA q of the chain
+    v4i braw[2], araw[2][2];         // raw e4m3 bytes: [0] = bytes [16 kg, +16), [1] = bytes [64 + 16 kg, +16)
+    float s_cur[TM], s_old[TM], s_nxt[TM];
+    v4f sbv[TN];   // SFB_ROWS: the sfb of the lane's columns per n-tile (gemm_fp8_kernel.hpp); finite from the start: 0 * sbv
+    if constexpr (SFB_ROWS == 1)   // (only there: an initialised array nobody reads still moves the other builds' schedule)
+#pragma unroll
+        for (int i = 0; i < TN; ++i) sbv[i] = v4f{0.f, 0.f, 0.f, 0.f};
+    auto clear_tile = [&]() {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < RING; ++i) part[i] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < TM; ++i) s_old[i] = 0.f;    // the first LAGT tiles "promote the previous block": part (= 0) * 0
+    };
+    auto convert = [](const v4i (&raw)[2], v4i (&dst)[4], int c) {
+        const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
+        dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
+                                     : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+    };
+    auto b_frag_off = [](int nt) { return (nt >> 1) * 4096 + (nt & 1) * 512; };
+    // the fragments of a tile's block 0 out of the stage it has landed in, converted in one burst (a tile's first block in this
+    // wave: the kernel's first tile, and a tile that follows one in which the wave had no rows)
+    auto first_fragments = [&](const uint8_t *st) {
+        const float sfb0 = *(const float *)(st + sb_off);
+#pragma unroll
+        for (int mt = 0; mt < TM; ++mt) {
+            araw[mt & 1][0] = *(const v4i *)(st + a_off0 + mt * 2048);
+            araw[mt & 1][1] = *(const v4i *)(st + a_off1 + mt * 2048);
+#pragma unroll
+            for (int c = 0; c < 16; ++c) convert(araw[mt & 1], afx[mt], c);
+            if constexpr (SFB_ROWS == 1) s_cur[mt] = *(const float *)(st + sa_off + mt * 64);
+            else
+            s_cur[mt] = *(const float *)(st + sa_off + mt * 64) * sfb0;
+            s_nxt[mt] = 0.f;
+        }
+        braw[0] = *(const v4i *)(st + b_off0);
+        braw[1] = *(const v4i *)(st + b_off1);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) convert(braw, bfx[0], c);
+        braw[0] = *(const v4i *)(st + b_off0 + b_frag_off(1));   // B(1) of block 0, raw
+        braw[1] = *(const v4i *)(st + b_off1 + b_frag_off(1));
+    };
+    auto rows_present = [&](const Tile &t) { return t.m0 + wm * (BM / Cfg::kWM) < t.M; };   // (wave-uniform)
+
+    // ---- prologue: blocks 0 and 1 of the first tile on their way, block 0 landed (a one-block tile's block 1 is a zero-filled stage:
+    //      has_next is false here).  Also the fresh start of a tile the ring does not run into.
+    auto prologue = [&]() {
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+#pragma unroll
+            for (int idx = 0; idx < NL; ++idx) {
+                if (d >= T.kb) issue_next(idx, d, 0);
+                else issue_cur(idx, d, d);
+            }
+    };
+    prologue();
+    wait_vmcnt<NL>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    clear_tile();
+    bool active = rows_present(T);
+    if (active) first_fragments(smem);
+    int cur = 0, nxt = 1, fill = 2;
+
+    // one k block; LAST2: the refill is the next tile's block kb + 2 - T.kb
+    auto k_block = [&](int kb, auto last2c) __attribute__((always_inline)) {
+        constexpr bool LAST2 = decltype(last2c)::value;
+        auto refill = [&](int idx) {
+            if constexpr (LAST2) issue_next(idx, fill, kb + 2 - T.kb);
+            else issue_cur(idx, fill, kb + 2);
+        };
+        wait_vmcnt<0>();                         // this wave's pieces of the next block (issued a block ago) have landed
+        __builtin_amdgcn_s_barrier();            // ... everyone's have; and everyone has left the block whose stage is refilled now
+        asm volatile("" ::: "memory");
+        if (!active) {
+#pragma unroll
+            for (int idx = 0; idx < NL; ++idx) refill(idx);
+        } else {
+            const uint8_t *sc = smem + cur * Cfg::STAGE_BYTES;   // being consumed (B raw reloads of this block)
+            const uint8_t *sn = smem + nxt * Cfg::STAGE_BYTES;   // landed: the next block's fragments are read ahead from it
+#pragma unroll
+            for (int u = 0; u < 4 * TILES; ++u) {
+                const int t = u >> 2, q = u & 3, nt = t / TM, mt = t % TM, g = u % G;
+                part[t % RING] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    __builtin_bit_cast(v8bf, bfx[nt & 1][q]), __builtin_bit_cast(v8bf, afx[mt][q]),
+                    q == 0 ? v4f{0.f, 0.f, 0.f, 0.f} : part[t % RING], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (u >= 4 && u < 4 + NL) refill(u - 4);
+#pragma unroll
+                for (int c = 0; c < 16 / G; ++c) convert(braw, bfx[(nt + 1) & 1], (16 / G) * g + c);
+                {
+                    const int nn = nt + 2;
+                    const uint8_t *src = nn < TN ? sc : sn;
+                    const int off = b_frag_off(nn < TN ? nn : nn - TN);
+                    if (g == G / 2 - 1) braw[0] = *(const v4i *)(src + b_off0 + off);
+                    if (g == G - 1) braw[1] = *(const v4i *)(src + b_off1 + off);
+                }
+                if (nt == TN - 1 && q == 0) {
+                    araw[mt & 1][0] = *(const v4i *)(sn + a_off0 + mt * 2048);
+                    araw[mt & 1][1] = *(const v4i *)(sn + a_off1 + mt * 2048);
+                }
+                if (nt == TN - 1 && mt >= 1) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) convert(araw[(mt - 1) & 1], afx[mt - 1], 4 * q + c);
+                }
+                if (t == 0) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) convert(araw[(TM - 1) & 1], afx[TM - 1], 4 * q + c);
+                }
+                if (u == 4 * TILES - 8) {
+                    if constexpr (SFB_ROWS == 1) {
+#pragma unroll
+                        for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64);
+                    } else {
+                    const float sfbn = *(const float *)(sn + sb_off);
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64) * sfbn;
+                    }
+                }
+                {
+                    const int j = t >= LAGT ? t - LAGT : TILES + t - LAGT, jn = j / TM, jm = j % TM;
+                    float sv = t >= LAGT ? s_cur[jm] : s_old[jm];
+                    if constexpr (SFB_ROWS == 1) {
+                        if (mt == 0 && q == 0) sbv[nt] = *(const v4f *)(sc + sbr_off + sbr_nt(nt));
+                        sv = sv * sbv[jn][q];   // fl(sfa[m] * sfb[n])
+                    }
+                    acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], sv, acc[jm][jn][q]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                s_old[i] = s_cur[i];
+                s_cur[i] = s_nxt[i];
+            }
+        }
+        const int f = cur;
+        cur = nxt; nxt = fill; fill = f;
+    };
+
+    for (;;) {
+        // the tile after this one (its descriptors are needed from this tile's second-to-last k block on)
+        int local_n = local + step;
+        const bool found = next_tile(local_n, Tn);
+        has_next = found && T.kb >= 2 && Tn.kb >= 2;   // the ring runs into the next tile
+        if (has_next) { a_rsrc_n = a_desc(Tn); b_rsrc_n = b_desc(Tn); }
+        for (int kb = 0; kb < T.kb - 2; ++kb) k_block(kb, std::false_type{});
+        if (T.kb >= 2) k_block(T.kb - 2, std::true_type{});
+        k_block(T.kb - 1, std::true_type{});
+
+        // ---- boundary: the last LAGT tiles of the last block, the stores, the accumulators
+        if (active) {
+#pragma unroll
+            for (int t = 0; t < LAGT; ++t) {
+                const int j = TILES + t - LAGT, jn = j / TM, jm = j % TM;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    acc[jm][jn][q] = __builtin_fmaf(part[j % RING][q], SFB_ROWS == 1 ? s_old[jm] * sbv[jn][q] : s_old[jm], acc[jm][jn][q]);
+            }
+            uint16_t *C = p.out + (int64_t)T.g * p.c_gs;
+            const int m_row = T.m0 + wm * (BM / Cfg::kWM) + li;
+            const int n_base = T.n0 + wn * (BN / WN) + 8 * kg;
+            if constexpr (OUT == 1) {
+                float *const Cf = reinterpret_cast<float *>(p.out) + (int64_t)T.g * p.c_gs;
+                const float *const Ci = p.c_in ? p.c_in + (int64_t)T.g * p.c_gs : nullptr;
+                const bool vec = f32_rows_vec(Cf, Ci, p.ldc);
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) {
+                    const int m = m_row + mt * 16;
+                    if (m >= T.M) continue;
+                    float *orow = Cf + (int64_t)m * p.ldc;
+                    const float *crow = Ci ? Ci + (int64_t)m * p.ldc : nullptr;
+#pragma unroll
+                    for (int j = 0; j < TN / 2; ++j) {
+                        const v4f v[2] = {acc[mt][2 * j], acc[mt][2 * j + 1]};
+                        store_row_f32<8>(orow, crow, n_base + 32 * j, p.n, vec, p.out_nt, v);
+                    }
+                }
+            }
+        }
+        if (!found) break;
+        if (!has_next) {   // ---- a fresh start: every wave has left every stage, the zero-filled refills have landed
+            T = Tn; local = local_n;
+            a_rsrc = a_desc(T); b_rsrc = b_desc(T);
+            load_offsets(T);
+            wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            cur = 0; nxt = 1; fill = 2;
+            prologue();
+            wait_vmcnt<NL>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            clear_tile();
+            active = rows_present(T);
+            if (active) first_fragments(smem);
+            continue;
+        }
+        // ---- the next tile becomes the current one: its block 0 sits in stage `cur`, its block 1 is on its way into `nxt`
+        const bool was_active = active;
+        T = Tn; local = local_n;
+        a_rsrc = a_rsrc_n; b_rsrc = b_rsrc_n;
+        load_offsets(T);
+        active = rows_present(T);
+        clear_tile();
+        // (a wave that multiplied the previous tile has this block's fragments already: converted in place during that tile's last
+        //  k block; its s_cur is this block's; one that had no rows there sets them up now)
+        if (active && !was_active) first_fragments(smem + cur * Cfg::STAGE_BYTES);
+    }
+    wait_vmcnt<0>();   // the refills past the last tile (zeros) land in LDS nobody reads: drain them before exit
+}
+
+
 // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32.  SFB_ROWS = 1 (with OUT = 1): per-row sfb [N, KB], as gemm_fp8_kernel.hpp's
 // SFB_ROWS -- the scale piece (512 slots) carries the BM sfa rows and the BN sfb rows, the promotion scale is fl(sfa[m] * sfb[n])
-template <bool KTAIL, int OUT = 0, int SFB_ROWS = 0>
+// KGROUP = 1: the k-grouped form above.
+template <bool KTAIL, int OUT = 0, int SFB_ROWS = 0, int KGROUP = 0>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 gemm_fp8_bf16x_persistent_kernel(const GemmParams p)
 {
+    if constexpr (KGROUP == 1) {
+        static_assert(!KTAIL && OUT == 1 && SFB_ROWS == 1, "k-grouped: fp32 rows, per-row sfb, whole k blocks");
+        bf16x_persistent_kgroup(p);
+        return;
+    }
     typedef GemmCfg<128, 256, 2, 4, 3> Cfg;
     constexpr int BM = Cfg::kBM, BN = Cfg::kBN, WN = Cfg::kWN, TM = Cfg::TM, TN = Cfg::TN, DNT = Cfg::DNT;
     constexpr int NL = Cfg::LOADS_PER_STAGE, TILES = TM * TN, G = 4 * TM, LAGT = 2, RING = 4;

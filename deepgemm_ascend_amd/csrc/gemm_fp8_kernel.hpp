@@ -32,7 +32,11 @@ struct GemmParams {
     const uint8_t *b;      // [G][n][ldb]
     const float *sfb;      // [G][nb_n][kb_n]
     uint16_t *out;         // [G][m_rows][ldc] bf16 bits
-    const int32_t *masked_m;  // grouped: device int32[G]; dense: nullptr
+    union {
+        const int32_t *masked_m;  // grouped: device int32[G]; dense: nullptr
+        const int32_t *ks;        // k-grouped builds (KGROUP = 1, dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt): device int32[G], the K of
+                                  // every group; group g covers k blocks [sum_{h<g} ks[h] / 128, +ks[g] / 128) of kb_n (kgroup_span)
+    };
     const int32_t *m_indices;  // contiguous-grouped: device int32[m], the B group of every row (-1 = skip); else nullptr
     const int64_t *row_index;  // indexed masked-grouped: device int64[groups * m]; row r of group g is row row_index[g*m + r]
                                // of ONE flat source / destination (a, sfa and out then have group stride 0): the kernel
@@ -106,6 +110,32 @@ __device__ __forceinline__ void store_row_f32(float *orow, const float *crow, in
 __device__ __forceinline__ bool f32_rows_vec(const float *out, const float *c, int64_t ldc)
 {
     return (ldc & 3) == 0 && ((((uintptr_t)out) | ((uintptr_t)c)) & 15) == 0;
+}
+
+// k-grouped builds: the k blocks of group g, [kb0, kb0 + kbn), from the device counts p.ks.  Counts are read as they are and clamped:
+// a negative count is 0, and no group reaches past kb_n (= K_total / 128), so no operand is read outside its extent whatever the
+// counts hold.  (kb, h): a running prefix -- the k block where group h starts -- that a caller walking groups in increasing order
+// carries from one call to the next; (0, 0) starts from the first group.
+__device__ __forceinline__ void kgroup_span(const GemmParams &p, int g, int &kb, int &h, int &kb0, int &kbn)
+{
+    typedef const __attribute__((address_space(4))) int32_t *const_i32_ptr;   // scalar loads: the counts are uniform
+    const const_i32_ptr ks = (const_i32_ptr)p.ks;
+    for (; h < g; ++h) kb = min(kb + (max(ks[h], 0) >> 7), p.kb_n);
+    kb0 = kb;
+    kbn = min(max(ks[g], 0) >> 7, p.kb_n - kb);
+}
+// ... and the tile (m0, n0) of an empty group: out = C exactly (not 0 + C), or zeros
+__device__ __forceinline__ void kgroup_copy_tile(const GemmParams &p, int g, int m0, int n0, int bm, int bn, int tid, int nt)
+{
+    float *const Cf = reinterpret_cast<float *>(p.out) + (int64_t)g * p.c_gs;
+    const float *const Ci = p.c_in ? p.c_in + (int64_t)g * p.c_gs : nullptr;
+    const int rows = min(bm, p.m - m0), cols = min(bn, p.n - n0);
+    for (int e = tid; e < rows * bn; e += nt) {
+        const int r = e / bn, c = e - r * bn;
+        if (c >= cols) continue;
+        const int64_t at = (int64_t)(m0 + r) * p.ldc + n0 + c;
+        Cf[at] = Ci ? Ci[at] : 0.f;
+    }
 }
 
 // In-kernel stamps (diagnostic build only; cdna_hip_programming.md section 7 "In-kernel stamps").
@@ -210,10 +240,15 @@ struct LoopClock {
 //         piece of a stage carries the tile's BN of them (SfbRowsCfg).  The promotion scale becomes per element, fl(sfa[m] * sfb[n]),
 //         formed right at the promotion FMA where the per-row value fl(sfa[m] * sfb[n / 128]) is used otherwise: with every row of a
 //         128-row block of B on one scale the bits are those of SFB_ROWS = 0.
-template <class Cfg0, int PP, bool KTAIL, bool CLK = false, int MATH = 0, bool UNAL = false, int OUT = 0, int SFB_ROWS = 0>
+// KGROUP = 1 (SFB_ROWS = 1, no split-K; dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt): the groups lie along K.  The raster is G x tiles(M, N)
+//         over one A [M, K_total] and one B [N, K_total] (group strides 0); a tile of group g runs the kbn k blocks of kgroup_span from
+//         kb0, with A and B advanced by 128 kb0 bytes in the DMA's scalar offset and the scales by kb0 columns, and stores through c_gs.
+//         An empty group's tile copies C (or writes zeros) and reads nothing.
+template <class Cfg0, int PP, bool KTAIL, bool CLK = false, int MATH = 0, bool UNAL = false, int OUT = 0, int SFB_ROWS = 0, int KGROUP = 0>
 __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const GemmParams p)
 {
     typedef StageCfg<Cfg0, SFB_ROWS> Cfg;
+    static_assert(KGROUP == 0 || (SFB_ROWS == 1 && !KTAIL), "k-grouped: the per-row-sfb builds, whole k blocks");
     static_assert(OUT == 0 || (MATH == 1 && PP == 0 && !CLK && !UNAL), "fp32 output: the bf16-exact builds");
     static_assert(SFB_ROWS == 0 || (OUT == 1 && MATH == 1), "per-row sfb: the fp32-output bf16-exact builds");
     static_assert(!UNAL || (Cfg::kLC && PP == 0 && MATH == 0 && KTAIL), "unaligned rows: loader waves, plain loop, fp8 matrix instruction");
@@ -275,9 +310,18 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
         tm = 2 * tm + (sub & 1);
         tn = 2 * tn + (sub >> 1);
     }
-    const int M = p.masked_m ? min(p.masked_m[g], p.m) : p.m;
+    const int M = (!KGROUP && p.masked_m) ? min(p.masked_m[g], p.m) : p.m;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;  // empty expert / fully masked tile: nothing read, nothing written
+    int kg_kb0 = 0, kg_kbn = 0;   // KGROUP: this group's k blocks
+    if constexpr (KGROUP == 1) {
+        int kb = 0, h = 0;
+        kgroup_span(p, g, kb, h, kg_kb0, kg_kbn);
+        if (kg_kbn == 0) {
+            kgroup_copy_tile(p, g, m0, n0, BM, BN, tid, NT);
+            return;
+        }
+    }
     if (p.tail_sub && n0 >= p.n) return;  // a quarter tile beyond the matrix edge
     // contiguous-grouped layout: one A/out matrix, the B group comes from the index of the tile's first row (the
     // layout contract aligns group segments to the tile height); padding tiles (index -1) do nothing
@@ -298,7 +342,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
         if (bg < 0 || bg >= p.b_groups) return;
     }
     const int kb_begin = p.splitk > 1 ? split * p.kb_per_split : 0;
-    const int kb_end = p.splitk > 1 ? min(p.kb_n, kb_begin + p.kb_per_split) : p.kb_n;
+    const int kb_end = KGROUP ? kg_kbn : p.splitk > 1 ? min(p.kb_n, kb_begin + p.kb_per_split) : p.kb_n;
 
     const int64_t *ridx = p.row_index ? p.row_index + (int64_t)g * p.m : nullptr;   // slot -> row of the flat buffers
     const uint8_t *A = p.a + (int64_t)g * p.a_gs;
@@ -363,6 +407,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
             const int nb = min(n0 / 128 + min(s - BM, 7), p.nb_n - 1);
             sc_src[it] = SFB + (int64_t)nb * p.kb_n;
         }
+        if constexpr (KGROUP == 1) sc_src[it] += kg_kb0;
     }
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
 
@@ -379,7 +424,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
     // consumes.
     auto issue_one = [&](int idx, int stage, int kb) {
         const uint32_t sa = lds0 + stage * Cfg::STAGE_BYTES + dwave * 1024;
-        const int k0 = kb * 128;
+        const int k0 = (KGROUP ? kg_kb0 + kb : kb) * 128;
         if (idx < Cfg::A_ITERS) {
 #ifdef DGA_ABL_NOADMA
             return;   // diagnostic: the A tile is never fetched (whatever lies in the LDS is multiplied)
@@ -397,7 +442,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
             dma16(voff, b_rsrc, (uint32_t)k0, sa + Cfg::A_BYTES + it * DNT * 16);
         } else {
             const int it = idx - Cfg::A_ITERS - Cfg::B_ITERS;
-            dma4(sc_src[it] + min(kb, p.kb_n - 1), lds0 + stage * Cfg::STAGE_BYTES + Cfg::A_BYTES + Cfg::B_BYTES +
+            dma4(sc_src[it] + min(kb, (KGROUP ? kg_kbn : p.kb_n) - 1), lds0 + stage * Cfg::STAGE_BYTES + Cfg::A_BYTES + Cfg::B_BYTES +
                                                        (it * DNT + dwave * 64) * 4);
         }
     };

@@ -49,9 +49,213 @@ __device__ __forceinline__ v4i transpose_bytes_4x4(v4i w)
 // and TM = 1 where 64-row tiles would leave CUs idle.
 // SFB_ROWS = 1 (with OUT = 1; dga_wgrad_gemm_fp8_fp8_fp32_nt): sfb is [N, KB], one scale per row of B; the k block's BN of them are
 // staged beside the sfa rows and every output takes its own column's: s = fl(sfa[m] * sfb[n]), in the oracle's order as above.
-template <int TM, int OUT = 0, int SFB_ROWS = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
+// The k-grouped form of the per-row-sfb build (dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt): the groups lie along K, as gemm_fp8_kernel.hpp's
+// KGROUP -- a tile of group g reads the kbn k blocks of kgroup_span from kb0 (operand rows and scales advanced by kb0 blocks, K bounded
+// by 128 kbn), an empty group's tile copies C or writes zeros.  Otherwise the kernel below with OUT = 1, SFB_ROWS = 1, step for step (a body
+// of its own: threaded through the kernel, the group's k range moved the schedule of the existing builds).
+template <int TM>
+__device__ __forceinline__ void strict_kgroup(const GemmParams &p)
+{
+    constexpr int SFB_ROWS = 1;
+    constexpr int BM = 32 * TM, BN = 128, TN = 4;
+    static_assert(BM + BN <= 256, "per-row sfb: one scale per thread");
+    constexpr int A_CH = BM * 8 / 256, B_CH = BN * 8 / 256;  // 16-byte chunks per thread per k block
+    constexpr int SC = SFB_ROWS ? BM + BN : BM + 4;          // scale slots
+    __shared__ __attribute__((aligned(16))) uint8_t smem[(BM + BN) * 128 + SC * 4];
+    uint8_t *lds_a = smem, *lds_b = smem + BM * 128;
+    float *lds_s = (float *)(smem + (BM + BN) * 128);  // [0,BM) sfa rows, [BM] sfb (SFB_ROWS: [BM, BM + BN) the sfb rows of the tile's columns)
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 15, q = lane >> 4;
+
+    const int tiles_per_group = p.tiles_m * p.tiles_n;
+    const int g = blockIdx.x / tiles_per_group;
+    const int t_in = blockIdx.x - g * tiles_per_group;
+    const int tm = t_in % p.tiles_m, tn = t_in / p.tiles_m;
+    const int M = p.m;
+    const int m0 = tm * BM, n0 = tn * BN;
+    int kg_kb0, kg_kbn;   // this group's k blocks
+    {
+        int kb = 0, h = 0;
+        kgroup_span(p, g, kb, h, kg_kb0, kg_kbn);
+        if (kg_kbn == 0) {
+            kgroup_copy_tile(p, g, m0, n0, BM, BN, tid, 256);
+            return;
+        }
+    }
+    const int KB = kg_kbn, K = 128 * kg_kbn;   // (from column 128 kb0)
+    const int bg = g;
+    const uint8_t *A = p.a + (int64_t)g * p.a_gs + (int64_t)128 * kg_kb0;
+    const uint8_t *B = p.b + (int64_t)bg * p.b_gs + (int64_t)128 * kg_kb0;
+    const float *SFA = p.sfa + (int64_t)g * p.sfa_gs + kg_kb0;
+    // 16-byte vector loads need K % 16 == 0 and 16-byte aligned operands; otherwise bytes are gathered one by one
+    const bool vec = ((K & 15) == 0) && ((p.lda & 15) == 0) && ((p.ldb & 15) == 0) &&
+                     ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0;
+
+    v4i ra[A_CH], rb[B_CH];
+    float rs = 0.f;
+    auto fetch_chunk = [&](const uint8_t *row, int kc) -> v4i {
+        if (vec) {
+            if (kc + 16 <= K) return *(const v4i *)(row + kc);
+            return v4i{0, 0, 0, 0};
+        }
+        uint32_t w[4] = {0, 0, 0, 0};
+        for (int j = 0; j < 16; ++j)
+            if (kc + j < K) w[j >> 2] |= (uint32_t)row[kc + j] << (8 * (j & 3));
+        return v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+    };
+    // row pointers of this thread's chunks (row clamp, row table, chunk column): once per tile, not once per k block
+    const uint8_t *a_ptr[A_CH], *b_ptr[B_CH];
+    int a_col[A_CH], b_col[B_CH];
+#pragma unroll
+    for (int it = 0; it < A_CH; ++it) {
+        const int c = it * 256 + tid, row = c >> 3;
+        const int mr = m0 + min(row, M - 1 - m0);
+        a_col[it] = (c & 7) * 16;
+        a_ptr[it] = A + (int64_t)mr * p.lda;
+    }
+#pragma unroll
+    for (int it = 0; it < B_CH; ++it) {
+        const int c = it * 256 + tid, row = c >> 3;
+        b_col[it] = (c & 7) * 16;
+        b_ptr[it] = B + (int64_t)(n0 + min(row, p.n - 1 - n0)) * p.ldb;
+    }
+    const float *s_ptr = nullptr;
+    if (tid < BM) {
+        const int mr = min(m0 + tid, M - 1);
+        s_ptr = SFA + (int64_t)mr * p.sfa_ld;
+    } else if (SFB_ROWS == 1 && tid < BM + BN) {
+        s_ptr = p.sfb + (int64_t)bg * p.sfb_gs + (int64_t)min(n0 + tid - BM, p.n - 1) * p.kb_n + kg_kb0;
+    }
+    auto fetch = [&](int kb) {
+        const int k0 = kb * 128;
+#pragma unroll
+        for (int it = 0; it < A_CH; ++it) ra[it] = fetch_chunk(a_ptr[it], k0 + a_col[it]);
+#pragma unroll
+        for (int it = 0; it < B_CH; ++it) rb[it] = fetch_chunk(b_ptr[it], k0 + b_col[it]);
+        if (s_ptr) rs = s_ptr[kb];
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int it = 0; it < A_CH; ++it) {
+            const int c = it * 256 + tid, row = c >> 3, ch = c & 7;
+            *(v4i *)(lds_a + row * 128 + ((ch ^ swz_a(row)) * 16)) = transpose_bytes_4x4(ra[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < B_CH; ++it) {
+            const int c = it * 256 + tid, row = c >> 3, ch = c & 7;
+            *(v4i *)(lds_b + row * 128 + ((ch ^ swz_a(row)) * 16)) = transpose_bytes_4x4(rb[it]);
+        }
+        if (tid <= BM || (SFB_ROWS == 1 && tid < BM + BN)) lds_s[tid] = rs;
+    };
+
+    v4f acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+
+    const int a_row = wm * (16 * TM) + r;   // + 16*mt
+    const int b_row = wn * 64 + r;          // + 16*nt
+
+    if (KB > 0) fetch(0);
+    for (int kb = 0; kb < KB; ++kb) {
+        __syncthreads();   // every wave has left the previous k block's LDS image
+        stage();
+        __syncthreads();
+        if (kb + 1 < KB) fetch(kb + 1);   // lands under this block's MFMAs
+
+        v4f part[TM][TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) part[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+        // chunk c + 1's dwords are read while chunk c's 32 MFMAs are issued (the loop is unrolled: the two register sets alternate)
+        int ca[2][TM], cb[2][TN];      // this lane's dword of a chunk: k = 16c + q, + 4, + 8, + 12
+        auto read_chunk = [&](int c, int (&da)[TM], int (&db)[TN]) {
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) {
+                const int row = a_row + 16 * mt;
+                da[mt] = *(const int *)(lds_a + row * 128 + ((c ^ swz_a(row)) * 16) + 4 * q);
+            }
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt) {
+                const int row = b_row + 16 * nt;
+                db[nt] = *(const int *)(lds_b + row * 128 + ((c ^ swz_a(row)) * 16) + 4 * q);
+            }
+        };
+        read_chunk(0, ca[0], cb[0]);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            if (c + 1 < 8) read_chunk(c + 1, ca[(c + 1) & 1], cb[(c + 1) & 1]);
+            // the chunk's twelve packed conversions first (steps 4c .. 4c + 3: two steps per conversion), then its 32 MFMAs: a
+            // conversion whose result the very next MFMA reads stalls that MFMA behind the vector write (1103 -> 1050 us at 4096^3;
+            // a whole chunk ahead instead costs 20 more registers, the third wave per SIMD with them, and measures 1078)
+            v2f fa[2][TM], fb[2][TN];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) fa[h][mt] = h ? __builtin_amdgcn_cvt_pk_f32_fp8(ca[c & 1][mt], true) : __builtin_amdgcn_cvt_pk_f32_fp8(ca[c & 1][mt], false);
+#pragma unroll
+                for (int nt = 0; nt < TN; ++nt) fb[h][nt] = h ? __builtin_amdgcn_cvt_pk_f32_fp8(cb[c & 1][nt], true) : __builtin_amdgcn_cvt_pk_f32_fp8(cb[c & 1][nt], false);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int d = 0; d < 2; ++d)
+#pragma unroll
+                    for (int nt = 0; nt < TN; ++nt)
+#pragma unroll
+                        for (int mt = 0; mt < TM; ++mt)
+                            part[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(d ? fb[h][nt].y : fb[h][nt].x, d ? fa[h][mt].y : fa[h][mt].x, part[mt][nt], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // two-level dequant in the oracle's order: s = sfa * sfb (rounded), acc = acc + partial * s (two roundings)
+        {   // the lane's outputs are columns n0 + wn 64 + 16 nt + 4 q + 0..3
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) {
+                const float sa = lds_s[a_row + 16 * mt];
+#pragma unroll
+                for (int nt = 0; nt < TN; ++nt) {
+                    const v4f sb = *(const v4f *)(lds_s + BM + wn * 64 + 16 * nt + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[mt][nt][e] = promote_no_fma(acc[mt][nt][e], part[mt][nt][e], mul_no_fma(sa, sb[e]));
+                }
+            }
+        }
+    }
+
+    // epilogue: D[i][j] with i = n (4q + t), j = m (r): a lane owns 4 consecutive n of one row
+    {
+        float *const Cf = reinterpret_cast<float *>(p.out) + (int64_t)g * p.c_gs;
+        const float *const Ci = p.c_in ? p.c_in + (int64_t)g * p.c_gs : nullptr;
+        const bool vec = f32_rows_vec(Cf, Ci, p.ldc);
+#pragma unroll
+        for (int mt = 0; mt < TM; ++mt) {
+            const int m = m0 + a_row + 16 * mt;
+            if (m >= M) continue;
+            const int64_t row = (int64_t)m * p.ldc;
+#pragma unroll
+            for (int nt = 0; nt < TN; ++nt) {
+                const v4f v[1] = {acc[mt][nt]};
+                store_row_f32<4>(Cf + row, Ci ? Ci + row : nullptr, n0 + wn * 64 + 16 * nt + 4 * q, p.n, vec, 0, v);
+            }
+        }
+    }
+}
+
+// KGROUP = 1 (with OUT = 1 and SFB_ROWS = 1): strict_kgroup above.
+template <int TM, int OUT = 0, int SFB_ROWS = 0, int KGROUP = 0>   // OUT = 1: fp32 rows (+ C), gemm_fp8_kernel.hpp store_row_f32
 __global__ void __launch_bounds__(256) gemm_fp8_strict_nt_kernel(const GemmParams p)
 {
+    if constexpr (KGROUP == 1) {
+        static_assert(OUT == 1 && SFB_ROWS == 1, "k-grouped: fp32 rows, per-row sfb");
+        strict_kgroup<TM>(p);
+        return;
+    }
     constexpr int BM = 32 * TM, BN = 128, TN = 4;
     static_assert(SFB_ROWS == 0 || (OUT == 1 && BM + BN <= 256), "per-row sfb: fp32 rows, one scale per thread");
     constexpr int A_CH = BM * 8 / 256, B_CH = BN * 8 / 256;  // 16-byte chunks per thread per k block

@@ -228,6 +228,40 @@ void wgrad_gemm_fp8_fp8_fp32_nt(const at::Tensor &a, const at::Tensor &sfa, cons
                                          wsb ? ws.data_ptr() : nullptr, wsb, cur_stream()), "wgrad_gemm_fp8_fp8_fp32_nt");
 }
 
+// the MoE weight gradient with the groups along K: out[g] = c[g] + A[:, k0_g : k0_g + ks[g]] . B[:, ...]^T, ks a device int32 [G]
+// read by the kernel; dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt, default tiling (dga_tiling_k_grouped_wgrad).  The counts are not
+// checked here (they stay on the device): the kernel clamps them to K_total
+void k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(const at::Tensor &a, const at::Tensor &sfa, const at::Tensor &b, const at::Tensor &sfb,
+                                          at::Tensor &out, const at::Tensor &ks, const c10::optional<at::Tensor> &c)
+{
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && out.dim() == 3, "a [M,K_total], b [N,K_total], out [G,M,N]");
+    const int64_t g = out.size(0), m = a.size(0), n = b.size(0), k = a.size(1), kb = k / 128;
+    TORCH_CHECK(k % 128 == 0, "K_total must be a multiple of 128");
+    want_fp8(a, "a"); want_fp8(b, "b");
+    want_shape(b, {n, k}, "b");
+    want_shape(out, {g, m, n}, "out"); want_dtype(out, at::kFloat, "out");
+    want_shape(sfa, {m, kb}, "sfa"); want_dtype(sfa, at::kFloat, "sfa");
+    want_shape(sfb, {n, kb}, "sfb"); want_dtype(sfb, at::kFloat, "sfb");
+    want_shape(ks, {g}, "ks"); want_dtype(ks, at::kInt, "ks");
+    if (c.has_value()) {
+        want_shape(*c, {g, m, n}, "c"); want_dtype(*c, at::kFloat, "c");
+        same_device({&a, &sfa, &b, &sfb, &out, &ks, &*c});
+    } else {
+        same_device({&a, &sfa, &b, &sfb, &out, &ks});
+    }
+    const c10::OptionalDeviceGuard guard(at::device_of(out));
+    dga_problem_t p{};
+    p.m = m; p.n = n; p.k = k; p.groups = g;
+    p.layoutTagA = DGA_LAYOUT_ROW_MAJOR; p.layoutTagB = DGA_LAYOUT_COLUMN_MAJOR; p.layoutTagC = DGA_LAYOUT_ROW_MAJOR;
+    p.dtype = DGA_DT_FP8_E4M3FN;
+    dga_tiling_t t{};
+    check(dga_tiling_k_grouped_wgrad(&p, &t), "tiling_k_grouped_wgrad");
+    check(dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(a.data_ptr(), k, sfa.data_ptr<float>(), b.data_ptr(), k, sfb.data_ptr<float>(),
+                                                   c.has_value() ? c->data_ptr<float>() : nullptr, out.data_ptr<float>(),
+                                                   ks.data_ptr<int32_t>(), g, m, n, k, 0, &t, nullptr, 0, cur_stream()),
+          "k_grouped_wgrad_gemm_fp8_fp8_fp32_nt");
+}
+
 void m_grouped_gemm_fp8_fp8_bf16_nt_masked(const at::Tensor &a, const at::Tensor &sfa, const at::Tensor &b,
                                            const at::Tensor &sfb, at::Tensor &out, const at::Tensor &masked_m,
                                            int64_t expected_m, bool strict, const std::string &policy)
@@ -305,6 +339,8 @@ PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.c
           py::arg("c") = py::none());
     m.def("wgrad_gemm_fp8_fp8_fp32_nt", &wgrad_gemm_fp8_fp8_fp32_nt, py::arg("a"), py::arg("sfa"), py::arg("b"), py::arg("sfb"),
           py::arg("out"), py::arg("c") = py::none());
+    m.def("k_grouped_wgrad_gemm_fp8_fp8_fp32_nt", &k_grouped_wgrad_gemm_fp8_fp8_fp32_nt, py::arg("a"), py::arg("sfa"), py::arg("b"),
+          py::arg("sfb"), py::arg("out"), py::arg("ks"), py::arg("c") = py::none());
     m.def("m_grouped_gemm_fp8_fp8_bf16_nt_masked", &m_grouped_gemm_fp8_fp8_bf16_nt_masked, py::arg("a"), py::arg("sfa"),
           py::arg("b"), py::arg("sfb"), py::arg("out"), py::arg("masked_m"), py::arg("expected_m"), py::arg("strict") = false,
           py::arg("policy") = "");

@@ -234,6 +234,20 @@ int dga_tiling_wgrad(const dga_problem_t *problem, dga_tiling_t *out);
  * quarter-tile tail and the strict kernel have a per-row-sfb form. */
 int dga_tiling_check_wgrad(const dga_tiling_t *tiling);
 
+/* TilingFunc of dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt (host only; problem->k = K_total, problem->groups = G): a rule on the raster of
+ * G x tiles(M, N) alone -- the persistent 128 x 256 build (DGA_BUILD_BX_PERSISTENT) where those tiles fill the CUs and every group has at
+ * least eight (one per XCD), otherwise the
+ * tallest, then widest one-tile tile (DGA_BUILD_BX_ONE_TILE of 128 x 128, 64 x 256, 64 x 128, 32 x 128) whose raster does, else 32 x 128;
+ * kernelSerial 0, splitkFactor 1, so dga_workspace_bytes() is 0.  Tag 7; with $DGA_DEFAULT_POLICY = "strict" the strict tag.  Does not
+ * consult the tiling cache (no cache row, sweep or predictor covers this entry).  No reference counterpart. */
+int dga_tiling_k_grouped_wgrad(const dga_problem_t *problem, dga_tiling_t *out);
+/* dga_tiling_check_wgrad plus the k-grouped entry's refusals (host only): DGA_E_TILING for splitkFactor > 1 (no split-K inside a
+ * group, under any tag) and, under the bf16-exact tag, for kernelSerial 4, 5, 6 and 7 (the two-launch split-K, the quarter-tile tail,
+ * the workgroup split-K, the one-launch Stream-K), every build but 0, DGA_BUILD_BX_PERSISTENT and DGA_BUILD_BX_ONE_TILE, a tile (m1, n1)
+ * that is not exactly one of 128 x 256, 128 x 128, 64 x 256, 64 x 128, 32 x 128, and DGA_BUILD_BX_PERSISTENT off 128 x 256.  The fast
+ * tags and the UE8M0 flag are refused as by dga_tiling_check_fp32_out. */
+int dga_tiling_check_k_grouped_wgrad(const dga_tiling_t *tiling);
+
 /* The arithmetic of an fp8 call that names neither a policy nor a tiling: $DGA_DEFAULT_POLICY, parsed and validated ONCE per process,
  * here, for every front end (the C entry points with tiling == NULL, deepgemm_ascend_amd/api.py, the deep_gemm_cpp extension).
  * Names: "bf16_exact" (the default: inside the operator's 2-ULP contract), "fast", "strict", "fast_ue8m0", "bf16_exact_ue8m0" (the
@@ -345,6 +359,25 @@ int dga_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const
 int dga_wgrad_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb,
                                    const float *c, float *out, int m, int n, int k, int flags, const dga_tiling_t *tiling,
                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* k_grouped_wgrad_gemm_fp8_fp8_fp32_nt: upstream DeepGEMM's MoE weight-gradient GEMM, G problems whose groups lie along K (the tokens):
+ *   out[g] (fp32 [M,N]) = C[g] (fp32, optional) + dequant(A[:, k0_g : k0_g + K_g]) . dequant(B[:, k0_g : k0_g + K_g])^T
+ * with A [M, K_total] fp8 (row stride lda), sfa [M, K_total/128], B [N, K_total] fp8 (row stride ldb), sfb [N, K_total/128] -- the
+ * per-1x128 scales of dga_wgrad_gemm_fp8_fp8_fp32_nt on both operands -- and K_g = ks[g], k0_g = sum_{h<g} K_g.  ks is a device
+ * int32[groups], read while the call executes (a captured graph replays with the counts of the moment); every K_g a multiple of 128
+ * (DGA_CONTIGUOUS_M_ALIGNMENT: the contiguous forward layout's segments, transposed), 0 allowed, sum <= K_total (columns past the sum
+ * are never read).  Counts that break this give unspecified numbers, never a read outside A, B, sfa, sfb or a write outside out: the
+ * kernels clamp every group to [0, K_total).  K_g = 0: out[g] = C[g] exactly, or zeros.  out and C are [G, M, N] contiguous; C may be
+ * out itself, a partial overlap is DGA_E_SHAPE.  K_total % 128, negative sizes: DGA_E_SHAPE; lda / ldb below K_total: DGA_E_SHAPE, not
+ * a multiple of 16: DGA_E_ALIGN; NULL pointers where there is work: DGA_E_NULL -- all before any launch.  flags: 0 or
+ * DGA_ROWS_*_ZERO_PADDED (no effect: rows of whole k blocks).  One launch; no workspace (workspace may be NULL, any size is ignored).
+ * Numerics: tag 7 -- group g is, bit for bit, dga_wgrad_gemm_fp8_fp8_fp32_nt on contiguous copies of its slices with the same tile and
+ * no split-K, then + C[g]; tag 3 -- the oracle's fp32 result, bit for bit.  tiling == NULL -> dga_tiling_k_grouped_wgrad(); a tiling is
+ * checked by dga_tiling_check_k_grouped_wgrad before anything is launched.  No reference counterpart. */
+int dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(const void *a, int64_t lda, const float *sfa, const void *b, int64_t ldb, const float *sfb,
+                                             const float *c, float *out, const int32_t *ks, int groups, int m, int n, int k_total,
+                                             int flags, const dga_tiling_t *tiling, void *workspace, size_t workspace_bytes,
+                                             void *stream);
 
 /* m_grouped_gemm_fp8_fp8_bf16_nt_masked: G independent problems
  *   a [G,m_max,K], sfa [G,m_max,KB], b [G,N,K], sfb [G,NB,KB], out [G,m_max,N];
