@@ -27,9 +27,10 @@ extern "C" int dga_gemm_fp8_loop_clock(const void *a, const float *sfa, const vo
     if (scratch_bytes < need) return DGA_E_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = dga::record_hip(hipMemsetAsync(scratch, 0, need, s))) return rc;
+    dga::Fp8Call call{a, sfa, b, sfb, out, m, n, k, tiling, nullptr, 0, s};
+    call.clock_stamps = static_cast<unsigned long long *>(scratch);
     for (int i = 0; i < launches; ++i) {                  // the last launch's stamps are the ones read back
-        int rc = dga::run_fp8(a, sfa, b, sfb, out, nullptr, nullptr, 1, 1, m, n, k, 0, tiling, nullptr, 0, s,
-                              static_cast<unsigned long long *>(scratch), nullptr);
+        int rc = dga::run_fp8(call);
         if (rc != DGA_OK) return rc;
     }
     std::vector<unsigned long long> h(waves * 2);

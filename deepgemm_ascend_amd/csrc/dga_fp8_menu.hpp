@@ -79,10 +79,9 @@ DGA_MENU_BX(DGA_MENU_EXTERN_BX_ROWS)
 // converted once per workgroup into a bf16 LDS image; waves = 8 (two per SIMD, 64 x 64 wave tiles) or 4 (one per SIMD, 64 x 128).  Dense and masked-grouped rasters (split-K too);
 // DGA_E_TILING for the contiguous / indexed layouts
 int launch_bf16x_image(const GemmParams &p, int waves, hipStream_t stream);
-// the persistent form of the 128 x 256 in-register build (dense / masked grouped rasters); DGA_E_TILING: not a launch it takes
-int launch_bf16x_persistent(const GemmParams &p, hipStream_t stream);
-int launch_bf16x_persistent_f32(const GemmParams &p, hipStream_t stream);   // ... its fp32-output form (dense)
-int launch_bf16x_persistent_rows(const GemmParams &p, hipStream_t stream);  // ... and that with per-row sfb (dense)
+// the persistent form of the 128 x 256 in-register build (bf16 rows: dense / masked grouped rasters; the fp32 forms: dense);
+// DGA_E_TILING: not a launch it takes
+int launch_bf16x_persistent(const GemmParams &p, Out out, hipStream_t stream);
 // the k-grouped weight-gradient builds (KGROUP = 1; dga_launch_menu_p.hip): the one-tile tiles, the persistent 128 x 256 build and the
 // strict kernel (bm 64 or 32) on the G x tiles(M, N) raster whose groups lie along K; DGA_E_TILING for any other raster
 template <class Cfg>
@@ -102,7 +101,7 @@ int launch_unaligned(const GemmParams &p, hipStream_t stream);
 // DGA_KERNEL_SPLITK_WORKGROUP): bit-identical to the two-launch split-K with splitkFactor 8.  DGA_E_TILING for anything else
 int launch_wsk(const GemmParams &p, hipStream_t stream);
 // the LDS-DMA staged builds (M <= 32); math 1 = the bf16-exact policy's arithmetic; DGA_E_TILING: not a problem they take
-int launch_wsk_dma(const GemmParams &p, hipStream_t stream, int math = 0, bool f32 = false);   // f32: fp32 rows (+ C), math 1 only
+int launch_wsk_dma(const GemmParams &p, hipStream_t stream, int math = 0, Out out = Out::Bf16);   // Out::F32: math 1 only
 int wsk_rows(int m);
 int wsk_max_ntiles(int m);
 
@@ -121,13 +120,13 @@ int launch_streamk(const GemmParams &p, void *ws, size_t ws_bytes, bool ue8m0, h
 size_t streamk_workspace_bytes();
 // ... and of the bf16-exact policy's persistent 128 x 256 kernel (gemm_fp8_bf16x_streamk_kernel.hpp; dga_launch_menu_m.hip): any dense
 // raster with a partial last round.  DGA_E_TILING: not a launch it takes (nothing to cut, no workspace, co-residency not guaranteed)
-int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, bool f32 = false);   // f32: fp32 rows (+ C)
+int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, Out out = Out::Bf16);   // no Out::F32Rows form
 size_t bx_streamk_workspace_bytes();
 // workgroups a launch on this stream can count on being resident together, one per CU; 0 when a CU mask narrows the queue
 int coresident_workgroups(hipStream_t stream);
 // one-launch split-K for decode rows under the bf16-exact policy (gemm_fp8_bf16x_dsk_kernel.hpp; dga_launch_menu_n.hip): dense problems of
 // at most as many 64 x 128 tiles as CUs; `splits` = the tiling's splitkFactor.  DGA_E_TILING: not a launch it takes
-int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, bool f32 = false);   // f32: fp32 rows (+ C)
+int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, Out out = Out::Bf16);   // no Out::F32Rows form
 int bx_dsk_splits(int64_t tiles, int kb, int want, int cus);
 size_t bx_dsk_workspace_bytes(int64_t tiles, int splits);
 

@@ -4,6 +4,7 @@
 
 #include "dga_hip.h"
 #include <cstdint>
+#include <cstdlib>
 
 namespace dga {
 int record_hip(hipError_t e);
@@ -25,12 +26,39 @@ struct Fp8Strided {
     int64_t lda, ldb;
     int flags;
 };
+// the output form of an fp8 GEMM: bf16 rows, fp32 rows (+ C; dga_gemm_fp8_fp8_fp32_nt), or fp32 rows with per-row sfb (sfb is [N, KB],
+// one scale per row of B; dga_wgrad_gemm_fp8_fp8_fp32_nt).  One-to-one with the kernels' (OUT, SFB_ROWS) template pairs (0, 0), (1, 0), (1, 1)
+enum class Out { Bf16, F32, F32Rows };
+// one call of the fp8 launcher (run_fp8): the operands first, then what only some entry points set
+struct Fp8Call {
+    const void *a;
+    const float *sfa;
+    const void *b;
+    const float *sfb;
+    void *out;
+    int m, n, k;
+    const dga_tiling_t *tiling;     // nullptr: the entry's own selector picks one
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+    int groups = 1, b_groups = 1, expected_m = 0;
+    const int32_t *masked_m = nullptr;     // masked grouped layout
+    // contiguous-grouped layout: one A/out matrix of m rows (groups == 1 on that side), b_groups B matrices picked per row block
+    const int32_t *m_indices = nullptr;
+    const Fp8Indexed *ix = nullptr;        // indexed masked-grouped form: a / sfa / out are flat row buffers addressed through ix->row_index
+    const Fp8Strided *sd = nullptr;        // dense operands with their own row strides
+    Out kind = Out::Bf16;                  // the fp32 forms are dense only
+    const float *c_in = nullptr;           // fp32 forms: the optional fp32 addend (may be out)
+    unsigned long long *clock_stamps = nullptr;   // dga_gemm_fp8_loop_clock only: the loop-clock build, two words per wave
+};
 // the fp8 launcher behind the C-ABI GEMM entry points (dga_launch.hip); clock_stamps: see dga_diag.hip
-int run_fp8(const void *a, const float *sfa, const void *b, const float *sfb, void *out, const int32_t *masked_m,
-            const int32_t *m_indices, int b_groups, int groups, int m, int n, int k, int expected_m,
-            const dga_tiling_t *tiling, void *workspace, size_t workspace_bytes, hipStream_t stream,
-            unsigned long long *clock_stamps, const Fp8Indexed *ix, const Fp8Strided *sd = nullptr, bool out_f32 = false,
-            const float *c_in = nullptr, bool sfb_rows = false);
+int run_fp8(const Fp8Call &c);
+// $NAME as an integer, `dflt` when unset
+inline int env_int(const char *name, int dflt)
+{
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
 // compiled fp8 kernel menu (dga_launch.hip)
 int variant_count();
 void variant_info(int i, int *bm, int *bn, int *wm, int *wn, int *lds);

@@ -6,22 +6,9 @@ namespace dga {
 template <class Cfg, bool KTAIL, int OUT>
 static int launch_bf16x_one(const GemmParams &p, hipStream_t stream)
 {
-    auto kfn = gemm_fp8_blockscaled_nt_kernel<Cfg, 0, KTAIL, false, 1, false, OUT>;
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    unsigned grid = p.launch_tiles > 0 ? static_cast<unsigned>(p.launch_tiles)
-                                       : static_cast<unsigned>(p.groups) * p.tiles_m * p.tiles_n;
-    if (grid == 0) return DGA_OK;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, stream, p);
-    return record_hip(hipGetLastError());
+    const unsigned grid = p.launch_tiles > 0 ? static_cast<unsigned>(p.launch_tiles)
+                                             : static_cast<unsigned>(p.groups) * p.tiles_m * p.tiles_n;
+    return launch_kernel<gemm_fp8_blockscaled_nt_kernel<Cfg, 0, KTAIL, false, 1, false, OUT>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p);
 }
 
 template <class Cfg>

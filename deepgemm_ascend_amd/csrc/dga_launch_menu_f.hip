@@ -8,25 +8,11 @@ namespace dga {
 template <class Cfg, bool KTAIL, bool AIMAGE = false>
 static int launch_bf16x_image_one(const GemmParams &p, hipStream_t stream)
 {
-    void (*kfn)(const GemmParams);
-    if constexpr (AIMAGE) kfn = gemm_fp8_bf16x_aimage_kernel<KTAIL>;
-    else kfn = gemm_fp8_bf16x_image_kernel<Cfg, KTAIL>;
     static_assert(Cfg::LDS_BYTES <= 160 * 1024, "LDS of one CU");
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
     const unsigned grid = p.launch_tiles > 0 ? static_cast<unsigned>(p.launch_tiles)
                                              : static_cast<unsigned>(p.groups) * p.tiles_m * p.tiles_n;
-    if (grid == 0) return DGA_OK;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, stream, p);
-    return record_hip(hipGetLastError());
+    if constexpr (AIMAGE) return launch_kernel<gemm_fp8_bf16x_aimage_kernel<KTAIL>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p);
+    else return launch_kernel<gemm_fp8_bf16x_image_kernel<Cfg, KTAIL>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p);
 }
 
 int launch_bf16x_image(const GemmParams &p, int waves, hipStream_t stream)

@@ -8,58 +8,25 @@ namespace dga {
 template <int TM, int TNMAX, int D, bool KTAIL>
 static int launch_wsk_one(const GemmParams &p, unsigned grid, hipStream_t stream)
 {
-    auto kfn = gemm_fp8_wsk_kernel<TM, TNMAX, D, KTAIL>;
     constexpr int kLds = 8 * TM * 16 * TNMAX * 16 * 4;
     static_assert(kLds <= 160 * 1024, "LDS of one CU");
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), kLds, stream, p);
-    return record_hip(hipGetLastError());
+    return launch_kernel<gemm_fp8_wsk_kernel<TM, TNMAX, D, KTAIL>>(grid, 512, kLds, stream, p);
 }
 
 template <int TM, int TN, int D, bool KTAIL, int WAVES = 8, int MATH = 0, int OUT = 0>
 static int launch_wskd_one(const GemmParams &p, unsigned grid, hipStream_t stream)
 {
-    auto kfn = gemm_fp8_wskd_kernel<TM, TN, D, KTAIL, WAVES, MATH, OUT>;
     constexpr int kLds = WAVES * D * ((TM + TN) * 16 * 128 + (TM * 16 + 2 + 63) / 64 * 256);
     static_assert(kLds <= 160 * 1024, "LDS of one CU");
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(WAVES * 64), kLds, stream, p);
-    return record_hip(hipGetLastError());
+    return launch_kernel<gemm_fp8_wskd_kernel<TM, TN, D, KTAIL, WAVES, MATH, OUT>>(grid, WAVES * 64, kLds, stream, p);
 }
 
 template <int TM, int TN, int D, bool KTAIL, int MATH, int OUT = 0>
 static int launch_wskc_one(const GemmParams &p, unsigned grid, hipStream_t stream)
 {
-    auto kfn = gemm_fp8_wskc_kernel<TM, TN, D, KTAIL, MATH, OUT>;
     constexpr int kLds = 8 * (D * ((TM + TN) * 16 * 128 + (TM * 16 + 2 + 63) / 64 * 256) + TM * 16 * TN * 16 * 4);
     static_assert(kLds <= 160 * 1024, "LDS of one CU");
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), kLds, stream, p);
-    return record_hip(hipGetLastError());
+    return launch_kernel<gemm_fp8_wskc_kernel<TM, TN, D, KTAIL, MATH, OUT>>(grid, 512, kLds, stream, p);
 }
 
 // the LDS-DMA staged builds (M <= 32): one workgroup per CU (or per n-tile where there are fewer), each walking its n-tiles TN at a time.
@@ -90,7 +57,7 @@ static int launch_wsk_dma_math(const GemmParams &p, hipStream_t stream)
     // the passes).  Three tiles per pass where that saves a pass without leaving a single tile to the last one, two otherwise
     // (cold, M = 8: 18432 x 7168 30.8 -> 28.7 us, 16384 x 7168 26.6 -> 24.7, 28672 x 4096 31.3 -> 27.9; $DGA_WSK_CONT = 0 keeps the
     // pass-by-pass build).
-    static const int cont_env = [] { const char *e = std::getenv("DGA_WSK_CONT"); return e ? std::atoi(e) : 1; }();
+    static const int cont_env = env_int("DGA_WSK_CONT", 1);
     const int p2 = (per + 1) / 2, p3 = (per + 2) / 3;
     if (cont_env && per >= 4) {
         if (p3 < p2 && per % 3 != 1)
@@ -102,9 +69,10 @@ static int launch_wsk_dma_math(const GemmParams &p, hipStream_t stream)
     return kt ? launch_wskd_one<1, 2, 3, true, 8, MATH, OUT>(p, g, stream) : launch_wskd_one<1, 2, 3, false, 8, MATH, OUT>(p, g, stream);
 }
 
-int launch_wsk_dma(const GemmParams &p, hipStream_t stream, int math, bool f32)
+int launch_wsk_dma(const GemmParams &p, hipStream_t stream, int math, Out out)
 {
-    if (f32) return math == 1 ? launch_wsk_dma_math<1, 1>(p, stream) : DGA_E_TILING;   // (fp32 rows: the bf16-exact arithmetic only)
+    if (out == Out::F32Rows) return DGA_E_TILING;   // (no per-row-sfb build)
+    if (out == Out::F32) return math == 1 ? launch_wsk_dma_math<1, 1>(p, stream) : DGA_E_TILING;   // (fp32 rows: the bf16-exact arithmetic only)
     return math ? launch_wsk_dma_math<1>(p, stream) : launch_wsk_dma_math<0>(p, stream);
 }
 

@@ -13,19 +13,7 @@ template <int MATH>
 static int launch_streamk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
     typedef GemmCfg<256, 256, 4, 2, 2> Cfg;
-    auto kfn = gemm_fp8_blockscaled_nt_streamk_kernel<Cfg, MATH>;
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, stream, p, sk);
-    return record_hip(hipGetLastError());
+    return launch_kernel<gemm_fp8_blockscaled_nt_streamk_kernel<Cfg, MATH>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p, sk);
 }
 
 // ws: the caller's workspace, at least streamk_workspace_bytes().  DGA_E_TILING: not a problem this kernel takes (the caller then

@@ -39,24 +39,14 @@ template <bool KTAIL, int OUT = 0>
 static int launch_bx_streamk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
     typedef GemmCfg<128, 256, 2, 4, 3> Cfg;
-    auto kfn = gemm_fp8_bf16x_streamk_kernel<KTAIL, OUT>;
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, stream, p, sk);
-    return record_hip(hipGetLastError());
+    return launch_kernel<gemm_fp8_bf16x_streamk_kernel<KTAIL, OUT>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p, sk);
 }
 
 // ws: the caller's workspace, at least bx_streamk_workspace_bytes().  DGA_E_TILING: not a launch this kernel takes (no partial round to
 // cut, a layout it does not have, co-residency not guaranteed, no or too small a workspace): the caller runs the tiling's tile kernel.
-int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, bool f32)
+int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, Out out)
 {
+    if (out == Out::F32Rows) return DGA_E_TILING;   // (no per-row-sfb build)
     if (p.groups != 1 || p.masked_m || p.m_indices || p.row_index || p.splitk > 1 || p.tail_sub || p.stamps || p.launch_tiles) return DGA_E_TILING;
     if (p.kb_n < 2) return DGA_E_TILING;
     const int grid = coresident_workgroups(stream);
@@ -78,11 +68,11 @@ int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStre
 #ifdef DGA_BXSK_KNOBS
     GemmParams q = p;
     if (const char *e = std::getenv("DGA_BXSK_KNOB")) q.tail_begin = std::atoi(e);
-    if (f32) return DGA_E_TILING;   // (the diagnostic knobs ride on the bf16 build only)
+    if (out != Out::Bf16) return DGA_E_TILING;   // (the diagnostic knobs ride on the bf16 build only)
     return (p.k % 128) ? launch_bx_streamk_one<true>(q, sk, static_cast<unsigned>(grid), stream)
                        : launch_bx_streamk_one<false>(q, sk, static_cast<unsigned>(grid), stream);
 #endif
-    if (f32)
+    if (out == Out::F32)
         return (p.k % 128) ? launch_bx_streamk_one<true, 1>(p, sk, static_cast<unsigned>(grid), stream)
                            : launch_bx_streamk_one<false, 1>(p, sk, static_cast<unsigned>(grid), stream);
     return (p.k % 128) ? launch_bx_streamk_one<true>(p, sk, static_cast<unsigned>(grid), stream)

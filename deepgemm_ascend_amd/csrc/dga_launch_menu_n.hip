@@ -30,26 +30,16 @@ size_t bx_dsk_workspace_bytes(int64_t tiles, int splits)
 template <bool KTAIL, bool IMG = true, int OUT = 0>
 static int launch_bx_dsk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
-    auto kfn = gemm_fp8_bf16x_dsk_kernel<KTAIL, IMG, OUT>;
     constexpr int kLds = IMG ? DskCfg::IMG_LDS_BYTES : DskCfg::LDS_BYTES;
-    static std::once_flag once[64];
-    static hipError_t attr_err[64];
-    int dev = 0;
-    if (int rc = record_hip(hipGetDevice(&dev))) return rc;
-    if (dev < 0 || dev >= 64) return DGA_E_HIP;
-    std::call_once(once[dev], [&] {
-        attr_err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    });
-    if (int rc = record_hip(attr_err[dev])) return rc;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(DskCfg::NT), kLds, stream, p, sk);
-    return record_hip(hipGetLastError());
+    return launch_kernel<gemm_fp8_bf16x_dsk_kernel<KTAIL, IMG, OUT>>(grid, DskCfg::NT, kLds, stream, p, sk);
 }
 
 // splits: the tiling's splitkFactor (clamped by bx_dsk_splits).  ws: the caller's workspace, bx_dsk_workspace_bytes() at least where the
 // launch splits across workgroups.  DGA_E_TILING: not a launch this kernel takes (a layout it does not have, more tiles than CUs, fewer
 // than four k blocks, co-residency not guaranteed, no or too small a workspace): the caller runs the tiling's tile kernel.
-int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, bool f32)
+int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, Out out)
 {
+    if (out == Out::F32Rows) return DGA_E_TILING;   // (no per-row-sfb build)
     if (p.groups != 1 || p.masked_m || p.m_indices || p.row_index || p.splitk > 1 || p.tail_sub || p.stamps || p.launch_tiles) return DGA_E_TILING;
     const int cus = coresident_workgroups(stream);
     if (cus <= 0) return DGA_E_TILING;
@@ -99,7 +89,7 @@ int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes,
     if (q.tail_begin & 64)
         return (p.k % 128) ? launch_bx_dsk_one<true, false>(q, sk, grid, stream) : launch_bx_dsk_one<false, false>(q, sk, grid, stream);
 #endif
-    if (f32) return (p.k % 128) ? launch_bx_dsk_one<true, true, 1>(q, sk, grid, stream) : launch_bx_dsk_one<false, true, 1>(q, sk, grid, stream);
+    if (out == Out::F32) return (p.k % 128) ? launch_bx_dsk_one<true, true, 1>(q, sk, grid, stream) : launch_bx_dsk_one<false, true, 1>(q, sk, grid, stream);
     return (p.k % 128) ? launch_bx_dsk_one<true>(q, sk, grid, stream) : launch_bx_dsk_one<false>(q, sk, grid, stream);
 }
 
