@@ -90,26 +90,13 @@ gemm_fp8_bf16x_aimage_kernel(const GemmParams p)
 
     // ---- tile id (as gemm_fp8_blockscaled_nt_kernel: dense, masked grouped, split-K)
     const int nwg = gridDim.x, bid = blockIdx.x;
-    int tile;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        tile = p.xcd_remap ? (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3) : bid;
-    }
+    const int tile = p.xcd_remap ? xcd_chunk_first(nwg, bid & 7) + (bid >> 3) : bid;
     const int tiles_per_group = p.tiles_m * p.tiles_n;
     const int split = p.splitk > 1 ? tile / tiles_per_group : 0;
     const int g = p.splitk > 1 ? 0 : tile / tiles_per_group;
     const int t_in = tile - (p.splitk > 1 ? split : g) * tiles_per_group;
     int tm, tn;
-    {
-        const int gm = p.raster_group;
-        const int per = gm * p.tiles_n;
-        const int band = t_in / per;
-        const int first = band * gm;
-        const int rows = min(p.tiles_m - first, gm);
-        const int loc = t_in - band * per;
-        tm = first + loc % rows;
-        tn = loc / rows;
-    }
+    raster_tile(p.raster_group, p.tiles_m, p.tiles_n, t_in, tm, tn);
     const int M = p.masked_m ? min(p.masked_m[g], p.m) : p.m;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
@@ -206,12 +193,6 @@ gemm_fp8_bf16x_aimage_kernel(const GemmParams p)
     const int b_row = wn * 64 + 8 * (li >> 2) + (li & 3);
     const int b_off0 = 2 * Cfg::A_IMG + b_row * 128 + ((kg ^ swz_b(b_row)) * 16);
     const int b_off1 = 2 * Cfg::A_IMG + b_row * 128 + (((kg + 4) ^ swz_b(b_row)) * 16);
-    auto b_frag_off = [](int nt) { return (nt >> 1) * 4096 + (nt & 1) * 512; };
-    auto convert_b = [](const v4i (&raw)[2], v4i (&dst)[4], int c) {
-        const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
-        dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
-                                     : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-    };
 
     v4f acc[TM][TN];
 #pragma unroll
@@ -277,7 +258,7 @@ gemm_fp8_bf16x_aimage_kernel(const GemmParams p)
     braw[0] = *(const v4i *)(smem + b_off0);
     braw[1] = *(const v4i *)(smem + b_off1);
 #pragma unroll
-    for (int c = 0; c < 16; ++c) convert_b(braw, bfx[0], c);
+    for (int c = 0; c < 16; ++c) bx_convert(braw, bfx[0], c);
     braw[0] = *(const v4i *)(smem + b_off0 + b_frag_off(1));
     braw[1] = *(const v4i *)(smem + b_off1 + b_frag_off(1));
     DGA_STAMP_DECL
@@ -338,7 +319,7 @@ gemm_fp8_bf16x_aimage_kernel(const GemmParams p)
             if constexpr (u == Cfg::XGAP + Cfg::B_DMA + 1) issue_scales(cur, kb_fetch);
             // B(nt + 1) -> bfx[(nt + 1) & 1], one conversion per gap; raw halves reloaded with B(nt + 2) as they are released
             // (n-tiles 2, 3: the next block's B(0), B(1) from the stage that landed before X)
-            convert_b(braw, bfx[(nt + 1) & 1], gq);
+            bx_convert(braw, bfx[(nt + 1) & 1], gq);
             if constexpr (gq == 7 || gq == 15) {
                 constexpr int nn = nt + 2;
                 const uint8_t *src = nn < TN ? sc : sn;

@@ -62,10 +62,7 @@ gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
 
     // ---- workgroup -> (m-tile, n-tile, split): the m-tiles of one (n-tile, split) -- they read the same weight bytes -- lie on one XCD
     int v = blockIdx.x;
-    if (p.xcd_remap) {
-        const int nwg = gridDim.x, xcd = v & 7, q = nwg >> 3, r = nwg & 7;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-    }
+    if (p.xcd_remap) v = xcd_chunk_first(gridDim.x, v & 7) + (v >> 3);
     const int tm = v % p.tiles_m, rest = v / p.tiles_m, s = rest % S, tn = rest / S;
     const int tile = tn * p.tiles_m + tm;
     const int M = p.m, m0 = tm * BM, n0 = tn * BN;
@@ -142,11 +139,6 @@ gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-    auto convert = [](const v4i (&raw)[2], v4i (&dst)[4], int c) {
-        const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
-        dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
-                                     : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-    };
 
     // ---- prologue: the slice's first THREE blocks on their way (every stage of the ring: a slice is a handful of blocks, and the
     //      first round trip from a cold HBM is the longest) -- block 0 then issues no refill, its predecessor's stage being block 2's
@@ -197,15 +189,15 @@ gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
                 for (int i = 0; i < L; ++i) sa[i] = *(const float *)(sc + sa_off + i * 64);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int c = 0; c < 16; ++c) convert(braw[0], bfx[0], c);
+                for (int c = 0; c < 16; ++c) bx_convert(braw[0], bfx[0], c);
 #pragma unroll
-                for (int c = 0; c < 16; ++c) convert(araw[0], afx[0], c);
+                for (int c = 0; c < 16; ++c) bx_convert(araw[0], afx[0], c);
                 if constexpr (L > 2) {
                     araw[0][0] = *(const v4i *)(sc + a_off0 + 2 * 2048);
                     araw[0][1] = *(const v4i *)(sc + a_off1 + 2 * 2048);
                 }
 #pragma unroll
-                for (int c = 0; c < 16; ++c) convert(braw[1], bfx[1], c);
+                for (int c = 0; c < 16; ++c) bx_convert(braw[1], bfx[1], c);
 #pragma unroll
                 for (int i = 0; i < L; ++i) s_cur[i] = sa[i] * sfb0;
                 __builtin_amdgcn_sched_barrier(0);
@@ -223,7 +215,7 @@ gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
                     // A(mt + 1) is converted behind the MFMAs of m-tile mt (two conversions a gap); its raw bytes were read an m-tile earlier
                     if (mt + 1 < L) {
 #pragma unroll
-                        for (int c = 2 * g8; c < 2 * g8 + 2; ++c) convert(araw[(mt + 1) & 1], afx[(mt + 1) & 1], c);
+                        for (int c = 2 * g8; c < 2 * g8 + 2; ++c) bx_convert(araw[(mt + 1) & 1], afx[(mt + 1) & 1], c);
                         if (g8 == 4 * TN - 1 && mt + 3 < L) {
                             araw[(mt + 1) & 1][0] = *(const v4i *)(sc + a_off0 + (mt + 3) * 2048);
                             araw[(mt + 1) & 1][1] = *(const v4i *)(sc + a_off1 + (mt + 3) * 2048);
@@ -284,14 +276,14 @@ gemm_fp8_bf16x_dsk_kernel(const GemmParams p, const StreamKArgs sk)
                 for (int i = 0; i < L; ++i) sa[i] = *(const float *)(sc + sa_off + i * 64);
                 if (gw < L) {
 #pragma unroll
-                    for (int c = 0; c < 16; ++c) convert(araw[0], afx[0], c);
+                    for (int c = 0; c < 16; ++c) bx_convert(araw[0], afx[0], c);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) *(v4i *)(img + ((gw * 4 + q) * 64 + lane) * 16) = afx[0][q];
                 }
 #pragma unroll
-                for (int c = 0; c < 16; ++c) convert(braw[0], bfx[0], c);
+                for (int c = 0; c < 16; ++c) bx_convert(braw[0], bfx[0], c);
 #pragma unroll
-                for (int c = 0; c < 16; ++c) convert(braw[1], bfx[1], c);
+                for (int c = 0; c < 16; ++c) bx_convert(braw[1], bfx[1], c);
 #pragma unroll
                 for (int i = 0; i < L; ++i) s_cur[i] = sa[i] * sfb0;
             }

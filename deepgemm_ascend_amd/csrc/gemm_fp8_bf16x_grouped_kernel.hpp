@@ -182,12 +182,6 @@ gemm_fp8_bf16x_grouped_kernel(const GemmParams p)
     v4i afx[TM][4], bfx[2][4];      // bf16 fragments: [q] = the 8 bf16 of MFMA q of the chain
     v4i braw[2], araw[2][2];         // raw e4m3 bytes: [0] = bytes [16 kg, +16), [1] = bytes [64 + 16 kg, +16)
     float s_cur[TM], s_old[TM];
-    auto convert = [](const v4i (&raw)[2], v4i (&dst)[4], int c) {
-        const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
-        dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
-                                     : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-    };
-    auto b_frag_off = [](int nt) { return (nt >> 1) * 4096 + (nt & 1) * 512; };
 
     // counted wait at the top of a block: everything but the NL pieces of the younger stage in flight -- and, in a tile's first two
     // blocks, but the previous tile's output stores, which were issued behind those pieces (never fewer stores than `extra`)
@@ -275,13 +269,13 @@ gemm_fp8_bf16x_grouped_kernel(const GemmParams p)
             for (int i = 0; i < L; ++i) sa[i] = *(const float *)(sc + sa_off + i * 64);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int c = 0; c < 8; ++c) convert(braw, bfx[0], c);
+            for (int c = 0; c < 8; ++c) bx_convert(braw, bfx[0], c);
             braw[0] = *(const v4i *)(sc + b_off0 + b_frag_off(1));    // B(1), raw
 #pragma unroll
-            for (int c = 8; c < 16; ++c) convert(braw, bfx[0], c);
+            for (int c = 8; c < 16; ++c) bx_convert(braw, bfx[0], c);
             braw[1] = *(const v4i *)(sc + b_off1 + b_frag_off(1));
 #pragma unroll
-            for (int c = 0; c < 16; ++c) convert(araw[0], afx[0], c);
+            for (int c = 0; c < 16; ++c) bx_convert(araw[0], afx[0], c);
             if constexpr (L > 2) {
                 araw[0][0] = *(const v4i *)(sc + a_off0 + 2 * 2048);
                 araw[0][1] = *(const v4i *)(sc + a_off1 + 2 * 2048);
@@ -307,7 +301,7 @@ gemm_fp8_bf16x_grouped_kernel(const GemmParams p)
                 // A(mt + 1) is converted behind the MFMAs of the first n-tile's m-tile mt; its raw bytes were read a tile earlier
                 if (nt == 0 && mt + 1 < L) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) convert(araw[(mt + 1) & 1], afx[mt + 1], 4 * q + c);
+                    for (int c = 0; c < 4; ++c) bx_convert(araw[(mt + 1) & 1], afx[mt + 1], 4 * q + c);
                     if (q == 3 && mt + 3 < L) {
                         araw[(mt + 1) & 1][0] = *(const v4i *)(sc + a_off0 + (mt + 3) * 2048);
                         araw[(mt + 1) & 1][1] = *(const v4i *)(sc + a_off1 + (mt + 3) * 2048);
@@ -317,7 +311,7 @@ gemm_fp8_bf16x_grouped_kernel(const GemmParams p)
                 // B(nt + 2) as the conversions release them
                 if (nt + 1 < TN) {
 #pragma unroll
-                    for (int c = 16 * g / G; c < 16 * (g + 1) / G; ++c) convert(braw, bfx[(nt + 1) & 1], c);
+                    for (int c = 16 * g / G; c < 16 * (g + 1) / G; ++c) bx_convert(braw, bfx[(nt + 1) & 1], c);
                     if (nt + 2 < TN) {
                         if (g == G / 2 - 1) braw[0] = *(const v4i *)(sc + b_off0 + b_frag_off(nt + 2));
                         if (g == G - 1) braw[1] = *(const v4i *)(sc + b_off1 + b_frag_off(nt + 2));

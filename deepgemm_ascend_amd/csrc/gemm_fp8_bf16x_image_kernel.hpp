@@ -118,26 +118,13 @@ gemm_fp8_bf16x_image_kernel(const GemmParams p)
 
     // ---- tile id: XCD-aware remap, then the grouped raster (as gemm_fp8_blockscaled_nt_kernel; dense, masked grouped, split-K)
     const int nwg = gridDim.x, bid = blockIdx.x;
-    int tile;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        tile = p.xcd_remap ? (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3) : bid;
-    }
+    const int tile = p.xcd_remap ? xcd_chunk_first(nwg, bid & 7) + (bid >> 3) : bid;
     const int tiles_per_group = p.tiles_m * p.tiles_n;
     const int split = p.splitk > 1 ? tile / tiles_per_group : 0;
     const int g = p.splitk > 1 ? 0 : tile / tiles_per_group;
     const int t_in = tile - (p.splitk > 1 ? split : g) * tiles_per_group;
     int tm, tn;
-    {
-        const int gm = p.raster_group;
-        const int per = gm * p.tiles_n;
-        const int band = t_in / per;
-        const int first = band * gm;
-        const int rows = min(p.tiles_m - first, gm);
-        const int loc = t_in - band * per;
-        tm = first + loc % rows;
-        tn = loc / rows;
-    }
+    raster_tile(p.raster_group, p.tiles_m, p.tiles_n, t_in, tm, tn);
     const int M = p.masked_m ? min(p.masked_m[g], p.m) : p.m;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;

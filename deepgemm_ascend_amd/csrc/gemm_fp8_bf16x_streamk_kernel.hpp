@@ -1,4 +1,5 @@
-// Stream-K form of the bf16-exact policy's persistent 128 x 256 kernel (gemm_fp8_bf16x_persistent_kernel.hpp; dispatchPolicyTag 7,
+// Stream-K form of the bf16-exact policy's persistent 128 x 256 kernel (gemm_fp8_bf16x_persistent_kernel.hpp, with which it shares
+// the wave's register state and the k-block loop: gemm_fp8_bf16x_wave_tile.inc, gemm_fp8_bf16x_k_block.inc; dispatchPolicyTag 7,
 // kernelSerial DGA_KERNEL_STREAMK_ONE_LAUNCH): ONE launch, one workgroup per CU.  The whole rounds of a dense raster run as in the
 // persistent kernel; the LAST, partial round -- R tiles for P workgroups -- is cut along K so that it costs a fraction of a round:
 //   * R <= P / 2: every remainder tile is cut into s = min(P / R, 8) equal k ranges (part-major over the workgroups, so that the
@@ -226,55 +227,8 @@ gemm_fp8_bf16x_streamk_kernel(const GemmParams p, const StreamKArgs sk)
         }
     };
 
-    // ---- per-lane fragment read offsets (bytes inside a stage): gemm_fp8_kernel.hpp
-    const int a_row = wm * (BM / Cfg::kWM) + li;
-    const int a_off0 = a_row * 128 + ((kg ^ swz_a(a_row)) * 16);
-    const int a_off1 = a_row * 128 + (((kg + 4) ^ swz_a(a_row)) * 16);
-    const int b_row = wn * (BN / WN) + 8 * (li >> 2) + (li & 3);
-    const int b_off0 = Cfg::A_BYTES + b_row * 128 + ((kg ^ swz_b(b_row)) * 16);
-    const int b_off1 = Cfg::A_BYTES + b_row * 128 + (((kg + 4) ^ swz_b(b_row)) * 16);
-    const int sa_off = Cfg::A_BYTES + Cfg::B_BYTES + (wm * (BM / Cfg::kWM) + li) * 4;
-    const int sb_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + (wn * (BN / WN)) / 128) * 4;
-
-    v4f acc[TM][TN];
-    v4f part[RING];
-    v4i afx[TM][4], bfx[2][4];      // bf16 fragments: [q] = the 8 bf16 of MFMA q of the chain
-    v4i braw[2], araw[2][2];         // raw e4m3 bytes: [0] = bytes [16 kg, +16), [1] = bytes [64 + 16 kg, +16)
-    float s_cur[TM], s_old[TM], s_nxt[TM];
-    auto clear_tile = [&]() {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < RING; ++i) part[i] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < TM; ++i) s_old[i] = 0.f;    // the first LAGT tiles "promote the previous block": part (= 0) * 0
-    };
-    auto convert = [](const v4i (&raw)[2], v4i (&dst)[4], int c) {
-        const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
-        dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
-                                     : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-    };
-    auto b_frag_off = [](int nt) { return (nt >> 1) * 4096 + (nt & 1) * 512; };
-    auto first_fragments = [&](const uint8_t *st) {
-        const float sfb0 = *(const float *)(st + sb_off);
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt) {
-            araw[mt & 1][0] = *(const v4i *)(st + a_off0 + mt * 2048);
-            araw[mt & 1][1] = *(const v4i *)(st + a_off1 + mt * 2048);
-#pragma unroll
-            for (int c = 0; c < 16; ++c) convert(araw[mt & 1], afx[mt], c);
-            s_cur[mt] = *(const float *)(st + sa_off + mt * 64) * sfb0;
-            s_nxt[mt] = 0.f;
-        }
-        braw[0] = *(const v4i *)(st + b_off0);
-        braw[1] = *(const v4i *)(st + b_off1);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) convert(braw, bfx[0], c);
-        braw[0] = *(const v4i *)(st + b_off0 + b_frag_off(1));   // B(1) of block 0, raw
-        braw[1] = *(const v4i *)(st + b_off1 + b_frag_off(1));
-    };
+    constexpr int SFB_ROWS = 0;   // (block sfb only)
+#include "gemm_fp8_bf16x_wave_tile.inc"
     auto rows_present = [&](const Seg &t) { return t.m0 + wm * (BM / Cfg::kWM) < p.m; };   // (wave-uniform)
 
     // ---- prologue: the first two blocks of the first segment on their way, the first landed
@@ -309,54 +263,7 @@ gemm_fp8_bf16x_streamk_kernel(const GemmParams p, const StreamKArgs sk)
 #pragma unroll
             for (int idx = 0; idx < NL; ++idx) refill(idx);
         } else {
-            const uint8_t *sc = smem + cur * Cfg::STAGE_BYTES;   // being consumed (B raw reloads of this block)
-            const uint8_t *sn = smem + nxt * Cfg::STAGE_BYTES;   // landed: the next block's fragments are read ahead from it
-#pragma unroll
-            for (int u = 0; u < 4 * TILES; ++u) {
-                const int t = u >> 2, q4 = u & 3, nt = t / TM, mt = t % TM, g = u % G;
-                part[t % RING] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    __builtin_bit_cast(v8bf, bfx[nt & 1][q4]), __builtin_bit_cast(v8bf, afx[mt][q4]),
-                    q4 == 0 ? v4f{0.f, 0.f, 0.f, 0.f} : part[t % RING], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (u >= 4 && u < 4 + NL) refill(u - 4);
-#pragma unroll
-                for (int c = 0; c < 16 / G; ++c) convert(braw, bfx[(nt + 1) & 1], (16 / G) * g + c);
-                {
-                    const int nn = nt + 2;
-                    const uint8_t *src = nn < TN ? sc : sn;
-                    const int off = b_frag_off(nn < TN ? nn : nn - TN);
-                    if (g == G / 2 - 1) braw[0] = *(const v4i *)(src + b_off0 + off);
-                    if (g == G - 1) braw[1] = *(const v4i *)(src + b_off1 + off);
-                }
-                if (nt == TN - 1 && q4 == 0) {
-                    araw[mt & 1][0] = *(const v4i *)(sn + a_off0 + mt * 2048);
-                    araw[mt & 1][1] = *(const v4i *)(sn + a_off1 + mt * 2048);
-                }
-                if (nt == TN - 1 && mt >= 1) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) convert(araw[(mt - 1) & 1], afx[mt - 1], 4 * q4 + c);
-                }
-                if (t == 0) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) convert(araw[(TM - 1) & 1], afx[TM - 1], 4 * q4 + c);
-                }
-                if (u == 4 * TILES - 8) {
-                    const float sfbn = *(const float *)(sn + sb_off);
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) s_nxt[i] = *(const float *)(sn + sa_off + i * 64) * sfbn;
-                }
-                {
-                    const int j = t >= LAGT ? t - LAGT : TILES + t - LAGT, jn = j / TM, jm = j % TM;
-                    const float sv = t >= LAGT ? s_cur[jm] : s_old[jm];
-                    acc[jm][jn][q4] = __builtin_fmaf(part[j % RING][q4], sv, acc[jm][jn][q4]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                s_old[i] = s_cur[i];
-                s_cur[i] = s_nxt[i];
-            }
+#include "gemm_fp8_bf16x_k_block.inc"
         }
         const int f = cur;
         cur = nxt; nxt = fill; fill = f;

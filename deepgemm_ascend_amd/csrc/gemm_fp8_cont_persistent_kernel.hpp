@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_cont_persiste
     int first = 0, count = total, step = gridDim.x, local = blockIdx.x;
     if (p.xcd_remap) {
         const int xcd = blockIdx.x & 7, q = total >> 3, r = total & 7;
-        first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+        first = xcd_chunk_first(total, xcd);
         count = q + (xcd < r ? 1 : 0);
         step = ((int)gridDim.x - xcd + 7) >> 3;
         local = blockIdx.x >> 3;
@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_cont_persiste
     const int sa_off = Cfg::A_BYTES + Cfg::B_BYTES + (wm * (BM / Cfg::kWM) + li) * 4;
     const int sb_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + (wn * (BN / WN)) / 128) * 4;
     auto read_b = [&](const uint8_t *st, int nt) {
-        const int boff = (nt >> 1) * 4096 + (nt & 1) * 512;
+        const int boff = b_frag_off(nt);
         const v4i lo = *(const v4i *)(st + b_off0 + boff);
         const v4i hi = *(const v4i *)(st + b_off1 + boff);
         return v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};

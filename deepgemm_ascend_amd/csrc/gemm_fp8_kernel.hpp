@@ -138,6 +138,44 @@ __device__ __forceinline__ void kgroup_copy_tile(const GemmParams &p, int g, int
     }
 }
 
+// ---- the tile walk every fp8 kernel shares
+// Tile t_in of one group's raster -> (tm, tn): bands of gm (GemmParams::raster_group) tile-rows, walked column by column inside a
+// band, so that consecutive tiles share A and B panels.  (Plain values, not the params: a kernel that hands its by-value params
+// on by reference keeps them addressable, and that moved the code of the image builds.  The fast policy's persistent, continuous
+// and Stream-K kernels keep the decode written out: inside their tile-list lambdas the call commuted scalar adds.)
+__device__ __forceinline__ void raster_tile(int gm, int tiles_m, int tiles_n, int t_in, int &tm, int &tn)
+{
+    const int per = gm * tiles_n;
+    const int band = t_in / per;
+    const int row0 = band * gm;
+    const int rows = min(tiles_m - row0, gm);
+    const int loc = t_in - band * per;
+    tm = row0 + loc % rows;
+    tn = loc / rows;
+}
+// n items cut into eight contiguous chunks, one per XCD (blocks b, b + 8, ... share an XCD and its L2): where chunk `xcd` starts
+__device__ __forceinline__ int xcd_chunk_first(int n, int xcd)
+{
+    const int q = n >> 3, r = n & 7;
+    return xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+}
+
+// ---- the fragment layout of the 16 x 16 wave tiles (the orientation note above), shared by every build that reads the LDS image
+// B fragment of n-tile nt, in bytes from the wave's first B row: n_local(nt, 0) = 32 (nt >> 1) + 4 (nt & 1) rows of 128 bytes
+__device__ __forceinline__ int b_frag_off(int nt) { return (nt >> 1) * 4096 + (nt & 1) * 512; }
+// bf16-exact builds: conversion c (0..15) of a fragment -- dword c >> 1 of the 32 raw e4m3 bytes, half c & 1 -> dword c & 3 of
+// MFMA (c >> 2) of the chain.  (c is a constant after unrolling; the builtin's half selector must be an immediate.)
+__device__ __forceinline__ void bx_convert(const v4i (&raw)[2], v4i (&dst)[4], int c, float scale = 1.0f)
+{
+#ifdef DGA_ABL_BX_NOCVT   // diagnostic (results are garbage): the MFMAs run on whatever the fragment registers hold
+    asm volatile("" : "+v"(dst[c >> 2][c & 3]));
+    return;
+#endif
+    const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
+    dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, scale, true))
+                                 : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, scale, false));
+}
+
 // In-kernel stamps (diagnostic build only; cdna_hip_programming.md section 7 "In-kernel stamps").
 #ifdef DGA_STAMPS
 #define DGA_STAMP_DECL unsigned long long st_prev = 0, st_seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -280,11 +318,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
         nwg >>= 1;
         if (bid >= nwg) { pass = 1; bid -= nwg; }
     }
-    int tile;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        tile = p.xcd_remap ? (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3) : bid;
-    }
+    const int tile = p.xcd_remap ? xcd_chunk_first(nwg, bid & 7) + (bid >> 3) : bid;
     const int tiles_per_group = p.tiles_m * p.tiles_n;
     // split-K (dense only, groups == 1): the grid is splitk x tiles, split-major, so the splits of one tile run on
     // different XCDs/CUs at the same time; grouped: group-major
@@ -296,16 +330,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
     int tm, tn;
     const int sub = p.tail_sub ? (t_in & 3) : 0;
     if (p.tail_sub) t_in = p.tail_begin + (t_in >> 2);
-    {
-        const int gm = p.raster_group;
-        const int per = gm * p.tiles_n;
-        const int band = t_in / per;
-        const int first = band * gm;
-        const int rows = min(p.tiles_m - first, gm);
-        const int loc = t_in - band * per;
-        tm = first + loc % rows;
-        tn = loc / rows;
-    }
+    raster_tile(p.raster_group, p.tiles_m, p.tiles_n, t_in, tm, tn);
     if (p.tail_sub) {  // quarter tile (sub & 1, sub >> 1) of parent tile (tm, tn)
         tm = 2 * tm + (sub & 1);
         tn = 2 * tn + (sub >> 1);
@@ -791,7 +816,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
             asm volatile("" ::: "memory");
         };
         auto read_b = [&](const uint8_t *st, int nt) {
-            const int boff = (nt >> 1) * 4096 + (nt & 1) * 512;
+            const int boff = b_frag_off(nt);
             const v4i lo = *(const v4i *)(st + b_off0 + boff);
             const v4i hi = *(const v4i *)(st + b_off1 + boff);
             return v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -986,18 +1011,6 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
 #pragma unroll
             for (int i = 0; i < TN; ++i) sbv[i] = v4f{0.f, 0.f, 0.f, 0.f};
         static_assert(SFB_ROWS == 0 || TM >= LAGT, "the lagged promotions are those of n-tile TN - 1");
-        // conversion c (0..15) of a fragment: dword c >> 1 of the 32 raw bytes, half c & 1 -> dword c & 3 of MFMA (c >> 2).
-        // (c is a constant after unrolling; the builtin's half selector must be an immediate)
-        auto convert = [](const v4i (&raw)[2], v4i (&dst)[4], int c, float scale = 1.0f) {
-#ifdef DGA_ABL_BX_NOCVT   // diagnostic (results are garbage): the MFMAs run on whatever the fragment registers hold
-            asm volatile("" : "+v"(dst[c >> 2][c & 3]));
-            return;
-#endif
-            const int w = raw[(c >> 1) >> 2][(c >> 1) & 3];
-            dst[c >> 2][c & 3] = (c & 1) ? __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, scale, true))
-                                         : __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, scale, false));
-        };
-        auto b_frag_off = [](int nt) { return (nt >> 1) * 4096 + (nt & 1) * 512; };
         // prologue: blocks 0 and 1 on their way, block 0 landed; its fragments converted in one burst (once per tile)
 #pragma unroll
         for (int d = 0; d < 2; ++d)
@@ -1017,14 +1030,14 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
                 else
                 s_cur[mt] = *(const float *)(smem + sa_off + mt * 64) * sfb0;
 #pragma unroll
-                for (int c = 0; c < 16; ++c) convert(araw[mt & 1], afx[mt], c, UE ? s_cur[mt] : 1.0f);
+                for (int c = 0; c < 16; ++c) bx_convert(araw[mt & 1], afx[mt], c, UE ? s_cur[mt] : 1.0f);
                 s_old[mt] = 0.f;    // the first LAGT tiles "promote the previous block": part (= 0) * 0
                 s_nxt[mt] = 0.f;
             }
             braw[0] = *(const v4i *)(smem + b_off0);
             braw[1] = *(const v4i *)(smem + b_off1);
 #pragma unroll
-            for (int c = 0; c < 16; ++c) convert(braw, bfx[0], c);
+            for (int c = 0; c < 16; ++c) bx_convert(braw, bfx[0], c);
             braw[0] = *(const v4i *)(smem + b_off0 + b_frag_off(1));   // B(1) of block 0, raw
             braw[1] = *(const v4i *)(smem + b_off1 + b_frag_off(1));
         }
@@ -1076,7 +1089,7 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
                 // B(nt + 1) -> bfx[(nt + 1) & 1]: 16 conversions over the n-tile's G gaps; the raw halves are reloaded with
                 // B(nt + 2) as they are released (from the readable stage once nt + 2 runs past this block)
 #pragma unroll
-                for (int c = 0; c < 16 / G; ++c) convert(braw, bfx[(nt + 1) & 1], (16 / G) * g + c);
+                for (int c = 0; c < 16 / G; ++c) bx_convert(braw, bfx[(nt + 1) & 1], (16 / G) * g + c);
                 {
                     const int nn = nt + 2;
                     const uint8_t *src = nn < TN ? sc : sn;
@@ -1096,11 +1109,11 @@ __global__ void __launch_bounds__(Cfg0::NT) gemm_fp8_blockscaled_nt_kernel(const
 #endif
                 if (nt == TN - 1 && mt >= 1) {     // the tile behind (mt - 1, TN - 1): A[mt - 1] of the next block
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) convert(araw[(mt - 1) & 1], afx[mt - 1], 4 * q + c, UE ? s_nxt[mt - 1] : 1.0f);
+                    for (int c = 0; c < 4; ++c) bx_convert(araw[(mt - 1) & 1], afx[mt - 1], 4 * q + c, UE ? s_nxt[mt - 1] : 1.0f);
                 }
                 if (t == 0) {                      // the tile behind the previous block's (TM - 1, TN - 1): A[TM - 1] of THIS block
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) convert(araw[(TM - 1) & 1], afx[TM - 1], 4 * q + c, UE ? s_cur[TM - 1] : 1.0f);
+                    for (int c = 0; c < 4; ++c) bx_convert(araw[(TM - 1) & 1], afx[TM - 1], 4 * q + c, UE ? s_cur[TM - 1] : 1.0f);
                 }
                 // the next block's scales: needed from its first promotions, LAGT tiles into it -- or (UE) by the conversions of its A
                 // fragments, which start in this block's last n-tile: read at the block's first gap (the stage has landed)

@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_persistent_ke
     int first = 0, count = total, step = gridDim.x, slot = blockIdx.x;
     if (p.xcd_remap) {
         const int xcd = blockIdx.x & 7, q = total >> 3, r = total & 7;
-        first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+        first = xcd_chunk_first(total, xcd);
         count = q + (xcd < r ? 1 : 0);
         step = ((int)gridDim.x - xcd + 7) >> 3;
         slot = blockIdx.x >> 3;

@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_fp8_blockscaled_nt_streamk_kerne
     const int sa_off = Cfg::A_BYTES + Cfg::B_BYTES + (wm * (BM / Cfg::kWM) + li) * 4;
     const int sb_off = Cfg::A_BYTES + Cfg::B_BYTES + (BM + (wn * (BN / WN)) / 128) * 4;
     auto read_b = [&](const uint8_t *st, int nt) {
-        const int boff = (nt >> 1) * 4096 + (nt & 1) * 512;
+        const int boff = b_frag_off(nt);
         const v4i lo = *(const v4i *)(st + b_off0 + boff);
         const v4i hi = *(const v4i *)(st + b_off1 + boff);
         return v8i{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
