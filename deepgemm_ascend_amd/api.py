@@ -967,6 +967,57 @@ def per_block_cast_to_fp8(x: torch.Tensor, aligned_rows: bool = False, use_ue8m0
     return _cast("dga_cast_to_fp8_128x128", x, 128, aligned_rows, use_ue8m0)
 
 
+def silu_and_mul_per_token_cast_to_fp8(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
+                                       m_indices: Optional[torch.Tensor] = None,
+                                       out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, use_ue8m0: bool = False,
+                                       sync: bool = False):
+    """The activation of an expert MLP fused into the quantiser of its second GEMM (dga_silu_mul_cast_to_fp8_1x128):
+    (q, sf) = per_token_cast_to_fp8(silu(x[..., :H]) * x[..., H:]) with the product kept in fp32, x [..., 2H] float32 / bfloat16 /
+    float16 (gate first, up second: the silu_and_mul convention) -> q [..., H] float8_e4m3fn, sf [..., ceil(H/128)] float32.
+      x [rows, 2H]                                   every row
+      x [G, Mmax, 2H], masked_m int32 [G]            rows r >= masked_m[g] are neither read nor written (the masked grouped GEMM's layout)
+      x [rows, 2H],    m_indices int32 [rows]        rows with a negative index are neither read nor written (the contiguous one's)
+    The masks are read on the device: a captured graph follows the routing.  out=(q, sf) writes into the caller's tensors (q uint8
+    or float8_e4m3fn); without it both are torch.empty, so the rows a mask excludes are UNINITIALISED -- pass out to give them
+    a value.  For gate >= 20 the result is the quantiser's on fl32(gate * up) bit for bit, for |gate| <= 16 the fp32 product is
+    within relative 2^-18 of the real-number value; use_ue8m0 as in per_token_cast_to_fp8."""
+    _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
+    want_dim = 3 if masked_m is not None else 2
+    _require(x.dim() == want_dim and x.is_contiguous(),
+             "x must be a contiguous [G, Mmax, 2H] tensor with masked_m" if masked_m is not None else "x must be a contiguous [rows, 2H] tensor")
+    _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
+    _require(x.shape[-1] % 2 == 0, "the last dimension of x must be even (gate and up halves)")
+    h = x.shape[-1] // 2
+    lead = tuple(x.shape[:-1])
+    groups, rows = (lead if masked_m is not None else (1, lead[0]))
+    if masked_m is not None:
+        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
+                 f"masked_m must be a contiguous int32 [{groups}]")
+    if m_indices is not None:
+        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
+                 f"m_indices must be a contiguous int32 [{rows}]")
+    hb = (h + 127) // 128
+    if out is None:
+        q = torch.empty(lead + (h,), dtype=torch.uint8, device=x.device)
+        sf = torch.empty(lead + (hb,), dtype=torch.float32, device=x.device)
+    else:
+        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be (q, sf)")
+        q, sf = out
+        _fp8_bytes(q)
+        _require(tuple(q.shape) == lead + (h,) and q.is_contiguous(), f"out q must be contiguous {list(lead + (h,))}")
+        _require(sf.dtype == torch.float32 and tuple(sf.shape) == lead + (hb,) and sf.is_contiguous(),
+                 f"out sf must be contiguous float32 {list(lead + (hb,))}")
+    with _device_guard(x, q, sf, *(t for t in (masked_m, m_indices) if t is not None)):
+        rc = _lib.lib().dga_silu_mul_cast_to_fp8_1x128(
+            x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
+            m_indices.data_ptr() if m_indices is not None else None, q.data_ptr(), sf.data_ptr(),
+            _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
+        _lib.check(rc, "silu_and_mul_per_token_cast_to_fp8")
+        if sync:
+            torch.cuda.current_stream(x.device).synchronize()
+    return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

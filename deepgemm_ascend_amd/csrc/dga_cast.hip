@@ -12,125 +12,9 @@
 
 #include "dga_hip.h"
 #include "dga_internal.hpp"
+#include "dga_cast_device.hpp"
 
 namespace dga {
-
-typedef float v4f_c __attribute__((ext_vector_type(4)));
-typedef int v4i_c __attribute__((ext_vector_type(4)));
-typedef int v2i_c __attribute__((ext_vector_type(2)));
-
-// two fp32 -> two e4m3fn bytes (low 16 bits), any input.  v_cvt_pk_fp8_f32 is OCP e4m3fn on gfx950 (round to nearest
-// even, subnormals included) but turns overflow into the NaN code and every NaN into 0xFF (probed:
-// scripts/ubench/probe_cvt_fp8.hip); the definition saturates (satfinite) and encodes NaN as sign | 0x7F, so inputs
-// are clamped first and NaN is patched afterwards.
-__device__ __forceinline__ uint32_t cvt2_e4m3fn(float a, float b)
-{
-    const float ca = __builtin_fminf(__builtin_fmaxf(a, -448.f), 448.f);
-    const float cb = __builtin_fminf(__builtin_fmaxf(b, -448.f), 448.f);
-    uint32_t r = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(ca, cb, 0, false) & 0xFFFFu;
-    if (a != a) r = (r & 0xFF00u) | ((__float_as_uint(a) >> 24) & 0x80u) | 0x7Fu;
-    if (b != b) r = (r & 0x00FFu) | ((((__float_as_uint(b) >> 24) & 0x80u) | 0x7Fu) << 8);
-    return r;
-}
-
-// max over the 16 lanes of a DPP row (= one 1x128 block), result in every lane: row_mirror, row_half_mirror, then the
-// two quad permutes -- four v_max_f32_dpp, no LDS traffic.
-template <int CTRL> __device__ __forceinline__ float dpp_max(float x)
-{
-    const int y = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false);
-    return __builtin_fmaxf(x, __builtin_bit_cast(float, y));
-}
-__device__ __forceinline__ float row16_max(float x)
-{
-    x = dpp_max<0x140>(x);  // row_mirror: lane i <-> 15 - i
-    x = dpp_max<0x141>(x);  // row_half_mirror: i <-> 7 - i inside each half
-    x = dpp_max<0x4E>(x);   // quad_perm [2,3,0,1]
-    x = dpp_max<0xB1>(x);   // quad_perm [1,0,3,2]
-    return x;
-}
-
-// DGA_CAST_UE8M0: the block scale rounded UP to a power of two, 2^ceil(log2(amax / 448)) -- upstream DeepGEMM's use_ue8m0
-// quantisation; such scales ride in the matrix instruction's E8M0 operands (DGA_POLICY_UE8M0_SCALES).  Exact on the bits: a
-// scale with a non-zero mantissa moves to the next exponent.
-__device__ __forceinline__ float block_scale(float amax, bool ue8m0)
-{
-    float s = amax > 0.f ? amax / 448.f : 1.f;
-    if (ue8m0) {
-        const uint32_t b = __float_as_uint(s);
-        if (b & 0x007FFFFFu) s = __uint_as_float((b & 0x7F800000u) + 0x00800000u);
-    }
-    return s;
-}
-
-__device__ __forceinline__ bool has_ff_byte(uint32_t w) { return (((~w) - 0x01010101u) & w & 0x80808080u) != 0; }
-
-// 8 values of one scale block -> 8 codes.  Fast path: the IEEE quotient x / s by the compiler's own fp32 division
-// recurrence (rcp, one Newton step, then q, two residual corrections -- the final fma is the correctly rounded
-// quotient) with the reciprocal refined once per block instead of once per element, and without the range scaling,
-// which is not needed while s is far from the ends of the exponent range.  No clamp either: |x / s| <= 448 (1 + 2^-22)
-// rounds to 448.  Anything unusual -- s tiny, huge, infinite, or a NaN among the inputs (the hardware's 0xFF code
-// shows it) -- takes the general path: true division, clamp, NaN patch.
-__device__ __forceinline__ void quant8(const float (&v)[8], float s, uint32_t &w0, uint32_t &w1)
-{
-    const uint32_t sb = __float_as_uint(s);
-    const bool s_ok = (sb - 0x20000000u) < 0x3F000000u;  // 2^-63 <= s < 2^63
-    const float r0 = __builtin_amdgcn_rcpf(s);
-    const float r1 = __builtin_fmaf(__builtin_fmaf(-s, r0, 1.f), r0, r0);
-    float q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float q0 = v[j] * r1;
-        const float q1 = __builtin_fmaf(__builtin_fmaf(-s, q0, v[j]), r1, q0);
-        // s > 0: the quotient has x's sign, also when it is a zero (the residual steps turn -0 into +0)
-        q[j] = __builtin_copysignf(__builtin_fmaf(__builtin_fmaf(-s, q1, v[j]), r1, q1), v[j]);
-    }
-    w0 = ((uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false) & 0xFFFFu) |
-         ((uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], 0, false) << 16);
-    w1 = ((uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[4], q[5], 0, false) & 0xFFFFu) |
-         ((uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[6], q[7], 0, false) << 16);
-    if (!s_ok || has_ff_byte(w0) || has_ff_byte(w1)) {
-        w0 = cvt2_e4m3fn(v[0] / s, v[1] / s) | (cvt2_e4m3fn(v[2] / s, v[3] / s) << 16);
-        w1 = cvt2_e4m3fn(v[4] / s, v[5] / s) | (cvt2_e4m3fn(v[6] / s, v[7] / s) << 16);
-    }
-}
-
-template <typename T> struct Elem;
-template <> struct Elem<float> {
-    static constexpr int kBytes = 4;
-    static __device__ __forceinline__ float load(const void *p, int64_t i) { return ((const float *)p)[i]; }
-    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8])
-    {
-        const v4f_c lo = *(const v4f_c *)((const float *)p + i), hi = *(const v4f_c *)((const float *)p + i + 4);
-        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-    }
-};
-struct Bf16Tag {};
-struct F16Tag {};
-template <> struct Elem<Bf16Tag> {
-    static constexpr int kBytes = 2;
-    static __device__ __forceinline__ float cv(uint32_t h) { return __uint_as_float(h << 16); }
-    static __device__ __forceinline__ float load(const void *p, int64_t i) { return cv(((const uint16_t *)p)[i]); }
-    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8])
-    {
-        const v4i_c w = *(const v4i_c *)((const uint16_t *)p + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = __uint_as_float((uint32_t)w[j] << 16);
-            v[2 * j + 1] = __uint_as_float((uint32_t)w[j] & 0xFFFF0000u);
-        }
-    }
-};
-template <> struct Elem<F16Tag> {
-    static constexpr int kBytes = 2;
-    static __device__ __forceinline__ float load(const void *p, int64_t i) { return (float)((const _Float16 *)p)[i]; }
-    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8])
-    {
-        typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-        const v8h w = *(const v8h *)((const _Float16 *)p + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)w[j];
-    }
-};
 
 // 16 lanes share one 1x128 block, 8 consecutive elements per lane: a wave covers 4 blocks per pass, loads and stores
 // are contiguous per 16-lane group (256 / 512 bytes in, 128 bytes out).

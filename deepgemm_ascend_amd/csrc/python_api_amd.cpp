@@ -14,6 +14,7 @@
 #include <initializer_list>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "dga_hip.h"
 
@@ -324,6 +325,35 @@ std::tuple<at::Tensor, at::Tensor> cast_to_fp8(const at::Tensor &x, int block_ro
     return {q, sf};
 }
 
+// silu(x[..., :H]) * x[..., H:] -> the per-token quantiser, one pass (dga_silu_mul_cast_to_fp8_1x128).  x [rows, 2H], or [G, Mmax, 2H] with
+// masked_m int32 [G]: the rows a mask excludes are not written (the outputs are at::empty: they hold no value there).
+std::tuple<at::Tensor, at::Tensor> silu_and_mul_per_token_cast_to_fp8(const at::Tensor &x, const c10::optional<at::Tensor> &masked_m)
+{
+    on_device(x, "x");
+    const bool masked = masked_m.has_value();
+    TORCH_CHECK(x.dim() == (masked ? 3 : 2), masked ? "x must be [G, Mmax, 2H] with masked_m" : "x must be [rows, 2H]");
+    const at::ScalarType st = x.scalar_type();
+    TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "x must be float32 / bfloat16 / float16");
+    TORCH_CHECK(x.size(-1) % 2 == 0, "the last dimension of x must be even (gate and up halves)");
+    const int64_t h = x.size(-1) / 2, groups = masked ? x.size(0) : 1, rows = masked ? x.size(1) : x.size(0);
+    if (masked) {
+        on_device(*masked_m, "masked_m");
+        TORCH_CHECK(masked_m->scalar_type() == at::kInt && masked_m->dim() == 1 && masked_m->size(0) == groups, "masked_m must be int32 [G]");
+        TORCH_CHECK(masked_m->device() == x.device(), "all tensors must live on one device");
+    }
+    const c10::OptionalDeviceGuard guard(at::device_of(x));
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    shape.back() = h;
+    at::Tensor q = at::empty(shape, x.options().dtype(at::kFloat8_e4m3fn));
+    shape.back() = (h + 127) / 128;
+    at::Tensor sf = at::empty(shape, x.options().dtype(at::kFloat));
+    const int dt = st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16;
+    check(dga_silu_mul_cast_to_fp8_1x128(x.data_ptr(), dt, groups, rows, h, masked ? masked_m->data_ptr<int32_t>() : nullptr, nullptr,
+                                         q.data_ptr(), sf.data_ptr<float>(), 0, cur_stream()),
+          "silu_and_mul_per_token_cast_to_fp8");
+    return {q, sf};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.cpp:30)
@@ -350,5 +380,6 @@ PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.c
     m.def("get_m_alignment_for_contiguous_layout", [] { return DGA_CONTIGUOUS_M_ALIGNMENT; });
     m.def("per_token_cast_to_fp8", [](const at::Tensor &x) { return cast_to_fp8(x, 1); });
     m.def("per_block_cast_to_fp8", [](const at::Tensor &x) { return cast_to_fp8(x, 128); });
+    m.def("silu_and_mul_per_token_cast_to_fp8", &silu_and_mul_per_token_cast_to_fp8, py::arg("x"), py::arg("masked_m") = py::none());
     m.def("abi_version", [] { return dga_abi_version(); });
 }

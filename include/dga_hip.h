@@ -445,6 +445,25 @@ int dga_cast_to_fp8_128x128_ld(const void *x, int x_dtype, int64_t rows, int64_t
 int dga_cast_to_fp8_1x128_ex(const void *x, int x_dtype, int64_t rows, int64_t k, void *q, int64_t ldq, float *sf, int flags, void *stream);
 int dga_cast_to_fp8_128x128_ex(const void *x, int x_dtype, int64_t rows, int64_t k, void *q, int64_t ldq, float *sf, int flags, void *stream);
 
+/* The activation of a MoE expert MLP fused into the 1x128 quantiser that feeds its second GEMM:
+ *   (q, sf) = cast_to_fp8_1x128( silu(x[..., :h]) * x[..., h:] ),   silu(g) = g / (1 + exp(-g)),
+ * x [groups, rows, 2h] contiguous (gate = the first h columns of a row, up = the last h: the silu_and_mul convention),
+ * x_dtype as above, q [groups, rows, h] e4m3fn bytes, sf [groups, rows, ceil(h/128)] fp32.  The product is formed in fp32 and never
+ * rounded to 16 bits; q and sf are what dga_cast_to_fp8_1x128_ex gives on that fp32 product (flags: DGA_CAST_UE8M0).  Accuracy of the
+ * product: for gate >= 20 it is fl32(gate * up) exactly (1 + exp(-g) rounds to 1), for |gate| <= 16 it is within relative 2^-18 of
+ * the real-number value (hardware base-2 exponential and a refined reciprocal, not the IEEE division), for gate <= -88.8 exp(-g)
+ * overflows and the product is +-0 (so for gate <= -120, where the real value is below the smallest fp32 subnormal per unit of up).
+ * Row masks, read on the device (a captured graph follows the routing); at most one may be given:
+ *   masked_m  int32[groups]  rows r >= masked_m[g] of group g are neither read nor written, in q and in sf alike (the layout of
+ *                            dga_m_grouped_gemm_fp8_fp8_bf16_nt_masked)
+ *   m_indices int32[rows]    groups = 1; rows with a negative index are neither read nor written (the tensor
+ *                            dga_m_grouped_gemm_fp8_fp8_bf16_nt_contiguous takes)
+ * DGA_E_RANGE: an unknown flag, or more 1x128 blocks than one grid holds (2^31 - 1 workgroups of 16 blocks);  DGA_E_SHAPE: a negative
+ * size, groups < 1, both masks, m_indices with groups != 1;  a zero size is DGA_OK with nothing done;  then DGA_E_NULL, DGA_E_DTYPE. */
+int dga_silu_mul_cast_to_fp8_1x128(const void *x, int x_dtype, int64_t groups, int64_t rows, int64_t h,
+                                   const int32_t *masked_m, const int32_t *m_indices,
+                                   void *q, float *sf, int flags, void *stream);
+
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
 /* struct Config in declaration order (get_best_config.hpp:12-31), 28 uint32. */
