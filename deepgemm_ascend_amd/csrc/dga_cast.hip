@@ -5,6 +5,7 @@
 // definition of record is the test oracle's quantiser (quant_1x128 / quant_128x128 in oracle/):
 //   amax = max |x| over the block (NaN ignored), scale = amax / 448 (1 if amax == 0),
 //   q = e4m3fn_rne_satfinite(x / scale)  with an IEEE fp32 division,
+//   a block with an infinite amax: scale +inf, finite x -> the zero of its sign, +-inf and NaN -> sign(x) | 0x7F,
 // and the results are byte-exact against it.  Both kernels are HBM streams (read 2 or 4 bytes, write 1 per element).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,14 +35,10 @@ __global__ void __launch_bounds__(256) cast_1x128_kernel(const void *x, uint8_t 
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (c0 + j < k) ? Elem<T>::load(x, base + j) : 0.f;
     }
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) amax = __builtin_fmaxf(amax, __builtin_fabsf(v[j]));
-    amax = row16_max(amax);
-    const float s = block_scale(amax, ue8m0);
-    if (sub == 0) sf[blk] = s;
+    float s;
     uint32_t w0, w1;
-    quant8(v, s, w0, w1);
+    quant_row_block(v, ue8m0, s, w0, w1);
+    if (sub == 0) sf[blk] = s;
     // (columns at and beyond k were read as 0 and quantise to the zero byte: they fill the row's tail up to ldq)
     const int64_t qbase = row * ldq + c0;
     if (vec_out && c0 + 8 <= ldq) {
@@ -74,14 +71,10 @@ __global__ void __launch_bounds__(256) cast_1x128_unrolled_kernel(const void *x,
     for (int j = 0; j < U; ++j) {
         if (!live[j]) continue;          // (uniform over the 16-lane group)
         const int64_t blk = blk0 + j * stride;
-        float amax = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) amax = __builtin_fmaxf(amax, __builtin_fabsf(v[j][e]));
-        amax = row16_max(amax);
-        const float s = block_scale(amax, ue8m0);
-        if (sub == 0) sf[blk] = s;
+        float s;
         uint32_t w0, w1;
-        quant8(v[j], s, w0, w1);
+        quant_row_block(v[j], ue8m0, s, w0, w1);
+        if (sub == 0) sf[blk] = s;
         *(v2i_c *)(q + blk * 128 + sub * 8) = v2i_c{(int)w0, (int)w1};
     }
 }
@@ -113,7 +106,7 @@ __global__ void __launch_bounds__(256) cast_128x128_kernel(const void *x, uint8_
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             v[g8 * 8 + j] = e[j];
-            amax = __builtin_fmaxf(amax, __builtin_fabsf(e[j]));
+            amax = __builtin_fmaxf(amax, abs_for_max(e[j]));
         }
     }
 #pragma unroll

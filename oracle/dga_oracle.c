@@ -244,6 +244,14 @@ DGA_ORACLE_API int dga_oracle_m_grouped_gemm_fp8_fp8_bf16_nt_masked(
 /* ---- quantiser used to make synthetic inputs (per-1x128 rows / per-128x128 blocks):
  *      scale = amax/448 (1.0 if amax==0), q = e4m3fn(x/scale).  Input-generation
  *      helper, not part of the GEMM definition. ---- */
+/* The block maximum ignores every NaN, signalling ones included: a comparison, not fmaxf (C's fmaxf returns NaN for a
+ * signalling NaN, and the scale of the block would follow it). */
+static float dga_oracle_amax_step(float amax, float x)
+{
+    const float ax = fabsf(x);
+    return ax > amax ? ax : amax;
+}
+
 /* ue8m0 != 0: the scale rounded UP to a power of two, 2^ceil(log2(amax / 448)) -- upstream DeepGEMM's use_ue8m0 quantisation
  * (ceil_to_ue8m0: 2^ceil(log2 x)); stated on the bits so that there is no libm in it: a scale with a non-zero mantissa moves to
  * the next exponent.  No reference counterpart (the reference has no quantiser at all). */
@@ -258,6 +266,20 @@ static float dga_oracle_block_scale(float amax, int ue8m0)
     return s;
 }
 
+/* One element of a block with scale s > 0.  Stated on the bits where the quotient would be the host's choice: a NaN input is
+ * sign(x) | 0x7F whatever the divide makes of its payload, and in a block whose amax is infinite (s = +inf, also under ue8m0:
+ * the mantissa of +inf is zero) every finite element is the zero of its own sign and every +-inf is sign(x) | 0x7F, the code
+ * of the NaN that inf / inf is, with the sign the divide would leave to the host.  Everything else is the IEEE quotient. */
+static uint8_t dga_oracle_quant_elem(float x, float s)
+{
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    const uint8_t sign = (uint8_t)((u >> 24) & 0x80);
+    if (isnan(x)) return sign | 0x7F;
+    if (isinf(s)) return isinf(x) ? (uint8_t)(sign | 0x7F) : sign;
+    return dga_oracle_f32_to_e4m3fn(x / s);
+}
+
 DGA_ORACLE_API void dga_oracle_quant_1x128_ex(const float *x, uint8_t *q, float *sf, int64_t rows, int64_t k, int ue8m0)
 {
     const int64_t kb_n = (k + 127) / 128;
@@ -265,10 +287,10 @@ DGA_ORACLE_API void dga_oracle_quant_1x128_ex(const float *x, uint8_t *q, float 
         for (int64_t kb = 0; kb < kb_n; ++kb) {
             const int64_t k0 = kb * 128, k1 = (k0 + 128 < k) ? k0 + 128 : k;
             float amax = 0.0f;
-            for (int64_t p = k0; p < k1; ++p) amax = fmaxf(amax, fabsf(x[i * k + p]));
+            for (int64_t p = k0; p < k1; ++p) amax = dga_oracle_amax_step(amax, x[i * k + p]);
             const float s = dga_oracle_block_scale(amax, ue8m0);
             sf[i * kb_n + kb] = s;
-            for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_f32_to_e4m3fn(x[i * k + p] / s);
+            for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_quant_elem(x[i * k + p], s);
         }
     }
 }
@@ -282,11 +304,11 @@ DGA_ORACLE_API void dga_oracle_quant_128x128_ex(const float *x, uint8_t *q, floa
             const int64_t k0 = kb * 128, k1 = (k0 + 128 < k) ? k0 + 128 : k;
             float amax = 0.0f;
             for (int64_t i = r0; i < r1; ++i)
-                for (int64_t p = k0; p < k1; ++p) amax = fmaxf(amax, fabsf(x[i * k + p]));
+                for (int64_t p = k0; p < k1; ++p) amax = dga_oracle_amax_step(amax, x[i * k + p]);
             const float s = dga_oracle_block_scale(amax, ue8m0);
             sf[rb * kb_n + kb] = s;
             for (int64_t i = r0; i < r1; ++i)
-                for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_f32_to_e4m3fn(x[i * k + p] / s);
+                for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_quant_elem(x[i * k + p], s);
         }
     }
 }
@@ -298,10 +320,10 @@ DGA_ORACLE_API void dga_oracle_quant_1x128(const float *x, uint8_t *q, float *sf
         for (int64_t kb = 0; kb < kb_n; ++kb) {
             const int64_t k0 = kb * 128, k1 = (k0 + 128 < k) ? k0 + 128 : k;
             float amax = 0.0f;
-            for (int64_t p = k0; p < k1; ++p) amax = fmaxf(amax, fabsf(x[i * k + p]));
+            for (int64_t p = k0; p < k1; ++p) amax = dga_oracle_amax_step(amax, x[i * k + p]);
             const float s = amax > 0.0f ? amax / 448.0f : 1.0f;
             sf[i * kb_n + kb] = s;
-            for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_f32_to_e4m3fn(x[i * k + p] / s);
+            for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_quant_elem(x[i * k + p], s);
         }
     }
 }
@@ -315,11 +337,11 @@ DGA_ORACLE_API void dga_oracle_quant_128x128(const float *x, uint8_t *q, float *
             const int64_t k0 = kb * 128, k1 = (k0 + 128 < k) ? k0 + 128 : k;
             float amax = 0.0f;
             for (int64_t i = r0; i < r1; ++i)
-                for (int64_t p = k0; p < k1; ++p) amax = fmaxf(amax, fabsf(x[i * k + p]));
+                for (int64_t p = k0; p < k1; ++p) amax = dga_oracle_amax_step(amax, x[i * k + p]);
             const float s = amax > 0.0f ? amax / 448.0f : 1.0f;
             sf[rb * kb_n + kb] = s;
             for (int64_t i = r0; i < r1; ++i)
-                for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_f32_to_e4m3fn(x[i * k + p] / s);
+                for (int64_t p = k0; p < k1; ++p) q[i * k + p] = dga_oracle_quant_elem(x[i * k + p], s);
         }
     }
 }

@@ -37,8 +37,9 @@ def test_per_block_cast(dga, oracle, dtype, rows, k):
 
 
 def test_cast_edge_values(dga, oracle):
-    """Zeros, an all-zero block (scale 1), subnormal results, ties, huge dynamic range, NaN, tiny amax."""
-    x = np.zeros((8, 256), np.float32)
+    """Zeros, an all-zero block (scale 1), subnormal results, ties, huge dynamic range, NaN, tiny amax; +-inf: a block with an
+    infinite maximum has scale +inf, its finite elements are the zero of their sign, its +-inf and NaN are sign | 0x7F."""
+    x = np.zeros((9, 256), np.float32)
     x[0, :128] = np.linspace(-1, 1, 128)           # ordinary
     x[1, 0] = 448.0; x[1, 1:9] = [2.0 ** -9, 2.0 ** -10, 3 * 2.0 ** -10, 1e-3, -1e-3, 2.0 ** -6, 17.0, 19.0]
     x[2, :128] = 0.0                               # all-zero block -> scale 1, codes 0
@@ -48,11 +49,21 @@ def test_cast_edge_values(dga, oracle):
     x[5, :128] = np.arange(128) * 0.0625           # many exact ties after scaling
     x[6, 5] = np.nan; x[6, 6] = -np.nan; x[6, 7] = 1.0
     x[7, 128:] = np.float32(1e-45)                 # denormal inputs
+    x[8, :10] = [np.inf, -np.inf, 1.0, -1.0, 0.0, -0.0, 3e38, -1e-45, np.nan, -np.nan]
+    x[8, 128] = -np.inf; x[8, 129:133] = [5.0, -5.0, np.inf, -np.nan]      # -inf alone makes the maximum infinite too
     xt = torch.from_numpy(x).cuda()
     _check(dga, oracle, xt, dga.per_token_cast_to_fp8, oracle.quant_1x128)
-    big = np.zeros((128, 128), np.float32); big[:8, :] = x[:, :128]
+    q, sf = dga.per_token_cast_to_fp8(xt)
+    assert q.view(torch.uint8)[8, :10].tolist() == [0x7F, 0xFF, 0, 0x80, 0, 0x80, 0, 0x80, 0x7F, 0xFF]
+    assert q.view(torch.uint8)[8, 128:134].tolist() == [0xFF, 0, 0x80, 0x7F, 0xFF, 0] and sf[8].tolist() == [np.inf, np.inf]
+    big = np.zeros((128, 128), np.float32); big[:8, :] = x[:8, :128]
     big[6] = 0.0                                   # (NaN covered per token; the block amax ignores it the same way)
     _check(dga, oracle, torch.from_numpy(big).cuda(), dga.per_block_cast_to_fp8, oracle.quant_128x128)
+    big[101, 64:] = x[8, :64]; big[6] = x[6, :128]  # the whole tile under the rule, NaN rows included
+    for ue8m0 in (False, True):
+        _check(dga, oracle, torch.from_numpy(big).cuda(), lambda t: dga.per_block_cast_to_fp8(t, use_ue8m0=ue8m0),
+               lambda a: oracle.quant_128x128(a, ue8m0=ue8m0))
+        _check(dga, oracle, xt, lambda t: dga.per_token_cast_to_fp8(t, use_ue8m0=ue8m0), lambda a: oracle.quant_1x128(a, ue8m0=ue8m0))
 
 
 def test_cast_feeds_the_gemm(dga, oracle):
