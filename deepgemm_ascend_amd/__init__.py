@@ -46,6 +46,7 @@ from .api import (  # noqa: F401
     select_kernel_with_predictor,
     select_tiling_strategy,
     silu_and_mul_per_token_cast_to_fp8,
+    silu_and_mul_backward_per_token_cast_to_fp8,
     platform_mi355x,
     run_mmad_bench,
     run_mmad_custom,

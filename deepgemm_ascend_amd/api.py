@@ -1018,6 +1018,66 @@ def silu_and_mul_per_token_cast_to_fp8(x: torch.Tensor, masked_m: Optional[torch
     return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
 
 
+def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
+                                                m_indices: Optional[torch.Tensor] = None,
+                                                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                                                grad_x_out: Optional[torch.Tensor] = None, use_ue8m0: bool = False,
+                                                sync: bool = False):
+    """The backward of silu_and_mul_per_token_cast_to_fp8's activation fused into the quantiser of the dgrad of the first GEMM
+    (dga_silu_mul_bwd_cast_to_fp8_1x128): with gate = x[..., :H], up = x[..., H:] and s = sigmoid(gate),
+      dgate = grad_h * up * (s + gate s (1 - s)),   dup = grad_h * gate s,   (dq, dsf) = per_token_cast_to_fp8([dgate | dup])
+    with both gradients kept in fp32.  x [..., 2H] (the tensor the forward read) and grad_h [..., H] share dtype (float32 / bfloat16 /
+    float16) and leading dimensions, both contiguous -> dq [..., 2H] float8_e4m3fn, dsf [..., 2H/128] float32: the lhs of
+    gemm_fp8_fp8_bf16_nt and the grouped entries with K = 2H.  H % 128 == 0 is required (no 1x128 block straddles the two halves).
+    Row layouts, masks (read on the device), out=(dq, dsf), use_ue8m0 and sync: as silu_and_mul_per_token_cast_to_fp8; a row a mask
+    excludes is neither read nor written, in any output.  grad_x_out: a contiguous [..., 2H] tensor of x's dtype that receives the
+    unquantised gradient in the same pass (fp32 rounded to nearest even for the 16-bit types) on the valid rows -- what a caller
+    transposes and quantises into the operand of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  For gate >= 20 the result is the quantiser's
+    on [fl32(grad_h * up) | fl32(grad_h * gate)] bit for bit; for |gate| <= 16 dup is within relative 2^-18 and dgate within
+    2^-17 |grad_h up| (s + |gate| s (1 - s)) of the real-number value."""
+    _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
+    want_dim = 3 if masked_m is not None else 2
+    _require(x.dim() == want_dim and x.is_contiguous(),
+             "x must be a contiguous [G, Mmax, 2H] tensor with masked_m" if masked_m is not None else "x must be a contiguous [rows, 2H] tensor")
+    _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
+    _require(x.shape[-1] % 256 == 0, "the last dimension of x must be 2H with H a multiple of 128 (gate and up halves of whole 1x128 blocks)")
+    h = x.shape[-1] // 2
+    lead = tuple(x.shape[:-1])
+    _require(tuple(grad_h.shape) == lead + (h,) and grad_h.is_contiguous(), f"grad_h must be contiguous {list(lead + (h,))}")
+    _require(grad_h.dtype == x.dtype, "grad_h must have x's dtype")
+    groups, rows = (lead if masked_m is not None else (1, lead[0]))
+    if masked_m is not None:
+        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
+                 f"masked_m must be a contiguous int32 [{groups}]")
+    if m_indices is not None:
+        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
+                 f"m_indices must be a contiguous int32 [{rows}]")
+    hb = 2 * h // 128
+    if out is None:
+        q = torch.empty(lead + (2 * h,), dtype=torch.uint8, device=x.device)
+        sf = torch.empty(lead + (hb,), dtype=torch.float32, device=x.device)
+    else:
+        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be (dq, dsf)")
+        q, sf = out
+        _fp8_bytes(q)
+        _require(tuple(q.shape) == lead + (2 * h,) and q.is_contiguous(), f"out dq must be contiguous {list(lead + (2 * h,))}")
+        _require(sf.dtype == torch.float32 and tuple(sf.shape) == lead + (hb,) and sf.is_contiguous(),
+                 f"out dsf must be contiguous float32 {list(lead + (hb,))}")
+    if grad_x_out is not None:
+        _require(tuple(grad_x_out.shape) == tuple(x.shape) and grad_x_out.is_contiguous(), f"grad_x_out must be contiguous {list(x.shape)}")
+        _require(grad_x_out.dtype == x.dtype, "grad_x_out must have x's dtype")
+    with _device_guard(x, grad_h, q, sf, *(t for t in (masked_m, m_indices, grad_x_out) if t is not None)):
+        rc = _lib.lib().dga_silu_mul_bwd_cast_to_fp8_1x128(
+            x.data_ptr(), grad_h.data_ptr(), _CAST_DT[x.dtype], groups, rows, h,
+            masked_m.data_ptr() if masked_m is not None else None, m_indices.data_ptr() if m_indices is not None else None,
+            q.data_ptr(), sf.data_ptr(), grad_x_out.data_ptr() if grad_x_out is not None else None,
+            _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
+        _lib.check(rc, "silu_and_mul_backward_per_token_cast_to_fp8")
+        if sync:
+            torch.cuda.current_stream(x.device).synchronize()
+    return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

@@ -464,6 +464,25 @@ int dga_silu_mul_cast_to_fp8_1x128(const void *x, int x_dtype, int64_t groups, i
                                    const int32_t *masked_m, const int32_t *m_indices,
                                    void *q, float *sf, int flags, void *stream);
 
+/* Its backward, fused into the 1x128 quantiser that feeds the dgrad of the first GEMM (K = 2h):
+ *   dgate = grad_h * up * silu'(gate),   dup = grad_h * silu(gate),   silu'(g) = s + g s (1 - s),  s = 1 / (1 + exp(-g)),
+ *   (dq, dsf) = cast_to_fp8_1x128( [dgate | dup] ),
+ * x [groups, rows, 2h] as above (the tensor the forward read), grad_h [groups, rows, h], both contiguous and of `dtype`;
+ * dq [groups, rows, 2h] e4m3fn bytes (dgate in the first h columns of a row, dup in the last h), dsf [groups, rows, 2h/128] fp32.
+ * h % 128 == 0 is required: no 1x128 block of the [2h] axis straddles the two halves.  grad_x (may be NULL): [groups, rows, 2h] of
+ * `dtype`, receives the unquantised fp32 gradient in the same pass (rounded to nearest even for the 16-bit types), on the rows that
+ * are written; what a caller transposes into the operand of dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  Both gradients are formed in
+ * fp32 and never rounded to 16 bits before they are quantised; dq and dsf are what dga_cast_to_fp8_1x128_ex gives on them (flags:
+ * DGA_CAST_UE8M0).  Accuracy: for gate >= 20 dgate = fl32(grad_h * up) and dup = fl32(grad_h * gate) exactly; for |gate| <= 16 dup is
+ * within relative 2^-18 and dgate within 2^-17 |grad_h up| (s + |g| s (1 - s)) of the real-number value (silu' has a root at
+ * g = -1.2785: no relative bound there); for gate <= -88.8 both are +-0.  A NaN in gate or grad_h gives NaN codes in both halves, a
+ * NaN in up in dgate alone.  masked_m, m_indices: as above; a row a mask excludes is neither read nor written, in dq, dsf and grad_x.
+ * DGA_E_RANGE: an unknown flag, or more blocks than one grid holds;  DGA_E_SHAPE: a negative size, h % 128 != 0, groups < 1, both
+ * masks, m_indices with groups != 1;  a zero size is DGA_OK with nothing done;  then DGA_E_NULL (x, grad_h, dq, dsf), DGA_E_DTYPE. */
+int dga_silu_mul_bwd_cast_to_fp8_1x128(const void *x, const void *grad_h, int dtype, int64_t groups, int64_t rows, int64_t h,
+                                       const int32_t *masked_m, const int32_t *m_indices,
+                                       void *dq, float *dsf, void *grad_x, int flags, void *stream);
+
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
 /* struct Config in declaration order (get_best_config.hpp:12-31), 28 uint32. */
