@@ -967,6 +967,44 @@ def per_block_cast_to_fp8(x: torch.Tensor, aligned_rows: bool = False, use_ue8m0
     return _cast("dga_cast_to_fp8_128x128", x, 128, aligned_rows, use_ue8m0)
 
 
+_FUSED_LAST_DIM = {2: "the last dimension of x must be even (gate and up halves)",
+                   256: "the last dimension of x must be 2H with H a multiple of 128 (gate and up halves of whole 1x128 blocks)"}
+
+
+def _fused_layout(x: torch.Tensor, masked_m: Optional[torch.Tensor], m_indices: Optional[torch.Tensor], multiple: int):
+    """The row layouts of the fused quantisers, checked: x [rows, 2H], or [G, Mmax, 2H] with masked_m int32 [G], or [rows, 2H] with m_indices
+    int32 [rows]; the last dimension a multiple of `multiple`.  Returns (H, the leading dimensions, groups, rows per group)."""
+    _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
+    want_dim = 3 if masked_m is not None else 2
+    _require(x.dim() == want_dim and x.is_contiguous(),
+             "x must be a contiguous [G, Mmax, 2H] tensor with masked_m" if masked_m is not None else "x must be a contiguous [rows, 2H] tensor")
+    _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
+    _require(x.shape[-1] % multiple == 0, _FUSED_LAST_DIM[multiple])
+    lead = tuple(x.shape[:-1])
+    groups, rows = (lead if masked_m is not None else (1, lead[0]))
+    if masked_m is not None:
+        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
+                 f"masked_m must be a contiguous int32 [{groups}]")
+    if m_indices is not None:
+        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
+                 f"m_indices must be a contiguous int32 [{rows}]")
+    return x.shape[-1] // 2, lead, groups, rows
+
+
+def _fused_out(out, lead: tuple, width: int, blocks: int, device, q_name: str, sf_name: str):
+    """(q [lead, width] bytes, sf [lead, blocks] float32) of a fused quantiser: torch.empty, or the caller's out=(q, sf) checked."""
+    if out is None:
+        return (torch.empty(lead + (width,), dtype=torch.uint8, device=device),
+                torch.empty(lead + (blocks,), dtype=torch.float32, device=device))
+    _require(isinstance(out, (tuple, list)) and len(out) == 2, f"out must be ({q_name}, {sf_name})")
+    q, sf = out
+    _fp8_bytes(q)
+    _require(tuple(q.shape) == lead + (width,) and q.is_contiguous(), f"out {q_name} must be contiguous {list(lead + (width,))}")
+    _require(sf.dtype == torch.float32 and tuple(sf.shape) == lead + (blocks,) and sf.is_contiguous(),
+             f"out {sf_name} must be contiguous float32 {list(lead + (blocks,))}")
+    return q, sf
+
+
 def silu_and_mul_per_token_cast_to_fp8(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
                                        m_indices: Optional[torch.Tensor] = None,
                                        out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, use_ue8m0: bool = False,
@@ -981,32 +1019,8 @@ def silu_and_mul_per_token_cast_to_fp8(x: torch.Tensor, masked_m: Optional[torch
     or float8_e4m3fn); without it both are torch.empty, so the rows a mask excludes are UNINITIALISED -- pass out to give them
     a value.  For gate >= 20 the result is the quantiser's on fl32(gate * up) bit for bit, for |gate| <= 16 the fp32 product is
     within relative 2^-18 of the real-number value; use_ue8m0 as in per_token_cast_to_fp8."""
-    _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
-    want_dim = 3 if masked_m is not None else 2
-    _require(x.dim() == want_dim and x.is_contiguous(),
-             "x must be a contiguous [G, Mmax, 2H] tensor with masked_m" if masked_m is not None else "x must be a contiguous [rows, 2H] tensor")
-    _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
-    _require(x.shape[-1] % 2 == 0, "the last dimension of x must be even (gate and up halves)")
-    h = x.shape[-1] // 2
-    lead = tuple(x.shape[:-1])
-    groups, rows = (lead if masked_m is not None else (1, lead[0]))
-    if masked_m is not None:
-        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
-                 f"masked_m must be a contiguous int32 [{groups}]")
-    if m_indices is not None:
-        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
-                 f"m_indices must be a contiguous int32 [{rows}]")
-    hb = (h + 127) // 128
-    if out is None:
-        q = torch.empty(lead + (h,), dtype=torch.uint8, device=x.device)
-        sf = torch.empty(lead + (hb,), dtype=torch.float32, device=x.device)
-    else:
-        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be (q, sf)")
-        q, sf = out
-        _fp8_bytes(q)
-        _require(tuple(q.shape) == lead + (h,) and q.is_contiguous(), f"out q must be contiguous {list(lead + (h,))}")
-        _require(sf.dtype == torch.float32 and tuple(sf.shape) == lead + (hb,) and sf.is_contiguous(),
-                 f"out sf must be contiguous float32 {list(lead + (hb,))}")
+    h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 2)
+    q, sf = _fused_out(out, lead, h, (h + 127) // 128, x.device, "q", "sf")
     with _device_guard(x, q, sf, *(t for t in (masked_m, m_indices) if t is not None)):
         rc = _lib.lib().dga_silu_mul_cast_to_fp8_1x128(
             x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
@@ -1035,34 +1049,10 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
     transposes and quantises into the operand of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  For gate >= 20 the result is the quantiser's
     on [fl32(grad_h * up) | fl32(grad_h * gate)] bit for bit; for |gate| <= 16 dup is within relative 2^-18 and dgate within
     2^-17 |grad_h up| (s + |gate| s (1 - s)) of the real-number value."""
-    _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
-    want_dim = 3 if masked_m is not None else 2
-    _require(x.dim() == want_dim and x.is_contiguous(),
-             "x must be a contiguous [G, Mmax, 2H] tensor with masked_m" if masked_m is not None else "x must be a contiguous [rows, 2H] tensor")
-    _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
-    _require(x.shape[-1] % 256 == 0, "the last dimension of x must be 2H with H a multiple of 128 (gate and up halves of whole 1x128 blocks)")
-    h = x.shape[-1] // 2
-    lead = tuple(x.shape[:-1])
+    h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 256)
     _require(tuple(grad_h.shape) == lead + (h,) and grad_h.is_contiguous(), f"grad_h must be contiguous {list(lead + (h,))}")
     _require(grad_h.dtype == x.dtype, "grad_h must have x's dtype")
-    groups, rows = (lead if masked_m is not None else (1, lead[0]))
-    if masked_m is not None:
-        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
-                 f"masked_m must be a contiguous int32 [{groups}]")
-    if m_indices is not None:
-        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
-                 f"m_indices must be a contiguous int32 [{rows}]")
-    hb = 2 * h // 128
-    if out is None:
-        q = torch.empty(lead + (2 * h,), dtype=torch.uint8, device=x.device)
-        sf = torch.empty(lead + (hb,), dtype=torch.float32, device=x.device)
-    else:
-        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be (dq, dsf)")
-        q, sf = out
-        _fp8_bytes(q)
-        _require(tuple(q.shape) == lead + (2 * h,) and q.is_contiguous(), f"out dq must be contiguous {list(lead + (2 * h,))}")
-        _require(sf.dtype == torch.float32 and tuple(sf.shape) == lead + (hb,) and sf.is_contiguous(),
-                 f"out dsf must be contiguous float32 {list(lead + (hb,))}")
+    q, sf = _fused_out(out, lead, 2 * h, 2 * h // 128, x.device, "dq", "dsf")
     if grad_x_out is not None:
         _require(tuple(grad_x_out.shape) == tuple(x.shape) and grad_x_out.is_contiguous(), f"grad_x_out must be contiguous {list(x.shape)}")
         _require(grad_x_out.dtype == x.dtype, "grad_x_out must have x's dtype")

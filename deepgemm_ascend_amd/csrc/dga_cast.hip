@@ -29,25 +29,13 @@ __global__ void __launch_bounds__(256) cast_1x128_kernel(const void *x, uint8_t 
     const int64_t row = blk / kb_n, kb = blk - row * kb_n;
     const int64_t c0 = kb * 128 + sub * 8, base = row * k + c0;
     float v[8];
-    if (vec_in && c0 + 8 <= k) {
-        Elem<T>::load8(x, base, v);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (c0 + j < k) ? Elem<T>::load(x, base + j) : 0.f;
-    }
+    load8_bounded<T>(x, base, v, vec_in, c0, k);
     float s;
     uint32_t w0, w1;
     quant_row_block(v, ue8m0, s, w0, w1);
     if (sub == 0) sf[blk] = s;
     // (columns at and beyond k were read as 0 and quantise to the zero byte: they fill the row's tail up to ldq)
-    const int64_t qbase = row * ldq + c0;
-    if (vec_out && c0 + 8 <= ldq) {
-        *(v2i_c *)(q + qbase) = v2i_c{(int)w0, (int)w1};
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (c0 + j < ldq) q[qbase + j] = (uint8_t)(((j < 4 ? w0 : w1) >> (8 * (j & 3))) & 0xFF);
-    }
+    store_codes8(q + row * ldq + c0, w0, w1, vec_out, c0, ldq);
 }
 
 // The same, U blocks per 16-lane group with all U loads issued before the first is used: U x 16 (32) bytes in flight per lane
@@ -96,13 +84,8 @@ __global__ void __launch_bounds__(256) cast_128x128_kernel(const void *x, uint8_
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) {
         float e[8];
-        const int64_t c = c0 + g8 * 8, base = row * k + c;
-        if (row_ok && vec_in && c + 8 <= k) {
-            Elem<T>::load8(x, base, e);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) e[j] = (row_ok && c + j < k) ? Elem<T>::load(x, base + j) : 0.f;
-        }
+        const int64_t c = c0 + g8 * 8;
+        load8_bounded<T>(x, row * k + c, e, vec_in, c, k, row_ok);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             v[g8 * 8 + j] = e[j];
@@ -119,20 +102,13 @@ __global__ void __launch_bounds__(256) cast_128x128_kernel(const void *x, uint8_
     if (!row_ok) return;
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) {
-        const int64_t c = c0 + g8 * 8, base = row * k + c;
+        const int64_t c = c0 + g8 * 8;
         float e[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) e[j] = v[g8 * 8 + j];
         uint32_t w0, w1;
         quant8(e, s, w0, w1);
-        const int64_t qbase = row * ldq + c;
-        if (vec_out && c + 8 <= ldq) {
-            *(v2i_c *)(q + qbase) = v2i_c{(int)w0, (int)w1};
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (c + j < ldq) q[qbase + j] = (uint8_t)(((j < 4 ? w0 : w1) >> (8 * (j & 3))) & 0xFF);
-        }
+        store_codes8(q + row * ldq + c, w0, w1, vec_out, c, ldq);
     }
 }
 
@@ -150,21 +126,20 @@ static int launch_cast(int mode, const void *x, void *q, float *sf, int64_t rows
     if (mode == 0 && vec_in && vec_out && k % 128 == 0 && ldq == k && two) {
         const int64_t blocks = rows * kb_n;
         const int64_t stride = (blocks + 1) / 2;
-        const int64_t grid = (stride * 16 + 255) / 256;
-        if (grid > 0x7FFFFFFFll) return DGA_E_RANGE;
+        unsigned grid;
+        if (int rc = grid_of_blocks(stride, 1, grid)) return rc;
         if (unroll >= 4)
             hipLaunchKernelGGL((cast_1x128_unrolled_kernel<T, 4>), dim3(static_cast<unsigned>(((blocks + 3) / 4 * 16 + 255) / 256)), dim3(256), 0,
                                stream, x, static_cast<uint8_t *>(q), sf, blocks, (blocks + 3) / 4, ue8m0);
         else
-            hipLaunchKernelGGL((cast_1x128_unrolled_kernel<T, 2>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream, x,
+            hipLaunchKernelGGL((cast_1x128_unrolled_kernel<T, 2>), dim3(grid), dim3(256), 0, stream, x,
                                static_cast<uint8_t *>(q), sf, blocks, stride, ue8m0);
         return record_hip(hipGetLastError());
     }
     if (mode == 0) {
-        const int64_t blocks = rows * kb_n;
-        const int64_t grid = (blocks * 16 + 255) / 256;
-        if (grid > 0x7FFFFFFFll) return DGA_E_RANGE;
-        hipLaunchKernelGGL(cast_1x128_kernel<T>, dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream, x,
+        unsigned grid;
+        if (int rc = grid_of_blocks(rows, kb_n, grid)) return rc;
+        hipLaunchKernelGGL(cast_1x128_kernel<T>, dim3(grid), dim3(256), 0, stream, x,
                            static_cast<uint8_t *>(q), sf, rows, k, kb_n, vec_in, vec_out, ldq, ue8m0);
     } else {
         const int64_t grid = ((rows + 127) / 128) * kb_n;
@@ -182,13 +157,9 @@ static int run_cast(int mode, const void *x, int x_dtype, int64_t rows, int64_t 
     if (rows < 0 || k < 0 || ldq < k || ldq > (k + 127) / 128 * 128) return DGA_E_SHAPE;
     if (rows == 0 || k == 0) return DGA_OK;
     if (!x || !q || !sf) return DGA_E_NULL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (x_dtype) {
-        case DGA_DT_FP32: return launch_cast<float>(mode, x, q, sf, rows, k, ldq, ue8m0, st);
-        case DGA_DT_BF16: return launch_cast<Bf16Tag>(mode, x, q, sf, rows, k, ldq, ue8m0, st);
-        case DGA_DT_FP16: return launch_cast<F16Tag>(mode, x, q, sf, rows, k, ldq, ue8m0, st);
-        default: return DGA_E_DTYPE;
-    }
+    return dispatch_dtype(x_dtype, [&](auto tag) {
+        return launch_cast<decltype(tag)>(mode, x, q, sf, rows, k, ldq, ue8m0, static_cast<hipStream_t>(stream));
+    });
 }
 
 }  // namespace dga

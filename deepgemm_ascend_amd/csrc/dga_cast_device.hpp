@@ -1,9 +1,12 @@
-// Device helpers shared by the fp8 quantisers (dga_cast.hip, dga_silu_mul_cast.hip): the e4m3fn conversion, the 16-lane
-// DPP row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition (oracle/:
-// quant_1x128), and the 8-element loads of the three input types.  One text, so that every quantiser gives the same bytes.
+// What the fp8 quantisers share (dga_cast.hip, dga_silu_mul_cast.hip, dga_silu_mul_bwd_cast.hip).  Device: the e4m3fn conversion, the 16-lane DPP
+// row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition (oracle/: quant_1x128); the bounded 8-element
+// loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels' row locator and refined sigmoid.  Host, at
+// the end: the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "dga_hip.h"
 
 namespace dga {
 
@@ -155,5 +158,166 @@ template <> struct Elem<F16Tag> {
         for (int j = 0; j < 8; ++j) v[j] = (float)w[j];
     }
 };
+
+// The lane's 8 elements, columns c0 .. c0 + 7 of a row of n columns, from element index `base` of p.  One 16-byte (fp32: two) load when the
+// caller vouches for the alignment (vec) and all 8 are inside the row, else element by element with zeros at and beyond n.  row_ok = false
+// (the 128x128 kernel's rows past the last): nothing is read, all 8 are zero.
+template <typename T>
+__device__ __forceinline__ void load8_bounded(const void *p, int64_t base, float (&v)[8], bool vec, int64_t c0, int64_t n, bool row_ok = true)
+{
+    if (row_ok && vec && c0 + 8 <= n) {
+        Elem<T>::load8(p, base, v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (row_ok && c0 + j < n) ? Elem<T>::load(p, base + j) : 0.f;
+    }
+}
+
+// The store counterpart of Elem<T>::load8: 8 fp32 values -> 8 elements of T at element index i, round to nearest even for the 16-bit types
+// (v_cvt_pk_bf16_f32, v_cvt_f16_f32), as they are for fp32.  vec: 16-byte stores.
+template <typename T> struct Store8;
+template <> struct Store8<float> {
+    static __device__ __forceinline__ void run(void *p, int64_t i, const float (&v)[8], bool vec)
+    {
+        float *o = (float *)p + i;
+        if (vec) {
+            *(v4f_c *)o = v4f_c{v[0], v[1], v[2], v[3]};
+            *(v4f_c *)(o + 4) = v4f_c{v[4], v[5], v[6], v[7]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = v[j];
+        }
+    }
+};
+template <> struct Store8<Bf16Tag> {
+    static __device__ __forceinline__ void run(void *p, int64_t i, const float (&v)[8], bool vec)
+    {
+        typedef float v2f __attribute__((ext_vector_type(2)));
+        typedef __bf16 v2b __attribute__((ext_vector_type(2)));
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector((v2f{v[2 * j], v[2 * j + 1]}), v2b));
+        uint16_t *o = (uint16_t *)p + i;
+        if (vec) {
+            *(v4i_c *)o = v4i_c{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+        }
+    }
+};
+template <> struct Store8<F16Tag> {
+    static __device__ __forceinline__ void run(void *p, int64_t i, const float (&v)[8], bool vec)
+    {
+        typedef _Float16 v8h __attribute__((ext_vector_type(8)));
+        _Float16 *o = (_Float16 *)p + i;
+        if (vec) {
+            *(v8h *)o = v8h{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
+                            (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = (_Float16)v[j];
+        }
+    }
+};
+
+// The lane's 8 codes (w0: the first four, w1: the rest) to q, the place of columns c0 .. c0 + 7 of a row of n columns.  One 8-byte store when
+// the caller vouches for the alignment (vec) and all 8 are inside the row, else byte by byte below n.  (c0, n) = (0, 8): all 8 are inside.
+__device__ __forceinline__ void store_codes8(uint8_t *q, uint32_t w0, uint32_t w1, bool vec, int64_t c0, int64_t n)
+{
+    if (vec && c0 + 8 <= n) {
+        *(v2i_c *)q = v2i_c{(int)w0, (int)w1};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (c0 + j < n) q[j] = (uint8_t)(((j < 4 ? w0 : w1) >> (8 * (j & 3))) & 0xFF);
+    }
+}
+
+// a / b for 0 <= a, 0 < b: the 32-bit division when both fit (a quarter of the instructions of the 64-bit one)
+__device__ __forceinline__ int64_t udiv(int64_t a, int64_t b, bool small)
+{
+    return small ? (int64_t)((uint32_t)a / (uint32_t)b) : a / b;
+}
+
+// The fused kernels' geometry: 16-lane block blk of rows of hb_n column blocks -> its row (counted over all groups of mmax rows) and column
+// block b.  False: the mask excludes the row (masked_m: row r of group g with r >= masked_m[g]; m_indices: a negative index), and the caller
+// returns before it reads anything.  The answer is the row's, so the 16 lanes of a block get the same one and leave together.
+__device__ __forceinline__ bool locate_row(int64_t blk, int64_t hb_n, int64_t mmax, const int32_t *masked_m, const int32_t *m_indices,
+                                           bool small, int64_t &row, int64_t &b)
+{
+    row = udiv(blk, hb_n, small);
+    b = blk - row * hb_n;
+    if (masked_m) {
+        const int64_t g = udiv(row, mmax, small);
+        return row - g * mmax < masked_m[g];
+    }
+    return !m_indices || m_indices[row] >= 0;
+}
+
+// s = 1 / (1 + e), e = exp(-g) = 2^(g * -log2 e): hardware exponential, hardware reciprocal, one Newton step.  With e = inf the reciprocal
+// is 0 and the Newton residual -inf * 0 + 1 is NaN: v_max_f32 drops the NaN (any ordinary residual is far above -1), and the step then
+// returns the 0.  A NaN g still comes out NaN (r0 is NaN, and so is -1 * r0 + r0).
+constexpr float kNegLog2E = -1.4426950408889634f;
+__device__ __forceinline__ float exp_neg(float g) { return __builtin_amdgcn_exp2f(g * kNegLog2E); }
+__device__ __forceinline__ float sigmoid_refined(float g, float &e)
+{
+    e = exp_neg(g);
+    const float d = 1.f + e;
+    const float r0 = __builtin_amdgcn_rcpf(d);
+    return __builtin_fmaf(__builtin_fmaxf(__builtin_fmaf(-d, r0, 1.f), -1.f), r0, r0);
+}
+
+// ---- host side: what the three units' launchers share
+
+// dtype (DGA_DT_*) -> f(tag), tag an object of the type the kernels are instantiated on (float / Bf16Tag / F16Tag); DGA_E_DTYPE for any other
+template <typename F> inline int dispatch_dtype(int dtype, F &&f)
+{
+    switch (dtype) {
+        case DGA_DT_FP32: return f(float{});
+        case DGA_DT_BF16: return f(Bf16Tag{});
+        case DGA_DT_FP16: return f(F16Tag{});
+        default: return DGA_E_DTYPE;
+    }
+}
+
+// rows * per_row 16-lane blocks -> the grid of 256-thread workgroups (16 blocks each); DGA_E_RANGE beyond 2^31 - 1 workgroups, decided
+// without the product: rows * per_row is inside int64 whenever this returns DGA_OK.  per_row > 0.
+inline int grid_of_blocks(int64_t rows, int64_t per_row, unsigned &grid)
+{
+    if (rows > 0x7FFFFFFFll * 16 / per_row) return DGA_E_RANGE;
+    grid = static_cast<unsigned>((rows * per_row + 15) / 16);
+    return DGA_OK;
+}
+
+// What a fused kernel is launched with besides its pointers: rows_total * hb_n blocks of 16 lanes, hb_n = ceil(h / 128)
+struct FusedGeometry {
+    int64_t blocks, hb_n;
+    unsigned grid;
+    bool small;   // blocks and mmax fit 32 bits (udiv)
+    bool ue8m0;
+};
+
+// The body of a fused entry point.  The checks in run_cast's order -- flags, shape (h a multiple of h_multiple), nothing to do, pointers
+// (have_ptrs: none of the required ones is null), dtype, groups * rows and the grid -- then launch(tag, geometry).
+template <typename L>
+inline int run_fused(int flags, int dtype, int64_t groups, int64_t rows, int64_t h, int64_t h_multiple, const int32_t *masked_m,
+                     const int32_t *m_indices, bool have_ptrs, L &&launch)
+{
+    if (flags & ~DGA_CAST_UE8M0) return DGA_E_RANGE;
+    if (groups < 1 || rows < 0 || h < 0 || h % h_multiple != 0 || (masked_m && m_indices) || (m_indices && groups != 1)) return DGA_E_SHAPE;
+    if (rows == 0 || h == 0) return DGA_OK;
+    if (!have_ptrs) return DGA_E_NULL;
+    return dispatch_dtype(dtype, [&](auto tag) -> int {
+        if (groups > 0x7FFFFFFFFFFFFFFFll / rows) return DGA_E_RANGE;
+        FusedGeometry g;
+        g.hb_n = (h + 127) / 128;
+        if (int rc = grid_of_blocks(groups * rows, g.hb_n, g.grid)) return rc;
+        g.blocks = groups * rows * g.hb_n;
+        g.small = g.blocks <= 0xFFFFFFFFll && rows <= 0xFFFFFFFFll;
+        g.ue8m0 = (flags & DGA_CAST_UE8M0) != 0;
+        return launch(tag, g);
+    });
+}
 
 }  // namespace dga

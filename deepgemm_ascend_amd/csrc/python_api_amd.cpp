@@ -325,74 +325,76 @@ std::tuple<at::Tensor, at::Tensor> cast_to_fp8(const at::Tensor &x, int block_ro
     return {q, sf};
 }
 
-// silu(x[..., :H]) * x[..., H:] -> the per-token quantiser, one pass (dga_silu_mul_cast_to_fp8_1x128).  x [rows, 2H], or [G, Mmax, 2H] with
-// masked_m int32 [G]: the rows a mask excludes are not written (the outputs are at::empty: they hold no value there).
-std::tuple<at::Tensor, at::Tensor> silu_and_mul_per_token_cast_to_fp8(const at::Tensor &x, const c10::optional<at::Tensor> &masked_m)
+// What the two fused quantiser entries share.  The layout: x [rows, 2H], or [G, Mmax, 2H] with masked_m int32 [G] on x's device, of one of the
+// three input types, the last dimension a multiple of `multiple` (last_dim: what to say when it is not).
+struct FusedLayout {
+    int64_t h, groups, rows;
+    int dt;
+    const int32_t *masked_m;
+};
+FusedLayout fused_layout(const at::Tensor &x, const c10::optional<at::Tensor> &masked_m, int64_t multiple, const char *last_dim)
 {
     on_device(x, "x");
     const bool masked = masked_m.has_value();
     TORCH_CHECK(x.dim() == (masked ? 3 : 2), masked ? "x must be [G, Mmax, 2H] with masked_m" : "x must be [rows, 2H]");
     const at::ScalarType st = x.scalar_type();
     TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "x must be float32 / bfloat16 / float16");
-    TORCH_CHECK(x.size(-1) % 2 == 0, "the last dimension of x must be even (gate and up halves)");
-    const int64_t h = x.size(-1) / 2, groups = masked ? x.size(0) : 1, rows = masked ? x.size(1) : x.size(0);
+    TORCH_CHECK(x.size(-1) % multiple == 0, last_dim);
+    const int64_t groups = masked ? x.size(0) : 1;
     if (masked) {
         on_device(*masked_m, "masked_m");
         TORCH_CHECK(masked_m->scalar_type() == at::kInt && masked_m->dim() == 1 && masked_m->size(0) == groups, "masked_m must be int32 [G]");
         TORCH_CHECK(masked_m->device() == x.device(), "all tensors must live on one device");
     }
-    const c10::OptionalDeviceGuard guard(at::device_of(x));
+    return {x.size(-1) / 2, groups, masked ? x.size(1) : x.size(0), st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16,
+            masked ? masked_m->data_ptr<int32_t>() : nullptr};
+}
+// ... and the outputs: (codes [..., width], scales [..., blocks]) with x's leading dimensions, at::empty (the rows a mask excludes are not
+// written: they hold no value)
+std::tuple<at::Tensor, at::Tensor> fused_outputs(const at::Tensor &x, int64_t width, int64_t blocks)
+{
     std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
-    shape.back() = h;
+    shape.back() = width;
     at::Tensor q = at::empty(shape, x.options().dtype(at::kFloat8_e4m3fn));
-    shape.back() = (h + 127) / 128;
-    at::Tensor sf = at::empty(shape, x.options().dtype(at::kFloat));
-    const int dt = st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16;
-    check(dga_silu_mul_cast_to_fp8_1x128(x.data_ptr(), dt, groups, rows, h, masked ? masked_m->data_ptr<int32_t>() : nullptr, nullptr,
-                                         q.data_ptr(), sf.data_ptr<float>(), 0, cur_stream()),
+    shape.back() = blocks;
+    return {q, at::empty(shape, x.options().dtype(at::kFloat))};
+}
+
+// silu(x[..., :H]) * x[..., H:] -> the per-token quantiser, one pass (dga_silu_mul_cast_to_fp8_1x128).
+std::tuple<at::Tensor, at::Tensor> silu_and_mul_per_token_cast_to_fp8(const at::Tensor &x, const c10::optional<at::Tensor> &masked_m)
+{
+    const FusedLayout l = fused_layout(x, masked_m, 2, "the last dimension of x must be even (gate and up halves)");
+    const c10::OptionalDeviceGuard guard(at::device_of(x));
+    auto [q, sf] = fused_outputs(x, l.h, (l.h + 127) / 128);
+    check(dga_silu_mul_cast_to_fp8_1x128(x.data_ptr(), l.dt, l.groups, l.rows, l.h, l.masked_m, nullptr, q.data_ptr(), sf.data_ptr<float>(), 0,
+                                         cur_stream()),
           "silu_and_mul_per_token_cast_to_fp8");
     return {q, sf};
 }
 
-// The backward of that activation -> the per-token quantiser, one pass (dga_silu_mul_bwd_cast_to_fp8_1x128): x [rows, 2H] and grad_h [rows, H],
-// or [G, Mmax, .] with masked_m int32 [G]; H % 128 == 0.  (dq [.., 2H], dsf [.., 2H/128]) = the 1x128 quantiser on [dgate | dup]; grad_x_out
-// (x's shape and dtype) receives the unquantised gradient.  The rows a mask excludes are not written.
+// The backward of that activation -> the per-token quantiser, one pass (dga_silu_mul_bwd_cast_to_fp8_1x128): grad_h [..., H] beside x; H % 128 == 0.
+// (dq [.., 2H], dsf [.., 2H/128]) = the 1x128 quantiser on [dgate | dup]; grad_x_out (x's shape and dtype) receives the unquantised gradient.
 std::tuple<at::Tensor, at::Tensor> silu_and_mul_backward_per_token_cast_to_fp8(const at::Tensor &x, const at::Tensor &grad_h,
                                                                                const c10::optional<at::Tensor> &masked_m,
                                                                                const c10::optional<at::Tensor> &grad_x_out)
 {
-    on_device(x, "x"); on_device(grad_h, "grad_h");
-    const bool masked = masked_m.has_value();
-    TORCH_CHECK(x.dim() == (masked ? 3 : 2), masked ? "x must be [G, Mmax, 2H] with masked_m" : "x must be [rows, 2H]");
-    const at::ScalarType st = x.scalar_type();
-    TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "x must be float32 / bfloat16 / float16");
-    TORCH_CHECK(x.size(-1) % 256 == 0, "the last dimension of x must be 2H with H a multiple of 128");
-    const int64_t h = x.size(-1) / 2, groups = masked ? x.size(0) : 1, rows = masked ? x.size(1) : x.size(0);
+    const FusedLayout l = fused_layout(x, masked_m, 256, "the last dimension of x must be 2H with H a multiple of 128");
+    on_device(grad_h, "grad_h");
     std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
-    shape.back() = h;
-    TORCH_CHECK(grad_h.sizes() == at::IntArrayRef(shape) && grad_h.scalar_type() == st, "grad_h must be [..., H] of x's dtype");
+    shape.back() = l.h;
+    TORCH_CHECK(grad_h.sizes() == at::IntArrayRef(shape) && grad_h.scalar_type() == x.scalar_type(), "grad_h must be [..., H] of x's dtype");
     TORCH_CHECK(x.is_contiguous() && grad_h.is_contiguous(), "x and grad_h must be contiguous");
     TORCH_CHECK(grad_h.device() == x.device(), "all tensors must live on one device");
-    if (masked) {
-        on_device(*masked_m, "masked_m");
-        TORCH_CHECK(masked_m->scalar_type() == at::kInt && masked_m->dim() == 1 && masked_m->size(0) == groups, "masked_m must be int32 [G]");
-        TORCH_CHECK(masked_m->device() == x.device(), "all tensors must live on one device");
-    }
     if (grad_x_out.has_value()) {
         on_device(*grad_x_out, "grad_x_out");
-        TORCH_CHECK(grad_x_out->sizes() == x.sizes() && grad_x_out->scalar_type() == st && grad_x_out->is_contiguous(),
+        TORCH_CHECK(grad_x_out->sizes() == x.sizes() && grad_x_out->scalar_type() == x.scalar_type() && grad_x_out->is_contiguous(),
                     "grad_x_out must be contiguous, of x's shape and dtype");
         TORCH_CHECK(grad_x_out->device() == x.device(), "all tensors must live on one device");
     }
     const c10::OptionalDeviceGuard guard(at::device_of(x));
-    shape.back() = 2 * h;
-    at::Tensor q = at::empty(shape, x.options().dtype(at::kFloat8_e4m3fn));
-    shape.back() = 2 * h / 128;
-    at::Tensor sf = at::empty(shape, x.options().dtype(at::kFloat));
-    const int dt = st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16;
-    check(dga_silu_mul_bwd_cast_to_fp8_1x128(x.data_ptr(), grad_h.data_ptr(), dt, groups, rows, h,
-                                             masked ? masked_m->data_ptr<int32_t>() : nullptr, nullptr, q.data_ptr(), sf.data_ptr<float>(),
-                                             grad_x_out.has_value() ? grad_x_out->data_ptr() : nullptr, 0, cur_stream()),
+    auto [q, sf] = fused_outputs(x, 2 * l.h, 2 * l.h / 128);
+    check(dga_silu_mul_bwd_cast_to_fp8_1x128(x.data_ptr(), grad_h.data_ptr(), l.dt, l.groups, l.rows, l.h, l.masked_m, nullptr, q.data_ptr(),
+                                             sf.data_ptr<float>(), grad_x_out.has_value() ? grad_x_out->data_ptr() : nullptr, 0, cur_stream()),
           "silu_and_mul_backward_per_token_cast_to_fp8");
     return {q, sf};
 }

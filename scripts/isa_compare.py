@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of the fp8 units of two source trees, kernel by kernel.
 
-    python scripts/isa_compare.py PARENT_TREE BRANCH_TREE [--work DIR] [--jobs N] [--units a.hip b.hip ...] > table.txt
+    python scripts/isa_compare.py PARENT_TREE BRANCH_TREE [--work DIR] [--jobs N] [--units a.hip b.hip ...] [--kernels REGEX] > table.txt
 
 Every unit is compiled in both trees with the flags its Makefile gives it (taken from `make -n`, as tests/test_build.py does),
 `--cuda-device-only -S -Rpass-analysis=kernel-resource-usage`.  Comment lines, trailing comments, .file / .loc / .ident and blank
-lines are dropped; what is left of every gemm_* kernel function is compared line for line, labels included.  The table has one
+lines are dropped; what is left of every kernel function whose mangled name matches --kernels (default gemm_; the quantiser units:
+--units dga_cast.hip dga_silu_mul_cast.hip dga_silu_mul_bwd_cast.hip --kernels cast_) is compared line for line, labels included.  The table has one
 row per kernel: identical yes/no and VGPRs / SGPRs / AGPRs / SGPR spill / VGPR spill / scratch / LDS / occupancy before -> after.
 A kernel that differs also gets its instruction counts for the mnemonics the main loops are made of.  Assembly already present
 under --work is reused (delete the directory to recompile).  Exit status 1 if any kernel differs."""
@@ -50,11 +51,11 @@ def compile_unit(tree, unit, work):
     return asm.read_text(), rem.read_text()
 
 
-def kernels(asm):
-    """name -> normalised lines of every gemm_* function"""
+def kernels(asm, pattern):
+    """name -> normalised lines of every function whose mangled name matches `pattern`"""
     out, name = {}, None
     for line in asm.splitlines():
-        m = re.match(r"^(_Z\w*gemm_\w*):", line)
+        m = re.match(r"^(_Z\w*(?:" + pattern + r")\w*):", line)
         if m:
             name = m.group(1)
             out[name] = []
@@ -97,6 +98,7 @@ def main():
     ap.add_argument("--work", default="build/isa_compare")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--units", nargs="*", default=UNITS)
+    ap.add_argument("--kernels", default="gemm_", help="regular expression a kernel's mangled name must contain")
     a = ap.parse_args()
     work = {k: Path(a.work) / k for k in ("parent", "branch")}
     for w in work.values():
@@ -108,7 +110,7 @@ def main():
     print("unit  kernel  identical  " + "  ".join(f"{s}(parent->branch)" for _, s in FIELDS))
     for u in a.units:
         (asm0, rem0), (asm1, rem1) = built[("parent", u)], built[("branch", u)]
-        k0, k1, r0, r1 = kernels(asm0), kernels(asm1), resources(rem0), resources(rem1)
+        k0, k1, r0, r1 = kernels(asm0, a.kernels), kernels(asm1, a.kernels), resources(rem0), resources(rem1)
         names = demangle(sorted(set(k0) | set(k1)))
         for n in sorted(names):
             same = k0.get(n) == k1.get(n)

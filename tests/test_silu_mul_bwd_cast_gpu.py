@@ -132,6 +132,44 @@ def test_exact_contiguous(dga, oracle, dtype, ue8m0):
     _assert_untouched(gq, gsf, ggx, rest)
 
 
+def _carved(shape, dtype, like=None):
+    """A contiguous tensor of `shape` that starts one element into a flat allocation of two elements more, every byte 0xA5 (or a copy of
+    `like`), and that allocation."""
+    n = int(np.prod(shape))
+    flat = torch.empty(n + 2, dtype=dtype, device="cuda")
+    flat.view(torch.uint8).fill_(SENTINEL_Q)
+    t = flat[1:n + 1].view(shape)
+    if like is not None:
+        t.copy_(like)
+    return t, flat
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("rows,h", [(3, 128), (17, 256)])
+def test_misaligned_pointers(dga, oracle, rows, h, dtype):
+    """x, grad_h and grad_x_out one element, dq one byte into their allocations: the kernel's element-by-element loads and stores.  dq, dsf
+    and grad_x_out equal bit for bit what the same values give through aligned tensors (which are the oracle's, as in test_exact_flat), and
+    the element in front of and behind each carved output keeps its bytes."""
+    x, grad, _, want_gx = _exact_case((rows,), h, dtype, rows * 7 + h)
+    gx = torch.empty_like(x)
+    q, sf = dga.silu_and_mul_backward_per_token_cast_to_fp8(x, grad, grad_x_out=gx, sync=True)
+    wq, wsf = _exact_want(oracle, (rows,), h, dtype, rows * 7 + h, False)
+    _assert_rows_exact(_u8(q), sf.cpu().numpy(), wq, wsf, np.arange(rows))
+    assert (_u8(gx) == want_gx).all(), "grad_x_out is not the RNE of the fp32 gradient"
+    (mx, _), (mgrad, _) = _carved(x.shape, dtype, x), _carved(grad.shape, dtype, grad)
+    (mgx, gx_flat), (mq, q_flat) = _carved(x.shape, dtype), _carved((rows, 2 * h), torch.uint8)
+    assert all(t.data_ptr() % 16 == t.element_size() for t in (mx, mgrad, mgx)) and mq.data_ptr() % 8 == 1
+    msf = torch.empty((rows, 2 * h // 128), dtype=torch.float32, device="cuda")
+    rq, rsf = dga.silu_and_mul_backward_per_token_cast_to_fp8(mx, mgrad, out=(mq, msf), grad_x_out=mgx, sync=True)
+    assert rq.data_ptr() == mq.data_ptr() and rsf is msf
+    assert torch.equal(mq, q.view(torch.uint8)), "dq differs from the aligned call's"
+    assert torch.equal(msf.view(torch.int32), sf.view(torch.int32)), "dsf differs from the aligned call's"
+    assert (_u8(mgx) == _u8(gx)).all(), "grad_x_out differs from the aligned call's"
+    for flat in (gx_flat, q_flat):
+        ends = _u8(flat[[0, -1]])
+        assert (ends == SENTINEL_Q).all(), "an element outside the carved tensor was written"
+
+
 def test_h_not_a_multiple_of_128_is_refused_on_the_device_too(dga):
     x = torch.zeros((4, 384), dtype=torch.bfloat16, device="cuda")
     with pytest.raises(dga.DGAError, match="H a multiple of 128"):
