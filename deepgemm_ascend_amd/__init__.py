@@ -35,6 +35,7 @@ from .api import (  # noqa: F401
     mfma_ceiling,
     per_block_cast_to_fp8,
     per_token_cast_to_fp8,
+    per_token_cast_to_fp8_transposed,
     platform_ascend910b,
     predict_time_us,
     route_slots,

@@ -971,15 +971,17 @@ _FUSED_LAST_DIM = {2: "the last dimension of x must be even (gate and up halves)
                    256: "the last dimension of x must be 2H with H a multiple of 128 (gate and up halves of whole 1x128 blocks)"}
 
 
-def _fused_layout(x: torch.Tensor, masked_m: Optional[torch.Tensor], m_indices: Optional[torch.Tensor], multiple: int):
+def _fused_layout(x: torch.Tensor, masked_m: Optional[torch.Tensor], m_indices: Optional[torch.Tensor], multiple: int, last: str = "2H"):
     """The row layouts of the fused quantisers, checked: x [rows, 2H], or [G, Mmax, 2H] with masked_m int32 [G], or [rows, 2H] with m_indices
-    int32 [rows]; the last dimension a multiple of `multiple`.  Returns (H, the leading dimensions, groups, rows per group)."""
+    int32 [rows]; the last dimension a multiple of `multiple` (`last`: its name in the messages -- per_token_cast_to_fp8_transposed has no
+    halves).  Returns (H, the leading dimensions, groups, rows per group)."""
     _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
     want_dim = 3 if masked_m is not None else 2
     _require(x.dim() == want_dim and x.is_contiguous(),
-             "x must be a contiguous [G, Mmax, 2H] tensor with masked_m" if masked_m is not None else "x must be a contiguous [rows, 2H] tensor")
+             f"x must be a contiguous [G, Mmax, {last}] tensor with masked_m" if masked_m is not None else f"x must be a contiguous [rows, {last}] tensor")
     _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
-    _require(x.shape[-1] % multiple == 0, _FUSED_LAST_DIM[multiple])
+    if multiple != 1:    # (1: per_token_cast_to_fp8_transposed, any width)
+        _require(x.shape[-1] % multiple == 0, _FUSED_LAST_DIM[multiple])
     lead = tuple(x.shape[:-1])
     groups, rows = (lead if masked_m is not None else (1, lead[0]))
     if masked_m is not None:
@@ -1045,8 +1047,8 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
     gemm_fp8_fp8_bf16_nt and the grouped entries with K = 2H.  H % 128 == 0 is required (no 1x128 block straddles the two halves).
     Row layouts, masks (read on the device), out=(dq, dsf), use_ue8m0 and sync: as silu_and_mul_per_token_cast_to_fp8; a row a mask
     excludes is neither read nor written, in any output.  grad_x_out: a contiguous [..., 2H] tensor of x's dtype that receives the
-    unquantised gradient in the same pass (fp32 rounded to nearest even for the 16-bit types) on the valid rows -- what a caller
-    transposes and quantises into the operand of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  For gate >= 20 the result is the quantiser's
+    unquantised gradient in the same pass (fp32 rounded to nearest even for the 16-bit types) on the valid rows -- what
+    per_token_cast_to_fp8_transposed (same mask) turns into the operand of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  For gate >= 20 the result is the quantiser's
     on [fl32(grad_h * up) | fl32(grad_h * gate)] bit for bit; for |gate| <= 16 dup is within relative 2^-18 and dgate within
     2^-17 |grad_h up| (s + |gate| s (1 - s)) of the real-number value."""
     h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 256)
@@ -1066,6 +1068,58 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
         if sync:
             torch.cuda.current_stream(x.device).synchronize()
     return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
+
+
+def per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None, m_indices: Optional[torch.Tensor] = None,
+                                     rowwise: bool = False, aligned_rows: bool = False, use_ue8m0: bool = False, out=None,
+                                     sync: bool = False):
+    """per_token_cast_to_fp8 of the transpose of token-major activations in one pass (dga_cast_to_fp8_1x128_transposed): the operands
+    of wgrad_gemm_fp8_fp8_fp32_nt / k_grouped_wgrad_gemm_fp8_fp8_fp32_nt, which run K along the tokens, without x.t().contiguous().
+      (qt, sft) = per_token_cast_to_fp8(x0.t().contiguous(), aligned_rows, use_ue8m0),  x0 = x with the rows a mask excludes set to zero,
+    byte for byte and bit for bit: qt [H, T] float8_e4m3fn, sft [H, ceil(T/128)] float32, T the number of rows of x over all groups.
+      x [T, H]                                     every row
+      x [G, Mmax, H], masked_m int32 [G]           rows r >= masked_m[g] are not read and count as zeros (T = G * Mmax)
+      x [T, H],       m_indices int32 [T]          rows with a negative index are not read and count as zeros
+    The masks are read on the device: a captured graph follows the routing.  Unlike in the fused quantisers EVERY element of qt and sft
+    is written: an excluded token has code 0, a 128-token block without a valid token has scale 1 (NaN or garbage in the padding rows
+    of a contiguous-layout buffer changes nothing: no masked_fill before the call).  aligned_rows=True: qt is a [H, T] view of rows
+    round_up(T, 128) bytes apart with zero tails, as in per_token_cast_to_fp8.
+    rowwise=True also returns (q, sf) = per_token_cast_to_fp8(x) from the same read of x -- the form fprop and dgrad take -- on the valid
+    rows (q [..., H], sf [..., ceil(H/128)]; the rows a mask excludes are not written), and the result is ((qt, sft), (q, sf)).
+    out= takes the caller's tensors in the same nesting, (qt, sft) or ((qt, sft), (q, sf)); qt with the row stride aligned_rows asks for."""
+    _, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 1, "H")
+    h, t_n = x.shape[-1], groups * rows
+    ldqt = (t_n + 127) // 128 * 128 if aligned_rows else t_n
+    tb_n, hb_n = (t_n + 127) // 128, (h + 127) // 128
+    if out is not None:
+        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be ((qt, sft), (q, sf))" if rowwise else "out must be (qt, sft)")
+    out_t, out_r = (out if rowwise else (out, None)) if out is not None else (None, None)
+    if out_t is None:
+        qt = torch.empty((h, ldqt), dtype=torch.uint8, device=x.device)[:, :t_n]
+        sft = torch.empty((h, tb_n), dtype=torch.float32, device=x.device)
+    else:
+        _require(isinstance(out_t, (tuple, list)) and len(out_t) == 2, "out must hold (qt, sft)")
+        qt, sft = out_t
+        _fp8_bytes(qt)
+        _require(tuple(qt.shape) == (h, t_n) and (t_n <= 1 or qt.stride(1) == 1) and (h <= 1 or qt.stride(0) == ldqt),
+                 f"out qt must be [{h}, {t_n}] with rows {ldqt} bytes apart")
+        _require(sft.dtype == torch.float32 and tuple(sft.shape) == (h, tb_n) and sft.is_contiguous(),
+                 f"out sft must be contiguous float32 [{h}, {tb_n}]")
+    q, sf = _fused_out(out_r, lead, h, hb_n, x.device, "q", "sf") if rowwise else (None, None)
+    with _device_guard(x, qt, sft, *(t for t in (masked_m, m_indices, q, sf) if t is not None)):
+        rc = _lib.lib().dga_cast_to_fp8_1x128_transposed(
+            x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
+            m_indices.data_ptr() if m_indices is not None else None, qt.data_ptr(), ldqt, sft.data_ptr(),
+            q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
+        _lib.check(rc, "per_token_cast_to_fp8_transposed")
+        if sync:
+            torch.cuda.current_stream(x.device).synchronize()
+    qt = qt.view(torch.float8_e4m3fn)   # (always a new tensor object: the promise below is never left on a tensor of the caller's)
+    if ldqt != t_n:
+        qt._dga_zero_padded = True      # (as _cast: the tails are zero, and views made from qt do not carry the promise)
+    if not rowwise:
+        return qt, sft
+    return (qt, sft), ((q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf)
 
 
 def route_tokens(expert_ids: torch.Tensor, groups: int):

@@ -1,4 +1,4 @@
-// What the fp8 quantisers share (dga_cast.hip, dga_silu_mul_cast.hip, dga_silu_mul_bwd_cast.hip).  Device: the e4m3fn conversion, the 16-lane DPP
+// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_silu_mul_cast.hip, dga_silu_mul_bwd_cast.hip).  Device: the e4m3fn conversion, the 16-lane DPP
 // row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition (oracle/: quant_1x128); the bounded 8-element
 // loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels' row locator and refined sigmoid.  Host, at
 // the end: the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
@@ -121,42 +121,53 @@ __device__ __forceinline__ void quant_row_block(const float (&v)[8], bool ue8m0,
     }
 }
 
+// An input type: one element, and the lane's 8 consecutive ones as one 16-byte (fp32: two) load.  load8 = unpack8(load8_raw): a kernel that
+// issues several predicated loads before it uses any keeps the Raw words until then (the conversion is a use, and a use waits).
 template <typename T> struct Elem;
 template <> struct Elem<float> {
     static constexpr int kBytes = 4;
+    struct Raw { v4f_c lo, hi; };
     static __device__ __forceinline__ float load(const void *p, int64_t i) { return ((const float *)p)[i]; }
-    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8])
+    static __device__ __forceinline__ Raw load8_raw(const void *p, int64_t i)
     {
-        const v4f_c lo = *(const v4f_c *)((const float *)p + i), hi = *(const v4f_c *)((const float *)p + i + 4);
+        return Raw{*(const v4f_c *)((const float *)p + i), *(const v4f_c *)((const float *)p + i + 4)};
+    }
+    static __device__ __forceinline__ void unpack8(const Raw &w, float (&v)[8])
+    {
+        const v4f_c lo = w.lo, hi = w.hi;
         v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
     }
+    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8]) { unpack8(load8_raw(p, i), v); }
 };
 struct Bf16Tag {};
 struct F16Tag {};
 template <> struct Elem<Bf16Tag> {
     static constexpr int kBytes = 2;
+    typedef v4i_c Raw;
     static __device__ __forceinline__ float cv(uint32_t h) { return __uint_as_float(h << 16); }
     static __device__ __forceinline__ float load(const void *p, int64_t i) { return cv(((const uint16_t *)p)[i]); }
-    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8])
+    static __device__ __forceinline__ Raw load8_raw(const void *p, int64_t i) { return *(const v4i_c *)((const uint16_t *)p + i); }
+    static __device__ __forceinline__ void unpack8(const Raw &w, float (&v)[8])
     {
-        const v4i_c w = *(const v4i_c *)((const uint16_t *)p + i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             v[2 * j] = __uint_as_float((uint32_t)w[j] << 16);
             v[2 * j + 1] = __uint_as_float((uint32_t)w[j] & 0xFFFF0000u);
         }
     }
+    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8]) { unpack8(load8_raw(p, i), v); }
 };
 template <> struct Elem<F16Tag> {
     static constexpr int kBytes = 2;
+    typedef _Float16 Raw __attribute__((ext_vector_type(8)));
     static __device__ __forceinline__ float load(const void *p, int64_t i) { return (float)((const _Float16 *)p)[i]; }
-    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8])
+    static __device__ __forceinline__ Raw load8_raw(const void *p, int64_t i) { return *(const Raw *)((const _Float16 *)p + i); }
+    static __device__ __forceinline__ void unpack8(const Raw &w, float (&v)[8])
     {
-        typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-        const v8h w = *(const v8h *)((const _Float16 *)p + i);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (float)w[j];
     }
+    static __device__ __forceinline__ void load8(const void *p, int64_t i, float (&v)[8]) { unpack8(load8_raw(p, i), v); }
 };
 
 // The lane's 8 elements, columns c0 .. c0 + 7 of a row of n columns, from element index `base` of p.  One 16-byte (fp32: two) load when the
@@ -299,13 +310,15 @@ struct FusedGeometry {
 };
 
 // The body of a fused entry point.  The checks in run_cast's order -- flags, shape (h a multiple of h_multiple), nothing to do, pointers
-// (have_ptrs: none of the required ones is null), dtype, groups * rows and the grid -- then launch(tag, geometry).
+// (have_ptrs: none of the required ones is null), dtype, groups * rows and the grid -- then launch(tag, geometry).  shape_ok: what else an
+// entry asks of its shape, refused with the shape.
 template <typename L>
 inline int run_fused(int flags, int dtype, int64_t groups, int64_t rows, int64_t h, int64_t h_multiple, const int32_t *masked_m,
-                     const int32_t *m_indices, bool have_ptrs, L &&launch)
+                     const int32_t *m_indices, bool have_ptrs, L &&launch, bool shape_ok = true)
 {
     if (flags & ~DGA_CAST_UE8M0) return DGA_E_RANGE;
-    if (groups < 1 || rows < 0 || h < 0 || h % h_multiple != 0 || (masked_m && m_indices) || (m_indices && groups != 1)) return DGA_E_SHAPE;
+    if (groups < 1 || rows < 0 || h < 0 || h % h_multiple != 0 || (masked_m && m_indices) || (m_indices && groups != 1) || !shape_ok)
+        return DGA_E_SHAPE;
     if (rows == 0 || h == 0) return DGA_OK;
     if (!have_ptrs) return DGA_E_NULL;
     return dispatch_dtype(dtype, [&](auto tag) -> int {

@@ -471,7 +471,7 @@ int dga_silu_mul_cast_to_fp8_1x128(const void *x, int x_dtype, int64_t groups, i
  * dq [groups, rows, 2h] e4m3fn bytes (dgate in the first h columns of a row, dup in the last h), dsf [groups, rows, 2h/128] fp32.
  * h % 128 == 0 is required: no 1x128 block of the [2h] axis straddles the two halves.  grad_x (may be NULL): [groups, rows, 2h] of
  * `dtype`, receives the unquantised fp32 gradient in the same pass (rounded to nearest even for the 16-bit types), on the rows that
- * are written; what a caller transposes into the operand of dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  Both gradients are formed in
+ * are written; what dga_cast_to_fp8_1x128_transposed (same mask) turns into the operand of dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  Both gradients are formed in
  * fp32 and never rounded to 16 bits before they are quantised; dq and dsf are what dga_cast_to_fp8_1x128_ex gives on them (flags:
  * DGA_CAST_UE8M0).  Accuracy: for gate >= 20 dgate = fl32(grad_h * up) and dup = fl32(grad_h * gate) exactly; for |gate| <= 16 dup is
  * within relative 2^-18 and dgate within 2^-17 |grad_h up| (s + |g| s (1 - s)) of the real-number value (silu' has a root at
@@ -482,6 +482,23 @@ int dga_silu_mul_cast_to_fp8_1x128(const void *x, int x_dtype, int64_t groups, i
 int dga_silu_mul_bwd_cast_to_fp8_1x128(const void *x, const void *grad_h, int dtype, int64_t groups, int64_t rows, int64_t h,
                                        const int32_t *masked_m, const int32_t *m_indices,
                                        void *dq, float *dsf, void *grad_x, int flags, void *stream);
+
+/* The 1x128 quantiser of the TRANSPOSE of token-major activations, in one pass -- the operands of dga_wgrad_gemm_fp8_fp8_fp32_nt and
+ * dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt (K along the tokens) from the [T, h] tensors the forward and the fused quantisers work on:
+ *   (qt, sft) = cast_to_fp8_1x128_ex( where(valid, x, 0)^T ),   byte for byte and bit for bit,
+ * x [groups, rows, h] contiguous of x_dtype (as above), T = groups * rows, qt [h, T] e4m3fn bytes in rows ldqt bytes apart,
+ * T <= ldqt <= round_up(T, 128), with zeros from byte T to the end of each row (the _ld forms' rule), sft [h, ceil(T/128)] fp32.
+ * masked_m, m_indices: as above, with the other meaning for the output: a row they exclude is not read (NaN or garbage in it changes
+ * nothing) and counts as zeros -- its codes are 0x00, and a 128-token block without a valid row has scale 1.  Every byte of qt and every
+ * scale of sft is written.  q_row, sf_row (both NULL or both set): (q_row [T, h], sf_row [T, ceil(h/128)]) = cast_to_fp8_1x128_ex(x)
+ * from the same read of x, on the valid rows; the rows a mask excludes are not written there.  T and h may be any value.
+ * flags: DGA_CAST_UE8M0.  DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a negative size, groups < 1, both masks, m_indices with
+ * groups != 1, ldqt outside its range, exactly one of q_row / sf_row;  T == 0 or h == 0 is DGA_OK with nothing touched;  then
+ * DGA_E_NULL (x, qt, sft), DGA_E_DTYPE, and DGA_E_RANGE for more 128 x 128 tiles than one grid holds. */
+int dga_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_t groups, int64_t rows, int64_t h,
+                                     const int32_t *masked_m, const int32_t *m_indices,
+                                     void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
+                                     int flags, void *stream);
 
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
