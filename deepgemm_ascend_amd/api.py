@@ -1070,25 +1070,11 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
     return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
 
 
-def per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None, m_indices: Optional[torch.Tensor] = None,
-                                     rowwise: bool = False, aligned_rows: bool = False, use_ue8m0: bool = False, out=None,
-                                     sync: bool = False):
-    """per_token_cast_to_fp8 of the transpose of token-major activations in one pass (dga_cast_to_fp8_1x128_transposed): the operands
-    of wgrad_gemm_fp8_fp8_fp32_nt / k_grouped_wgrad_gemm_fp8_fp8_fp32_nt, which run K along the tokens, without x.t().contiguous().
-      (qt, sft) = per_token_cast_to_fp8(x0.t().contiguous(), aligned_rows, use_ue8m0),  x0 = x with the rows a mask excludes set to zero,
-    byte for byte and bit for bit: qt [H, T] float8_e4m3fn, sft [H, ceil(T/128)] float32, T the number of rows of x over all groups.
-      x [T, H]                                     every row
-      x [G, Mmax, H], masked_m int32 [G]           rows r >= masked_m[g] are not read and count as zeros (T = G * Mmax)
-      x [T, H],       m_indices int32 [T]          rows with a negative index are not read and count as zeros
-    The masks are read on the device: a captured graph follows the routing.  Unlike in the fused quantisers EVERY element of qt and sft
-    is written: an excluded token has code 0, a 128-token block without a valid token has scale 1 (NaN or garbage in the padding rows
-    of a contiguous-layout buffer changes nothing: no masked_fill before the call).  aligned_rows=True: qt is a [H, T] view of rows
-    round_up(T, 128) bytes apart with zero tails, as in per_token_cast_to_fp8.
-    rowwise=True also returns (q, sf) = per_token_cast_to_fp8(x) from the same read of x -- the form fprop and dgrad take -- on the valid
-    rows (q [..., H], sf [..., ceil(H/128)]; the rows a mask excludes are not written), and the result is ((qt, sft), (q, sf)).
-    out= takes the caller's tensors in the same nesting, (qt, sft) or ((qt, sft), (q, sf)); qt with the row stride aligned_rows asks for."""
-    _, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 1, "H")
-    h, t_n = x.shape[-1], groups * rows
+def _cast_transposed(c_name: str, name: str, x, h: int, lead: tuple, groups: int, rows: int, masked_m, m_indices, rowwise: bool,
+                     aligned_rows: bool, use_ue8m0: bool, out, sync: bool):
+    """What the transposing quantisers share once the layout of x is known (h: the channels of the result): the outputs -- torch.empty, or
+    the caller's out= checked --, the call of the C entry `c_name`, and the nesting of the result."""
+    t_n = groups * rows
     ldqt = (t_n + 127) // 128 * 128 if aligned_rows else t_n
     tb_n, hb_n = (t_n + 127) // 128, (h + 127) // 128
     if out is not None:
@@ -1107,11 +1093,11 @@ def per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.T
                  f"out sft must be contiguous float32 [{h}, {tb_n}]")
     q, sf = _fused_out(out_r, lead, h, hb_n, x.device, "q", "sf") if rowwise else (None, None)
     with _device_guard(x, qt, sft, *(t for t in (masked_m, m_indices, q, sf) if t is not None)):
-        rc = _lib.lib().dga_cast_to_fp8_1x128_transposed(
+        rc = getattr(_lib.lib(), c_name)(
             x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
             m_indices.data_ptr() if m_indices is not None else None, qt.data_ptr(), ldqt, sft.data_ptr(),
             q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
-        _lib.check(rc, "per_token_cast_to_fp8_transposed")
+        _lib.check(rc, name)
         if sync:
             torch.cuda.current_stream(x.device).synchronize()
     qt = qt.view(torch.float8_e4m3fn)   # (always a new tensor object: the promise below is never left on a tensor of the caller's)
@@ -1120,6 +1106,49 @@ def per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.T
     if not rowwise:
         return qt, sft
     return (qt, sft), ((q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf)
+
+
+def per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None, m_indices: Optional[torch.Tensor] = None,
+                                     rowwise: bool = False, aligned_rows: bool = False, use_ue8m0: bool = False, out=None,
+                                     sync: bool = False):
+    """per_token_cast_to_fp8 of the transpose of token-major activations in one pass (dga_cast_to_fp8_1x128_transposed): the operands
+    of wgrad_gemm_fp8_fp8_fp32_nt / k_grouped_wgrad_gemm_fp8_fp8_fp32_nt, which run K along the tokens, without x.t().contiguous().
+      (qt, sft) = per_token_cast_to_fp8(x0.t().contiguous(), aligned_rows, use_ue8m0),  x0 = x with the rows a mask excludes set to zero,
+    byte for byte and bit for bit: qt [H, T] float8_e4m3fn, sft [H, ceil(T/128)] float32, T the number of rows of x over all groups.
+      x [T, H]                                     every row
+      x [G, Mmax, H], masked_m int32 [G]           rows r >= masked_m[g] are not read and count as zeros (T = G * Mmax)
+      x [T, H],       m_indices int32 [T]          rows with a negative index are not read and count as zeros
+    The masks are read on the device: a captured graph follows the routing.  Unlike in the fused quantisers EVERY element of qt and sft
+    is written: an excluded token has code 0, a 128-token block without a valid token has scale 1 (NaN or garbage in the padding rows
+    of a contiguous-layout buffer changes nothing: no masked_fill before the call).  aligned_rows=True: qt is a [H, T] view of rows
+    round_up(T, 128) bytes apart with zero tails, as in per_token_cast_to_fp8.
+    rowwise=True also returns (q, sf) = per_token_cast_to_fp8(x) from the same read of x -- the form fprop and dgrad take -- on the valid
+    rows (q [..., H], sf [..., ceil(H/128)]; the rows a mask excludes are not written), and the result is ((qt, sft), (q, sf)).
+    out= takes the caller's tensors in the same nesting, (qt, sft) or ((qt, sft), (q, sf)); qt with the row stride aligned_rows asks for."""
+    _, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 1, "H")
+    return _cast_transposed("dga_cast_to_fp8_1x128_transposed", "per_token_cast_to_fp8_transposed", x, x.shape[-1], lead, groups, rows,
+                            masked_m, m_indices, rowwise, aligned_rows, use_ue8m0, out, sync)
+
+
+def silu_and_mul_per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
+                                                  m_indices: Optional[torch.Tensor] = None, rowwise: bool = False,
+                                                  aligned_rows: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):
+    """The operand of the weight gradient of an expert MLP's second GEMM, dW2[g] = dout_g^T . h_g with h = silu(x[..., :H]) * x[..., H:],
+    from gate_up in one pass (dga_silu_mul_cast_to_fp8_1x128_transposed): per_token_cast_to_fp8_transposed of h, with h kept in fp32
+    registers and never written.
+      (qt, sft) = per_token_cast_to_fp8(h0.t().contiguous(), aligned_rows, use_ue8m0),  h0 = h with the rows a mask excludes set to +0:
+    qt [H, T] float8_e4m3fn, sft [H, ceil(T/128)] float32, T the number of rows of x over all groups.  x [T, 2H], or [G, Mmax, 2H] with
+    masked_m int32 [G], or [T, 2H] with m_indices int32 [T] (float32 / bfloat16 / float16, gate first): silu_and_mul_per_token_cast_to_fp8's
+    layouts, with per_token_cast_to_fp8_transposed's meaning for the output -- a row a mask excludes is not read and counts as zeros (code
+    0, a 128-token block without a valid token has scale 1), and EVERY element of qt and sft is written.  The product is the forward
+    quantiser's: for gate >= 20 the result is per_token_cast_to_fp8_transposed's on fl32(gate * up) byte for byte, for |gate| <= 16 the
+    fp32 product is within relative 2^-18 of the real-number value and every block amax is rounded from an fp64 value.
+    rowwise=True also returns (q, sf) = silu_and_mul_per_token_cast_to_fp8(x, same mask, use_ue8m0), bit for bit, from the same read of x
+    on the valid rows (the rows a mask excludes are not written), and the result is ((qt, sft), (q, sf)): a training forward gets the
+    operand of its second GEMM and that of dW2 in one pass.  aligned_rows, out=, use_ue8m0, sync: as per_token_cast_to_fp8_transposed."""
+    h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 2)
+    return _cast_transposed("dga_silu_mul_cast_to_fp8_1x128_transposed", "silu_and_mul_per_token_cast_to_fp8_transposed", x, h, lead,
+                            groups, rows, masked_m, m_indices, rowwise, aligned_rows, use_ue8m0, out, sync)
 
 
 def route_tokens(expert_ids: torch.Tensor, groups: int):

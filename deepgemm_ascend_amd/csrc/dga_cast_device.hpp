@@ -1,7 +1,8 @@
-// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_silu_mul_cast.hip, dga_silu_mul_bwd_cast.hip).  Device: the e4m3fn conversion, the 16-lane DPP
-// row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition (oracle/: quant_1x128); the bounded 8-element
-// loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels' row locator and refined sigmoid.  Host, at
-// the end: the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
+// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_silu_mul_cast.hip, dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip).
+// Device: the e4m3fn conversion, the 16-lane DPP row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition
+// (oracle/: quant_1x128); the bounded 8-element loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels'
+// row locator, refined sigmoid and silu(g) * u with its fp64-rounded block amax; the transposing kernels' row masks.  Host, at the end:
+// the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -279,6 +280,54 @@ __device__ __forceinline__ float sigmoid_refined(float g, float &e)
     return __builtin_fmaf(__builtin_fmaxf(__builtin_fmaf(-d, r0, 1.f), -1.f), r0, r0);
 }
 
+// silu(g) * u = (g s) u, s the refined sigmoid (sigmoid_refined: 0 for exp(-g) = inf, NaN for a NaN g)
+__device__ __forceinline__ float silu_mul(float g, float u)
+{
+    float e;
+    return (g * sigmoid_refined(g, e)) * u;
+}
+
+// The lane's largest |h| once more, as the fp32 nearest to the real-number value: the block scale is amax / 448, and an amax that is
+// within 2^-19.7 but a ULP or two off the correctly rounded one puts every dequantised value (code x scale) of its block the same
+// ULP off.  fp64 exponential and division (error 2^-51, so the one rounding to fp32 is the right one but for 2^-27 of the inputs),
+// one element per lane and block.  Where 1 + exp(-g) rounds to 1 in fp32 the value stays h32 = fl32(g * u): the contract for
+// gate >= 20.  h32 = |silu_mul(g, u)|.
+__device__ __forceinline__ float silu_mul_abs_rounded(float g, float u, float h32)
+{
+    const bool one = 1.f + exp_neg(g) == 1.f;
+    const double gd = g;
+    const float hd = (float)(gd / (1.0 + exp(-gd)) * (double)u);
+    return one ? h32 : __builtin_fabsf(hd);
+}
+
+// ---- the transposing quantisers (dga_cast_transposed.hip, dga_silu_mul_cast_transposed.hip): 256 lanes on 128 tokens x 128 channels
+
+// locate_row's predicate for the 8 consecutive rows r0 .. r0 + 7 of t_n > 0 (counted over all groups of mmax rows): ok[p] = the row exists
+// and the mask does not exclude it.  No branch between the 8 reads of the mask, so they go out together: a row beyond the last asks about
+// the last, and the group and the row in it come from one division, stepped (a step crosses at most one group boundary: mmax >= 1).
+__device__ __forceinline__ void rows_valid8(int64_t r0, int64_t t_n, int64_t mmax, const int32_t *masked_m, const int32_t *m_indices,
+                                            bool small, bool (&ok)[8])
+{
+    const int64_t last = t_n - 1, first = r0 < last ? r0 : last;
+    if (masked_m) {
+        int64_t g = udiv(first, mmax, small), r = first - g * mmax;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            ok[p] = (r < masked_m[g]) & (r0 + p <= last);
+            r += r0 + p < last;
+            const bool next = r == mmax;
+            g += next;
+            r = next ? 0 : r;
+        }
+    } else if (m_indices) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) ok[p] = (m_indices[r0 + p < last ? r0 + p : last] >= 0) & (r0 + p <= last);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) ok[p] = r0 + p <= last;
+    }
+}
+
 // ---- host side: what the three units' launchers share
 
 // dtype (DGA_DT_*) -> f(tag), tag an object of the type the kernels are instantiated on (float / Bf16Tag / F16Tag); DGA_E_DTYPE for any other
@@ -331,6 +380,15 @@ inline int run_fused(int flags, int dtype, int64_t groups, int64_t rows, int64_t
         g.ue8m0 = (flags & DGA_CAST_UE8M0) != 0;
         return launch(tag, g);
     });
+}
+
+// The transposing entries' row stride: T <= ldqt <= round_up(T, 128) with T = groups * rows, decided without a product or a sum that
+// overflows (a T beyond int64 has no ldqt)
+inline bool transposed_ldqt_ok(int64_t groups, int64_t rows, int64_t ldqt)
+{
+    if (groups < 1 || rows < 0 || rows > 0x7FFFFFFFFFFFFFFFll / groups) return false;
+    const int64_t t_n = groups * rows;
+    return ldqt >= t_n && ldqt - t_n <= (128 - t_n % 128) % 128;
 }
 
 }  // namespace dga

@@ -15,32 +15,6 @@
 
 namespace dga {
 
-// locate_row's predicate for the 8 consecutive rows r0 .. r0 + 7 of t_n > 0 (counted over all groups of mmax rows): ok[p] = the row exists
-// and the mask does not exclude it.  No branch between the 8 reads of the mask, so they go out together: a row beyond the last asks about
-// the last, and the group and the row in it come from one division, stepped (a step crosses at most one group boundary: mmax >= 1).
-__device__ __forceinline__ void rows_valid8(int64_t r0, int64_t t_n, int64_t mmax, const int32_t *masked_m, const int32_t *m_indices,
-                                            bool small, bool (&ok)[8])
-{
-    const int64_t last = t_n - 1, first = r0 < last ? r0 : last;
-    if (masked_m) {
-        int64_t g = udiv(first, mmax, small), r = first - g * mmax;
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            ok[p] = (r < masked_m[g]) & (r0 + p <= last);
-            r += r0 + p < last;
-            const bool next = r == mmax;
-            g += next;
-            r = next ? 0 : r;
-        }
-    } else if (m_indices) {
-#pragma unroll
-        for (int p = 0; p < 8; ++p) ok[p] = (m_indices[r0 + p < last ? r0 + p : last] >= 0) & (r0 + p <= last);
-    } else {
-#pragma unroll
-        for (int p = 0; p < 8; ++p) ok[p] = r0 + p <= last;
-    }
-}
-
 // One workgroup per tile of 128 tokens x 128 channels; workgroups that follow each other share the tokens (whole rows of x are read side
 // by side).  16 lanes share a row, 8 consecutive channels per lane (cast_1x128_kernel's loads: 256 contiguous bytes of bf16 per row), and
 // row group rg = t / 16 holds the 8 CONSECUTIVE tokens 8 rg .. 8 rg + 7, one per pass: 64 fp32 values per lane, and the 8 codes of one
@@ -149,13 +123,7 @@ extern "C" int dga_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int6
                                                 void *q_row, float *sf_row, int flags, void *stream)
 {
     using namespace dga;
-    // T <= ldqt <= round_up(T, 128), decided without a product or a sum that overflows (a T beyond int64 has no ldqt)
-    const auto ldqt_ok = [&] {
-        if (groups < 1 || rows < 0 || rows > 0x7FFFFFFFFFFFFFFFll / groups) return false;
-        const int64_t t_n = groups * rows;
-        return ldqt >= t_n && ldqt - t_n <= (128 - t_n % 128) % 128;
-    };
-    const bool shape_ok = ldqt_ok() && (q_row != nullptr) == (sf_row != nullptr);
+    const bool shape_ok = transposed_ldqt_ok(groups, rows, ldqt) && (q_row != nullptr) == (sf_row != nullptr);
     return run_fused(flags, x_dtype, groups, rows, h, 1, masked_m, m_indices, x && qt && sft, [&](auto tag, const FusedGeometry &g) -> int {
         using T = decltype(tag);
         const int64_t t_n = groups * rows, tb_n = (t_n + 127) / 128;

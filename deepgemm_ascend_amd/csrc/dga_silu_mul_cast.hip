@@ -26,26 +26,6 @@
 
 namespace dga {
 
-// silu(g) * u = (g s) u, s the refined sigmoid (sigmoid_refined: 0 for exp(-g) = inf, NaN for a NaN g)
-__device__ __forceinline__ float silu_mul(float g, float u)
-{
-    float e;
-    return (g * sigmoid_refined(g, e)) * u;
-}
-
-// The lane's largest |h| once more, as the fp32 nearest to the real-number value: the block scale is amax / 448, and an amax that is
-// within 2^-19.7 but a ULP or two off the correctly rounded one puts every dequantised value (code x scale) of its block the same
-// ULP off.  fp64 exponential and division (error 2^-51, so the one rounding to fp32 is the right one but for 2^-27 of the inputs),
-// one element per lane and block.  Where 1 + exp(-g) rounds to 1 in fp32 the value stays h32 = fl32(g * u): the contract for
-// gate >= 20.  h32 = |silu_mul(g, u)|.
-__device__ __forceinline__ float silu_mul_abs_rounded(float g, float u, float h32)
-{
-    const bool one = 1.f + exp_neg(g) == 1.f;
-    const double gd = g;
-    const float hd = (float)(gd / (1.0 + exp(-gd)) * (double)u);
-    return one ? h32 : __builtin_fabsf(hd);
-}
-
 // cast_1x128_kernel's geometry: 16 lanes share one 1x128 block of h, 8 consecutive elements per lane (for bf16 one 16-byte load
 // of gate and one of up: 32 bytes in flight per lane), DPP row max, no LDS.  `blocks` = rows_total * hb_n 16-lane groups over the
 // rows of all groups; a group of lanes whose row the mask excludes leaves as a whole before it reads x.

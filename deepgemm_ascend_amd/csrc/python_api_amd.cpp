@@ -424,6 +424,33 @@ std::tuple<at::Tensor, at::Tensor> per_token_cast_to_fp8_transposed(const at::Te
     return {qt, sft};
 }
 
+// The same on h = silu(x[..., :H]) * x[..., H:] in one pass (dga_silu_mul_cast_to_fp8_1x128_transposed): x [T, 2H] -> (qt [H, T],
+// sft [H, ceil(T/128)]), the operand of dW2; rows with a negative m_indices (int32 [T]) are not read and count as zeros.
+std::tuple<at::Tensor, at::Tensor> silu_and_mul_per_token_cast_to_fp8_transposed(const at::Tensor &x, const c10::optional<at::Tensor> &m_indices)
+{
+    on_device(x, "x");
+    TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), "x must be a contiguous [T, 2H] tensor");
+    const at::ScalarType st = x.scalar_type();
+    TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "x must be float32 / bfloat16 / float16");
+    TORCH_CHECK(x.size(1) % 2 == 0, "the last dimension of x must be even (gate and up halves)");
+    const int64_t t_n = x.size(0), h = x.size(1) / 2;
+    if (m_indices.has_value()) {
+        on_device(*m_indices, "m_indices");
+        TORCH_CHECK(m_indices->scalar_type() == at::kInt && m_indices->dim() == 1 && m_indices->size(0) == t_n && m_indices->is_contiguous(),
+                    "m_indices must be a contiguous int32 [T]");
+        TORCH_CHECK(m_indices->device() == x.device(), "all tensors must live on one device");
+    }
+    const c10::OptionalDeviceGuard guard(at::device_of(x));
+    at::Tensor qt = at::empty({h, t_n}, x.options().dtype(at::kFloat8_e4m3fn));
+    at::Tensor sft = at::empty({h, (t_n + 127) / 128}, x.options().dtype(at::kFloat));
+    const int dt = st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16;
+    check(dga_silu_mul_cast_to_fp8_1x128_transposed(x.data_ptr(), dt, 1, t_n, h, nullptr,
+                                                    m_indices.has_value() ? m_indices->data_ptr<int32_t>() : nullptr, qt.data_ptr(), t_n,
+                                                    sft.data_ptr<float>(), nullptr, nullptr, 0, cur_stream()),
+          "silu_and_mul_per_token_cast_to_fp8_transposed");
+    return {qt, sft};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.cpp:30)
@@ -454,5 +481,7 @@ PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.c
     m.def("silu_and_mul_backward_per_token_cast_to_fp8", &silu_and_mul_backward_per_token_cast_to_fp8, py::arg("x"), py::arg("grad_h"),
           py::arg("masked_m") = py::none(), py::arg("grad_x_out") = py::none());
     m.def("per_token_cast_to_fp8_transposed", &per_token_cast_to_fp8_transposed, py::arg("x"), py::arg("m_indices") = py::none());
+    m.def("silu_and_mul_per_token_cast_to_fp8_transposed", &silu_and_mul_per_token_cast_to_fp8_transposed, py::arg("x"),
+          py::arg("m_indices") = py::none());
     m.def("abi_version", [] { return dga_abi_version(); });
 }

@@ -500,6 +500,27 @@ int dga_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_t groups,
                                      void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
                                      int flags, void *stream);
 
+/* The same quantiser on h = silu(gate) * up -- the operand of the weight gradient of an expert MLP's second GEMM, dW2[g] = dout_g^T . h_g,
+ * from the tensor dga_silu_mul_cast_to_fp8_1x128 read, in one pass and without h ever leaving fp32 registers:
+ *   (qt, sft) = cast_to_fp8_1x128_ex( where(valid, silu(gate) * up, 0)^T ),
+ * x [groups, rows, 2h] contiguous of x_dtype (gate in the first h columns of a row, up in the last h), T = groups * rows, qt [h, T] e4m3fn
+ * bytes in rows ldqt bytes apart, T <= ldqt <= round_up(T, 128), zeros from byte T to the end of each row, sft [h, ceil(T/128)] fp32.
+ * The product is dga_silu_mul_cast_to_fp8_1x128's, with its accuracy: fl32(gate * up) exactly for gate >= 20 -- there qt and sft are
+ * dga_cast_to_fp8_1x128_transposed's on that product byte for byte --, within relative 2^-18 for |gate| <= 16, +-0 for gate <= -88.8; the
+ * amax of every 128-token block is rounded from an fp64 value of its largest element, as the forward's block amax is.  A NaN in gate or
+ * up gives code sign | 0x7F and is ignored by the amax.  masked_m, m_indices: as in dga_cast_to_fp8_1x128_transposed -- a row they
+ * exclude is not read and counts as h = +0 (code 0x00; a 128-token block without a valid row has scale 1), and every byte of qt and every
+ * scale of sft is written.  q_row, sf_row (both NULL or both set): (q_row [T, h], sf_row [T, ceil(h/128)]) are
+ * dga_silu_mul_cast_to_fp8_1x128's outputs, bit for bit, from the same read of x, on the valid rows; the rows a mask excludes are not
+ * written there -- a training forward gets both operands in one pass.  T and h may be any value.  flags: DGA_CAST_UE8M0.  Checks, in
+ * dga_cast_to_fp8_1x128_transposed's order: DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a negative size, groups < 1, both masks,
+ * m_indices with groups != 1, ldqt outside its range, exactly one of q_row / sf_row;  T == 0 or h == 0 is DGA_OK with nothing touched;
+ * then DGA_E_NULL (x, qt, sft), DGA_E_DTYPE, and DGA_E_RANGE for more 128 x 128 tiles than one grid holds. */
+int dga_silu_mul_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_t groups, int64_t rows, int64_t h,
+                                              const int32_t *masked_m, const int32_t *m_indices,
+                                              void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
+                                              int flags, void *stream);
+
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
 /* struct Config in declaration order (get_best_config.hpp:12-31), 28 uint32. */
