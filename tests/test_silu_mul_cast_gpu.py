@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+from fused_bounds import EPS, _e4m3_rne_satfinite, _h_ref     # (moved there unchanged: tests/test_moe_mlp_step_gpu.py shares them)
+
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -18
 DTYPES = [torch.bfloat16, torch.float16, torch.float32]
 SENTINEL_Q = 0xA5
 SENTINEL_SF = 0x7FC0A5A5            # a NaN pattern the kernel never writes (its scales are positive and finite)
@@ -144,25 +145,6 @@ def _tol_inputs(lead, h, dtype, seed):
     gate = (torch.randn(lead + (h,), device="cuda", generator=g) * 3.0).clamp(-16.0, 16.0).to(dtype)
     up = (torch.randn(lead + (h,), device="cuda", generator=g) * 3.0).to(dtype)
     return torch.cat([gate, up], dim=-1).contiguous(), gate, up
-
-
-def _h_ref(gate, up):
-    """fl32 of the float64 value of g / (1 + exp(-g)) * u, rows flattened."""
-    g = gate.double().cpu().numpy().reshape(-1, gate.shape[-1])
-    u = up.double().cpu().numpy().reshape(-1, up.shape[-1])
-    return (g / (1.0 + np.exp(-g)) * u).astype(np.float32)
-
-
-def _e4m3_rne_satfinite(oracle, y):
-    """float64 -> the e4m3fn value nearest to it (ties to the even code, |y| > 448 to +-448), from the oracle's code table."""
-    vals = oracle.e4m3fn_table()[:0x7F].astype(np.float64)          # codes 0x00..0x7E: 0 .. 448, increasing with the code
-    assert (np.diff(vals) > 0).all() and vals[0] == 0.0 and vals[-1] == 448.0
-    a = np.minimum(np.abs(y), 448.0)
-    hi = np.clip(np.searchsorted(vals, a, side="left"), 1, len(vals) - 1)
-    lo = hi - 1
-    dlo, dhi = a - vals[lo], vals[hi] - a
-    code = np.where(dlo < dhi, lo, np.where(dhi < dlo, hi, np.where(lo % 2 == 0, lo, hi)))
-    return np.copysign(vals[code], y)
 
 
 def _check_tolerance(oracle, gq, gsf, href, ue8m0, rows, label):
