@@ -1151,6 +1151,56 @@ def silu_and_mul_per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Opt
                             groups, rows, masked_m, m_indices, rowwise, aligned_rows, use_ue8m0, out, sync)
 
 
+def _block_out(out, q_shape: tuple, sf_shape: tuple, device, q_name: str, sf_name: str):
+    """_fused_out for the weight quantiser, whose codes and scales do not share their leading dimensions: (q q_shape bytes, sf sf_shape
+    float32), torch.empty or the caller's out=(q, sf) checked."""
+    if out is None:
+        return torch.empty(q_shape, dtype=torch.uint8, device=device), torch.empty(sf_shape, dtype=torch.float32, device=device)
+    _require(isinstance(out, (tuple, list)) and len(out) == 2 and all(isinstance(t, torch.Tensor) for t in out),
+             f"out must hold ({q_name}, {sf_name})")
+    q, sf = out
+    _fp8_bytes(q)
+    _require(tuple(q.shape) == q_shape and q.is_contiguous(), f"out {q_name} must be contiguous {list(q_shape)}")
+    _require(sf.dtype == torch.float32 and tuple(sf.shape) == sf_shape and sf.is_contiguous(),
+             f"out {sf_name} must be contiguous float32 {list(sf_shape)}")
+    return q, sf
+
+
+def per_block_cast_to_fp8_transposed(w: torch.Tensor, rowwise: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):
+    """per_block_cast_to_fp8 of the transposes of grouped expert weights in one pass (dga_cast_to_fp8_128x128_transposed): the rhs of dgrad,
+    and with rowwise=True the rhs of fprop too, from the master weights -- no loop over the experts, no w[g].t().contiguous(), no stack.
+      (qt[g], sft[g]) = per_block_cast_to_fp8(w[g].t().contiguous(), use_ue8m0=use_ue8m0)   for every g, byte for byte and bit for bit,
+    w [G, N, K] contiguous, float32 / bfloat16 / float16 -> qt [G, K, N] float8_e4m3fn, sft [G, ceil(K/128), ceil(N/128)] float32.  A 2-D
+    w [N, K] gives 2-D results.  (A 128x128 block's amax does not change under transposition: these are per_block_cast_to_fp8(w[g])'s codes
+    and scales transposed, and no scale block mixes two experts, whatever N is.)
+    rowwise=True also returns (q[g], sf[g]) = per_block_cast_to_fp8(w[g], use_ue8m0=use_ue8m0) from the same read of w, q [G, N, K],
+    sf [G, ceil(N/128), ceil(K/128)], and the result is ((qt, sft), (q, sf)).  out= takes the caller's tensors in the same nesting,
+    (qt, sft) or ((qt, sft), (q, sf)), codes uint8 or float8_e4m3fn, all contiguous and of exactly these shapes; every element of every
+    output is written.  The results are what the grouped GEMM entries (and, 2-D, gemm_fp8_fp8_bf16_nt) take as rhs as they are."""
+    _require(w.dim() in (2, 3) and w.is_contiguous(), "w must be a contiguous [N, K] or [G, N, K] tensor")
+    _require(w.dtype in _CAST_DT, "w must be float32, bfloat16 or float16")
+    lead = tuple(w.shape[:-2])
+    groups = lead[0] if lead else 1
+    n, k = w.shape[-2:]
+    nb, kb = (n + 127) // 128, (k + 127) // 128
+    if out is not None:
+        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be ((qt, sft), (q, sf))" if rowwise else "out must be (qt, sft)")
+    out_t, out_r = (out if rowwise else (out, None)) if out is not None else (None, None)
+    qt, sft = _block_out(out_t, lead + (k, n), lead + (kb, nb), w.device, "qt", "sft")
+    q, sf = _block_out(out_r, lead + (n, k), lead + (nb, kb), w.device, "q", "sf") if rowwise else (None, None)
+    with _device_guard(w, qt, sft, *(t for t in (q, sf) if t is not None)):
+        rc = _lib.lib().dga_cast_to_fp8_128x128_transposed(
+            w.data_ptr(), _CAST_DT[w.dtype], groups, n, k, qt.data_ptr(), sft.data_ptr(), q.data_ptr() if rowwise else None,
+            sf.data_ptr() if rowwise else None, _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(w))
+        _lib.check(rc, "per_block_cast_to_fp8_transposed")
+        if sync:
+            torch.cuda.current_stream(w.device).synchronize()
+    f8 = lambda t: t if t.dtype != torch.uint8 else t.view(torch.float8_e4m3fn)
+    if not rowwise:
+        return f8(qt), sft
+    return (f8(qt), sft), (f8(q), sf)
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

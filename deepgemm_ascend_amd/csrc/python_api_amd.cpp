@@ -451,6 +451,30 @@ std::tuple<at::Tensor, at::Tensor> silu_and_mul_per_token_cast_to_fp8_transposed
     return {qt, sft};
 }
 
+// per_block_cast_to_fp8 of every w[g]^T in one pass (dga_cast_to_fp8_128x128_transposed): w [G, N, K] or [N, K] -> (qt [G, K, N],
+// sft [G, ceil(K/128), ceil(N/128)]), 2-D for a 2-D w: the rhs of dgrad from the master weights.
+std::tuple<at::Tensor, at::Tensor> per_block_cast_to_fp8_transposed(const at::Tensor &w)
+{
+    on_device(w, "w");
+    TORCH_CHECK((w.dim() == 2 || w.dim() == 3) && w.is_contiguous(), "w must be a contiguous [N, K] or [G, N, K] tensor");
+    const at::ScalarType st = w.scalar_type();
+    TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "w must be float32 / bfloat16 / float16");
+    const int64_t groups = w.dim() == 3 ? w.size(0) : 1, n = w.size(-2), k = w.size(-1);
+    const c10::OptionalDeviceGuard guard(at::device_of(w));
+    std::vector<int64_t> shape(w.sizes().begin(), w.sizes().end());
+    shape[shape.size() - 2] = k;
+    shape.back() = n;
+    at::Tensor qt = at::empty(shape, w.options().dtype(at::kFloat8_e4m3fn));
+    shape[shape.size() - 2] = (k + 127) / 128;
+    shape.back() = (n + 127) / 128;
+    at::Tensor sft = at::empty(shape, w.options().dtype(at::kFloat));
+    const int dt = st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16;
+    check(dga_cast_to_fp8_128x128_transposed(w.data_ptr(), dt, groups, n, k, qt.data_ptr(), sft.data_ptr<float>(), nullptr, nullptr, 0,
+                                             cur_stream()),
+          "per_block_cast_to_fp8_transposed");
+    return {qt, sft};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.cpp:30)
@@ -483,5 +507,6 @@ PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.c
     m.def("per_token_cast_to_fp8_transposed", &per_token_cast_to_fp8_transposed, py::arg("x"), py::arg("m_indices") = py::none());
     m.def("silu_and_mul_per_token_cast_to_fp8_transposed", &silu_and_mul_per_token_cast_to_fp8_transposed, py::arg("x"),
           py::arg("m_indices") = py::none());
+    m.def("per_block_cast_to_fp8_transposed", &per_block_cast_to_fp8_transposed, py::arg("w"));
     m.def("abi_version", [] { return dga_abi_version(); });
 }

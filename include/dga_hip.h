@@ -521,6 +521,19 @@ int dga_silu_mul_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_
                                               void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
                                               int flags, void *stream);
 
+/* The 128x128 quantiser of grouped expert weights and of their transposes, in one pass -- the rhs of fprop (W) and of dgrad (W^T) from
+ * the master weights, with no loop over the experts, no transposing copy and no stacking:
+ *   (qt[g], sft[g]) = cast_to_fp8_128x128_ex( w[g]^T ),   byte for byte and bit for bit, for every group g,
+ * w [groups, n, k] contiguous of w_dtype (DGA_DT_FP32 / BF16 / FP16), qt [groups, k, n] e4m3fn bytes, sft [groups, ceil(k/128),
+ * ceil(n/128)] fp32, both contiguous.  A 128x128 block's amax does not change under transposition, so these are the codes and scales of
+ * cast_to_fp8_128x128_ex(w[g]) transposed; no scale block mixes two groups, whatever n is.  q_row, sf_row (both NULL or both set):
+ * (q_row[g] [n, k], sf_row[g] [ceil(n/128), ceil(k/128)]) = cast_to_fp8_128x128_ex(w[g]) from the same read of w.  Every byte of every
+ * output and every scale is written; n and k may be any value.  flags: DGA_CAST_UE8M0.  DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a
+ * negative size, exactly one of q_row / sf_row;  groups, n or k zero is DGA_OK with nothing touched;  then DGA_E_NULL (w, qt, sft),
+ * DGA_E_DTYPE, and DGA_E_RANGE for more 128 x 128 tiles than one grid holds (2^31 - 1). */
+int dga_cast_to_fp8_128x128_transposed(const void *w, int w_dtype, int64_t groups, int64_t n, int64_t k,
+                                       void *qt, float *sft, void *q_row, float *sf_row, int flags, void *stream);
+
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
 /* struct Config in declaration order (get_best_config.hpp:12-31), 28 uint32. */
