@@ -1071,9 +1071,10 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
 
 
 def _cast_transposed(c_name: str, name: str, x, h: int, lead: tuple, groups: int, rows: int, masked_m, m_indices, rowwise: bool,
-                     aligned_rows: bool, use_ue8m0: bool, out, sync: bool):
+                     aligned_rows: bool, use_ue8m0: bool, out, sync: bool, call=None, also=()):
     """What the transposing quantisers share once the layout of x is known (h: the channels of the result): the outputs -- torch.empty, or
-    the caller's out= checked --, the call of the C entry `c_name`, and the nesting of the result."""
+    the caller's out= checked --, the call of the C entry `c_name`, and the nesting of the result.  call: an entry with other inputs than
+    (x, masked_m, m_indices) -- call(fn, qt, ldqt, sft, q, sf, flags, stream) -> rc, q and sf pointers or None; also: its further tensors."""
     t_n = groups * rows
     ldqt = (t_n + 127) // 128 * 128 if aligned_rows else t_n
     tb_n, hb_n = (t_n + 127) // 128, (h + 127) // 128
@@ -1092,11 +1093,15 @@ def _cast_transposed(c_name: str, name: str, x, h: int, lead: tuple, groups: int
         _require(sft.dtype == torch.float32 and tuple(sft.shape) == (h, tb_n) and sft.is_contiguous(),
                  f"out sft must be contiguous float32 [{h}, {tb_n}]")
     q, sf = _fused_out(out_r, lead, h, hb_n, x.device, "q", "sf") if rowwise else (None, None)
-    with _device_guard(x, qt, sft, *(t for t in (masked_m, m_indices, q, sf) if t is not None)):
-        rc = getattr(_lib.lib(), c_name)(
-            x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
-            m_indices.data_ptr() if m_indices is not None else None, qt.data_ptr(), ldqt, sft.data_ptr(),
-            q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
+    with _device_guard(x, qt, sft, *also, *(t for t in (masked_m, m_indices, q, sf) if t is not None)):
+        fn, flags = getattr(_lib.lib(), c_name), _lib.CAST_UE8M0 if use_ue8m0 else 0
+        if call is not None:
+            rc = call(fn, qt.data_ptr(), ldqt, sft.data_ptr(), q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, flags,
+                      _stream_ptr(x))
+        else:
+            rc = fn(x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
+                    m_indices.data_ptr() if m_indices is not None else None, qt.data_ptr(), ldqt, sft.data_ptr(),
+                    q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, flags, _stream_ptr(x))
         _lib.check(rc, name)
         if sync:
             torch.cuda.current_stream(x.device).synchronize()
@@ -1149,6 +1154,111 @@ def silu_and_mul_per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Opt
     h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 2)
     return _cast_transposed("dga_silu_mul_cast_to_fp8_1x128_transposed", "silu_and_mul_per_token_cast_to_fp8_transposed", x, h, lead,
                             groups, rows, masked_m, m_indices, rowwise, aligned_rows, use_ue8m0, out, sync)
+
+
+def gather_per_token_cast_to_fp8_transposed(src: torch.Tensor, index: torch.Tensor, index_div: int = 1,
+                                            row_scale: Optional[torch.Tensor] = None, masked_m: Optional[torch.Tensor] = None,
+                                            rowwise: bool = False, aligned_rows: bool = False, use_ue8m0: bool = False, out=None,
+                                            sync: bool = False):
+    """The dispatch of an MoE layer fused into per_token_cast_to_fp8_transposed (dga_gather_cast_to_fp8_1x128_transposed): the rows are read
+    through a table, and the gathered tensor is never written.  src [S, H] contiguous float32 / bfloat16 / float16, any H >= 1; index int64
+    [T], or [G, Mmax] with masked_m int32 [G]; P = S * index_div pairs.  Row r is valid iff masked_m does not exclude it and
+    0 <= index[r] < P; an index entry that masked_m excludes is not read (route_slots leaves stale values there), a value outside [0, P)
+    excludes the row and dereferences nothing.  A valid row is
+      xg[r] = src[index[r] // index_div]                                  (src's dtype)
+      xg[r] = row_scale[index[r]] * src[index[r] // index_div].float()    (row_scale: float32, P elements; xg is float32)
+    and the result is per_token_cast_to_fp8_transposed(xg, m_indices=where(valid, 0, -1), rowwise, aligned_rows, use_ue8m0), byte for byte
+    and bit for bit, with that entry's contract: excluded rows count as zeros and are never read, every element of qt [H, T] and
+    sft [H, ceil(T/128)] is written (T = index.numel()), a 128-token block without a valid token has scale 1; rowwise=True also returns
+    (q, sf) with index's leading dimensions, written on the valid rows only, and the result is ((qt, sft), (q, sf)); out= takes the same
+    nesting; aligned_rows keeps its row stride.  On route_slots(keys = the top-k ids flattened, cap = Mmax): index = inverse.view(G, Mmax),
+    index_div = k, masked_m = counts is the lhs of the step's first GEMM (with rowwise) and the operand of dW1; the same call on dY with
+    row_scale = w.view(-1) is dOut = w * dY[token], never written; a 1-D index with -1 on the padding rows is the contiguous layout.
+    The table is read on the device: a captured graph follows the routing."""
+    _require(src.dim() == 2 and src.is_contiguous(), "src must be a contiguous [S, H] tensor")
+    _require(src.dtype in _CAST_DT, "src must be float32, bfloat16 or float16")
+    _require(isinstance(index_div, int) and index_div >= 1, "index_div must be an integer >= 1")
+    want_dim = 2 if masked_m is not None else 1
+    _require(index.dtype == torch.int64 and index.dim() == want_dim and index.is_contiguous(),
+             "index must be a contiguous int64 [G, Mmax] tensor with masked_m" if masked_m is not None else "index must be a contiguous int64 [T] tensor")
+    lead = tuple(index.shape)
+    groups, rows = (lead if masked_m is not None else (1, lead[0]))
+    if masked_m is not None:
+        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
+                 f"masked_m must be a contiguous int32 [{groups}]")
+    s_n, h = src.shape
+    if row_scale is not None:
+        _require(row_scale.dtype == torch.float32 and row_scale.numel() == s_n * index_div and row_scale.is_contiguous(),
+                 f"row_scale must be contiguous float32 with {s_n * index_div} elements")
+    call = lambda fn, qt, ldqt, sft, q, sf, flags, stream: fn(
+        src.data_ptr(), _CAST_DT[src.dtype], s_n, h, index.data_ptr(), index_div, row_scale.data_ptr() if row_scale is not None else None,
+        groups, rows, masked_m.data_ptr() if masked_m is not None else None, qt, ldqt, sft, q, sf, flags, stream)
+    return _cast_transposed("dga_gather_cast_to_fp8_1x128_transposed", "gather_per_token_cast_to_fp8_transposed", src, h, lead, groups, rows,
+                            masked_m, None, rowwise, aligned_rows, use_ue8m0, out, sync, call=call,
+                            also=(index,) + ((row_scale,) if row_scale is not None else ()))
+
+
+def _combine_layout(name: str, src: torch.Tensor, dest: torch.Tensor):
+    """The checks combine_tokens and combine_tokens_weight_grad share: src [S, H], dest int64 [T, k] with k >= 1.  Returns (S, H, T, k)."""
+    _require(src.dim() == 2 and src.is_contiguous(), "src must be a contiguous [S, H] tensor")
+    _require(src.dtype in _CAST_DT, "src must be float32, bfloat16 or float16")
+    _require(dest.dtype == torch.int64 and dest.dim() == 2 and dest.is_contiguous() and dest.shape[1] >= 1,
+             "dest must be a contiguous int64 [T, k] tensor with k >= 1")
+    return src.shape[0], src.shape[1], dest.shape[0], dest.shape[1]
+
+
+def combine_tokens(src: torch.Tensor, dest: torch.Tensor, weights: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   sync: bool = False) -> torch.Tensor:
+    """The combine of an MoE layer on route_slots' pair -> slot table (dga_combine_rows): y[t] = sum_j weights[t, j] * src[dest[t, j]].
+    src [S, H] contiguous float32 / bfloat16 / float16, dest int64 [T, k], weights float32 [T, k] or None, out [T, H] of src's dtype
+    (the default) or float32.  Per element, in float32: acc = +0; for j = 0 .. k-1 in that order, where 0 <= dest[t, j] < S,
+    acc = fl32(acc + fl32(weights[t, j] * src[dest[t, j], c])) -- two roundings, never a fused multiply-add; without weights the product is
+    the value itself -- and out[t, c] = acc rounded to nearest even.  A choice whose dest is outside [0, S) is skipped whatever its weight
+    (route_slots marks dropped rows with -1), a token without a valid choice gets a row of +0, and every element of out is written.  The
+    definition is numpy float32 arithmetic, so a host reference matches bit for bit.  weights=None is the backward of the dispatch,
+    dX[t] = sum_j dX_slots[dest[t, j]]."""
+    s_n, h, t_n, k = _combine_layout("combine_tokens", src, dest)
+    if weights is not None:
+        _require(weights.dtype == torch.float32 and tuple(weights.shape) == (t_n, k) and weights.is_contiguous(),
+                 f"weights must be contiguous float32 [{t_n}, {k}]")
+    if out is None:
+        out = torch.empty((t_n, h), dtype=src.dtype, device=src.device)
+    else:
+        _require(tuple(out.shape) == (t_n, h) and out.is_contiguous(), f"out must be contiguous [{t_n}, {h}]")
+        _require(out.dtype in (src.dtype, torch.float32), "out must have src's dtype or float32")
+    with _device_guard(src, dest, out, *((weights,) if weights is not None else ())):
+        rc = _lib.lib().dga_combine_rows(src.data_ptr(), _CAST_DT[src.dtype], s_n, h, dest.data_ptr(),
+                                         weights.data_ptr() if weights is not None else None, t_n, k, out.data_ptr(), _CAST_DT[out.dtype],
+                                         _stream_ptr(src))
+        _lib.check(rc, "combine_tokens")
+        if sync:
+            torch.cuda.current_stream(src.device).synchronize()
+    return out
+
+
+def combine_tokens_weight_grad(src: torch.Tensor, grad: torch.Tensor, dest: torch.Tensor, out: Optional[torch.Tensor] = None,
+                               sync: bool = False) -> torch.Tensor:
+    """The gradient of combine_tokens with respect to its weights (dga_combine_rows_weight_grad): dw[t, j] = <src[dest[t, j]], grad[t]>,
+    float32 [T, k].  src [S, H] and grad [T, H] contiguous, of one dtype (float32 / bfloat16 / float16), dest int64 [T, k].  Products and
+    sums are float32 in a fixed order -- no floating-point atomics, two runs give the same bits --, |dw - exact| <= (H + 2) 2^-24 sum_c
+    |src grad|.  A choice whose dest is outside [0, S) gets +0; every element of dw is written; grad[t] is read once per 8 choices."""
+    s_n, h, t_n, k = _combine_layout("combine_tokens_weight_grad", src, dest)
+    _require(grad.dim() == 2 and tuple(grad.shape) == (t_n, h) and grad.is_contiguous(), f"grad must be contiguous [{t_n}, {h}]")
+    _require(grad.dtype == src.dtype, "grad must have src's dtype")
+    if out is None:
+        out = torch.empty((t_n, k), dtype=torch.float32, device=src.device)
+    else:
+        _require(out.dtype == torch.float32 and tuple(out.shape) == (t_n, k) and out.is_contiguous(),
+                 f"out must be contiguous float32 [{t_n}, {k}]")
+    with _device_guard(src, grad, dest, out):
+        if h == 0:
+            out.zero_()   # (the C entry touches nothing for an empty row)
+        rc = _lib.lib().dga_combine_rows_weight_grad(src.data_ptr(), grad.data_ptr(), _CAST_DT[src.dtype], s_n, h, dest.data_ptr(), t_n, k,
+                                                     out.data_ptr(), _stream_ptr(src))
+        _lib.check(rc, "combine_tokens_weight_grad")
+        if sync:
+            torch.cuda.current_stream(src.device).synchronize()
+    return out
 
 
 def _block_out(out, q_shape: tuple, sf_shape: tuple, device, q_name: str, sf_name: str):

@@ -1,7 +1,9 @@
-// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_cast_transposed_block.hip, dga_silu_mul_cast.hip, dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip).
+// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_cast_transposed_block.hip, dga_gather_cast_transposed.hip, dga_silu_mul_cast.hip,
+// dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip; dga_combine.hip takes the element types' loads and stores).
 // Device: the e4m3fn conversion, the 16-lane DPP row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition
 // (oracle/: quant_1x128); the bounded 8-element loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels'
-// row locator, refined sigmoid and silu(g) * u with its fp64-rounded block amax; the transposing kernels' row masks.  Host, at the end:
+// row locator, refined sigmoid and silu(g) * u with its fp64-rounded block amax; the transposing kernels' row masks and the gathering one's
+// table reads.  Host, at the end:
 // the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -326,6 +328,34 @@ __device__ __forceinline__ void rows_valid8(int64_t r0, int64_t t_n, int64_t mma
 #pragma unroll
         for (int p = 0; p < 8; ++p) ok[p] = r0 + p <= last;
     }
+}
+
+// ---- the gathering transposing quantiser (dga_gather_cast_transposed.hip): the rows of src behind a slot -> pair table
+
+// The 8 tokens r0 .. r0 + 7 whose mask answers are ok[] (rows_valid8): token p reads row index[r0 + p] / index_div of src, h elements a
+// row.  An index is read only where ok[p] -- the table holds stale values under the mask -- and a value outside [0, pairs) clears ok[p]:
+// nothing is dereferenced through it.  No branch between the 8 index reads nor between the 8 scale reads (SCALED: sc[p] =
+// row_scale[index], 0 where the row is excluded), so each set goes out together.  at[p] = the element index of column c0 of the row of
+// src, meaningful where ok[p].  small: pairs fits 32 bits, and with it every valid index and index_div (udiv).
+template <bool SCALED>
+__device__ __forceinline__ void gather_rows8(const int64_t *index, const float *row_scale, int64_t r0, int64_t pairs, int64_t index_div,
+                                             bool small, int64_t h, int64_t c0, bool (&ok)[8], int64_t (&at)[8], float (&sc)[8])
+{
+    int64_t ix[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        ix[p] = -1;
+        if (ok[p]) ix[p] = index[r0 + p];
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) ok[p] = (uint64_t)ix[p] < (uint64_t)pairs;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        sc[p] = 0.f;
+        if (SCALED && ok[p]) sc[p] = row_scale[ix[p]];
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) at[p] = (index_div == 1 ? ix[p] : udiv(ok[p] ? ix[p] : 0, index_div, small)) * h + c0;
 }
 
 // ---- host side: what the three units' launchers share

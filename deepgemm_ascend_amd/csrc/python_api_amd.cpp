@@ -475,6 +475,89 @@ std::tuple<at::Tensor, at::Tensor> per_block_cast_to_fp8_transposed(const at::Te
     return {qt, sft};
 }
 
+// The 16-bit / fp32 element types of the quantisers and the combine -> DGA_DT_*
+int cast_dtype(const at::Tensor &t, const char *what)
+{
+    const at::ScalarType st = t.scalar_type();
+    TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, what, " must be float32 / bfloat16 / float16");
+    return st == at::kFloat ? DGA_DT_FP32 : st == at::kBFloat16 ? DGA_DT_BF16 : DGA_DT_FP16;
+}
+
+// per_token_cast_to_fp8_transposed of the rows src[index[r] / index_div] (times row_scale[index[r]]) in one pass
+// (dga_gather_cast_to_fp8_1x128_transposed): src [S, H], index int64 [T] -> (qt [H, T], sft [H, ceil(T/128)]); a row whose index is outside
+// [0, S * index_div) is not read and counts as zeros.
+std::tuple<at::Tensor, at::Tensor> gather_per_token_cast_to_fp8_transposed(const at::Tensor &src, const at::Tensor &index, int64_t index_div,
+                                                                           const c10::optional<at::Tensor> &row_scale)
+{
+    on_device(src, "src"); on_device(index, "index");
+    TORCH_CHECK(src.dim() == 2 && src.is_contiguous(), "src must be a contiguous [S, H] tensor");
+    const int dt = cast_dtype(src, "src");
+    TORCH_CHECK(index.scalar_type() == at::kLong && index.dim() == 1 && index.is_contiguous(), "index must be a contiguous int64 [T] tensor");
+    TORCH_CHECK(index.device() == src.device(), "all tensors must live on one device");
+    TORCH_CHECK(index_div >= 1, "index_div must be >= 1");
+    const int64_t s_n = src.size(0), h = src.size(1), t_n = index.size(0);
+    if (row_scale.has_value()) {
+        on_device(*row_scale, "row_scale");
+        TORCH_CHECK(row_scale->scalar_type() == at::kFloat && row_scale->numel() == s_n * index_div && row_scale->is_contiguous(),
+                    "row_scale must be contiguous float32 with S * index_div elements");
+        TORCH_CHECK(row_scale->device() == src.device(), "all tensors must live on one device");
+    }
+    const c10::OptionalDeviceGuard guard(at::device_of(src));
+    at::Tensor qt = at::empty({h, t_n}, src.options().dtype(at::kFloat8_e4m3fn));
+    at::Tensor sft = at::empty({h, (t_n + 127) / 128}, src.options().dtype(at::kFloat));
+    check(dga_gather_cast_to_fp8_1x128_transposed(src.data_ptr(), dt, s_n, h, index.data_ptr<int64_t>(), index_div,
+                                                  row_scale.has_value() ? row_scale->data_ptr<float>() : nullptr, 1, t_n, nullptr,
+                                                  qt.data_ptr(), t_n, sft.data_ptr<float>(), nullptr, nullptr, 0, cur_stream()),
+          "gather_per_token_cast_to_fp8_transposed");
+    return {qt, sft};
+}
+
+// y[t] = sum_j weights[t, j] * src[dest[t, j]] (dga_combine_rows): src [S, H], dest int64 [T, k], weights float32 [T, k] or None -> y [T, H] of
+// src's dtype; a dest outside [0, S) is skipped.
+void combine_layout(const at::Tensor &src, const at::Tensor &dest)
+{
+    on_device(src, "src"); on_device(dest, "dest");
+    TORCH_CHECK(src.dim() == 2 && src.is_contiguous(), "src must be a contiguous [S, H] tensor");
+    TORCH_CHECK(dest.scalar_type() == at::kLong && dest.dim() == 2 && dest.is_contiguous() && dest.size(1) >= 1,
+                "dest must be a contiguous int64 [T, k] tensor with k >= 1");
+    TORCH_CHECK(dest.device() == src.device(), "all tensors must live on one device");
+}
+at::Tensor combine_tokens(const at::Tensor &src, const at::Tensor &dest, const c10::optional<at::Tensor> &weights)
+{
+    combine_layout(src, dest);
+    const int dt = cast_dtype(src, "src");
+    if (weights.has_value()) {
+        on_device(*weights, "weights");
+        TORCH_CHECK(weights->scalar_type() == at::kFloat && weights->sizes() == dest.sizes() && weights->is_contiguous(),
+                    "weights must be contiguous float32 [T, k]");
+        TORCH_CHECK(weights->device() == src.device(), "all tensors must live on one device");
+    }
+    const c10::OptionalDeviceGuard guard(at::device_of(src));
+    at::Tensor out = at::empty({dest.size(0), src.size(1)}, src.options());
+    check(dga_combine_rows(src.data_ptr(), dt, src.size(0), src.size(1), dest.data_ptr<int64_t>(),
+                           weights.has_value() ? weights->data_ptr<float>() : nullptr, dest.size(0), dest.size(1), out.data_ptr(), dt,
+                           cur_stream()),
+          "combine_tokens");
+    return out;
+}
+
+// dw[t, j] = <src[dest[t, j]], grad[t]> (dga_combine_rows_weight_grad): float32 [T, k], +0 for a dest outside [0, S).
+at::Tensor combine_tokens_weight_grad(const at::Tensor &src, const at::Tensor &grad, const at::Tensor &dest)
+{
+    combine_layout(src, dest);
+    const int dt = cast_dtype(src, "src");
+    on_device(grad, "grad");
+    TORCH_CHECK(grad.dim() == 2 && grad.size(0) == dest.size(0) && grad.size(1) == src.size(1) && grad.is_contiguous() &&
+                grad.scalar_type() == src.scalar_type(), "grad must be contiguous [T, H] of src's dtype");
+    TORCH_CHECK(grad.device() == src.device(), "all tensors must live on one device");
+    const c10::OptionalDeviceGuard guard(at::device_of(src));
+    at::Tensor dw = src.size(1) == 0 ? at::zeros(dest.sizes(), src.options().dtype(at::kFloat)) : at::empty(dest.sizes(), src.options().dtype(at::kFloat));
+    check(dga_combine_rows_weight_grad(src.data_ptr(), grad.data_ptr(), dt, src.size(0), src.size(1), dest.data_ptr<int64_t>(), dest.size(0),
+                                       dest.size(1), dw.data_ptr<float>(), cur_stream()),
+          "combine_tokens_weight_grad");
+    return dw;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.cpp:30)
@@ -508,5 +591,9 @@ PYBIND11_MODULE(deep_gemm_cpp, m)   // the reference's module name (python_api.c
     m.def("silu_and_mul_per_token_cast_to_fp8_transposed", &silu_and_mul_per_token_cast_to_fp8_transposed, py::arg("x"),
           py::arg("m_indices") = py::none());
     m.def("per_block_cast_to_fp8_transposed", &per_block_cast_to_fp8_transposed, py::arg("w"));
+    m.def("gather_per_token_cast_to_fp8_transposed", &gather_per_token_cast_to_fp8_transposed, py::arg("src"), py::arg("index"),
+          py::arg("index_div") = 1, py::arg("row_scale") = py::none());
+    m.def("combine_tokens", &combine_tokens, py::arg("src"), py::arg("dest"), py::arg("weights") = py::none());
+    m.def("combine_tokens_weight_grad", &combine_tokens_weight_grad, py::arg("src"), py::arg("grad"), py::arg("dest"));
     m.def("abi_version", [] { return dga_abi_version(); });
 }

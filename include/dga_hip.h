@@ -500,6 +500,29 @@ int dga_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_t groups,
                                      void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
                                      int flags, void *stream);
 
+/* The same quantiser with the rows read through a table -- the dispatch of an MoE layer fused into the quantiser, driven by
+ * dga_route_slots' slot -> pair table (`inverse`) as it is:
+ *   xg[r] = src[index[r] / index_div]                                        (row_scale == NULL; xg has src_dtype)
+ *   xg[r] = fl32(row_scale[index[r]] * fl32(src[index[r] / index_div]))      (row_scale: fp32 [src_rows * index_div]; xg is fp32;
+ *                                                                             one multiplication, no special cases)
+ * src [src_rows, h] contiguous of src_dtype (as above), index int64 [groups, rows], T = groups * rows, P = src_rows * index_div the number
+ * of (token, choice) pairs.  Row r is valid iff masked_m does not exclude it and 0 <= index[r] < P.  An index that masked_m excludes is NOT
+ * READ (dga_route_slots leaves stale values there); a value outside [0, P) excludes the row and dereferences nothing.  The result is
+ * dga_cast_to_fp8_1x128_transposed's on xg with the excluded rows masked, byte for byte and bit for bit, and that entry's contract carries
+ * over: an excluded row counts as zeros and is never read, every byte of qt [h, T] (rows ldqt bytes apart) and every scale of sft is
+ * written, a 128-token block without a valid row has scale 1, and (q_row, sf_row) -- both NULL or both set -- are written on the valid rows
+ * only.  xg itself is never written.  The uses on dga_route_slots(keys = the top-k ids, cap = rows): index = inverse, index_div = k,
+ * masked_m = counts for the forward's lhs; the same with src = dY and row_scale = the routing weights for the backward's; groups = 1 and
+ * index with -1 on the padding rows for the contiguous layout.  flags: DGA_CAST_UE8M0.  Checks, in dga_cast_to_fp8_1x128_transposed's
+ * order: DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a negative size, groups < 1, index_div < 1, src_rows * index_div beyond int64,
+ * groups != 1 without masked_m, ldqt outside its range, exactly one of q_row / sf_row;  T == 0 or h == 0 is DGA_OK with nothing touched;
+ * then DGA_E_NULL (src unless src_rows == 0, index, qt, sft), DGA_E_DTYPE, and DGA_E_RANGE for more 128 x 128 tiles than one grid holds
+ * or src_rows * h beyond int64. */
+int dga_gather_cast_to_fp8_1x128_transposed(const void *src, int src_dtype, int64_t src_rows, int64_t h, const int64_t *index,
+                                            int64_t index_div, const float *row_scale, int64_t groups, int64_t rows,
+                                            const int32_t *masked_m, void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
+                                            int flags, void *stream);
+
 /* The same quantiser on h = silu(gate) * up -- the operand of the weight gradient of an expert MLP's second GEMM, dW2[g] = dout_g^T . h_g,
  * from the tensor dga_silu_mul_cast_to_fp8_1x128 read, in one pass and without h ever leaving fp32 registers:
  *   (qt, sft) = cast_to_fp8_1x128_ex( where(valid, silu(gate) * up, 0)^T ),
@@ -603,6 +626,29 @@ int dga_copy_rows(void *dst, int64_t dst_row_stride, const int64_t *dst_index, c
 int dga_copy_rows2(void *dst0, int64_t dst0_row_stride, const void *src0, int64_t src0_row_stride, int64_t row_bytes0,
                    void *dst1, int64_t dst1_row_stride, const void *src1, int64_t src1_row_stride, int64_t row_bytes1,
                    const int64_t *dst_index, const int64_t *src_index, int64_t rows, void *stream);
+
+/* The combine of an MoE layer on dga_route_slots' pair -> slot table (dest int64 [tokens, k], k >= 1; a dropped choice holds -1):
+ *   acc = +0;  for j = 0 .. k - 1 in that order, where 0 <= dest[t, j] < src_rows:
+ *       acc = fl32(acc + fl32(weights[t, j] * fl32(src[dest[t, j], c])))       (two roundings, never a fused multiply-add;
+ *                                                                                weights == NULL: the product is the value itself)
+ *   out[t, c] = RNE(acc)
+ * src [src_rows, h] contiguous of src_dtype (DGA_DT_FP32 / BF16 / FP16), weights fp32 [tokens, k] or NULL, out [tokens, h] contiguous of
+ * out_dtype = src_dtype or DGA_DT_FP32.  A choice whose dest is outside [0, src_rows) is skipped whatever its weight, a token without a
+ * valid choice gets a row of +0, and every element of out is written.  This is float32 arithmetic in a stated order: a host reference
+ * reproduces it bit for bit.  weights == NULL is the backward of the dispatch, dX[t] = sum_j dX_slots[dest[t, j]].  One pass: every valid
+ * choice's row is read once and out is written once.  DGA_E_SHAPE: a negative size, k < 1, tokens * k beyond int64;  tokens == 0 or h == 0
+ * is DGA_OK with nothing touched;  then DGA_E_NULL (src unless src_rows == 0, dest, out), DGA_E_DTYPE, and DGA_E_RANGE for k beyond
+ * 2^31 - 1, rows * h beyond int64 or more workgroups than one grid holds. */
+int dga_combine_rows(const void *src, int src_dtype, int64_t src_rows, int64_t h, const int64_t *dest, const float *weights,
+                     int64_t tokens, int64_t k, void *out, int out_dtype, void *stream);
+
+/* The gradient of the combine with respect to its weights: dw[t, j] = sum_c src[dest[t, j], c] * grad[t, c], fp32 [tokens, k], products and
+ * sums in fp32 in a fixed order (no floating-point atomics: two runs on the same inputs give the same bits), +0 for a choice whose dest is
+ * outside [0, src_rows).  src [src_rows, h] and grad [tokens, h] contiguous of `dtype`; grad[t] is read once for every 8 choices of a
+ * token.  Every element of dw is written.  Checks as in dga_combine_rows (DGA_E_NULL: src unless src_rows == 0, grad, dest, dw); h == 0 is
+ * DGA_OK with nothing touched, dw included. */
+int dga_combine_rows_weight_grad(const void *src, const void *grad, int dtype, int64_t src_rows, int64_t h, const int64_t *dest,
+                                 int64_t tokens, int64_t k, float *dw, void *stream);
 
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
