@@ -3,10 +3,10 @@ $DGA_B16_PLAN): the operator (catlass_dynamic_matmul, NT, 16-bit out; reference 
 /root/reference/aclnn_catlass_dynamic_matmul/op_kernel/catlass_dynamic_matmul.cpp:16-45) and run_mmad_rtc (y [K,N], f32 out;
 /root/reference/deep_gemm_ascend/framework/csrc/jit_kernels/impls/gemm.hpp:68-111) against the fp32 matmul of the same 16-bit values.
 (The 256x256 tile's continuous loop once ignored its K slice: a plan with that tile and split-K summed the whole K once per slice.)"""
-import os
-
 import pytest
 import torch
+
+from b16_cases import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -16,18 +16,8 @@ SPLITS = [1, 2, 3, 5]
 
 def _with_plan(plan, fn, deep=None):
     """deep: $DGA_B16_DEEP -- the four-stage build of a tile of at most 64 rows forced on ("1") or off ("0")."""
-    old = {k: os.environ.get(k) for k in ("DGA_B16_PLAN", "DGA_B16_DEEP")}
-    try:
-        os.environ["DGA_B16_PLAN"] = plan
-        if deep is not None:
-            os.environ["DGA_B16_DEEP"] = deep
+    with switches(plan=plan, deep=deep):
         return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

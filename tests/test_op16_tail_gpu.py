@@ -2,24 +2,17 @@
 gemm_b16_kernel.hpp `tail_sub`): the purpose of the reference's Stream-K handler (wave quantisation,
 /root/reference/aclnn_catlass_dynamic_matmul/op_host/op_tiling/select_kernel.cpp:303-331) without partial sums -- every output
 still comes from one accumulation in k order, so the bytes are those of the single launch."""
-import os
-
 import pytest
 import torch
+
+from b16_cases import switches
 
 pytestmark = pytest.mark.gpu
 
 
 def _with_plan(plan, fn):
-    old = os.environ.get("DGA_B16_PLAN")
-    try:
-        os.environ["DGA_B16_PLAN"] = plan
+    with switches(plan=plan):
         return fn()
-    finally:
-        if old is None:
-            os.environ.pop("DGA_B16_PLAN", None)
-        else:
-            os.environ["DGA_B16_PLAN"] = old
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

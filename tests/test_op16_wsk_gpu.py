@@ -9,24 +9,17 @@ import numpy as np
 import pytest
 import torch
 
+from b16_cases import switches
+
 pytestmark = pytest.mark.gpu
 
 
 def _run(dga, x, w, wsk):
     m, n = x.shape[0], w.shape[0]
     out = torch.full((m, n), float("nan"), dtype=x.dtype, device="cuda")
-    old = {k: os.environ.get(k) for k in ("DGA_B16_WSK", "DGA_B16_PLAN")}
-    try:
-        os.environ["DGA_B16_WSK"] = "1" if wsk else "0"
-        if not wsk:   # the tile kernel with K cut eight ways + the combine kernel
-            os.environ["DGA_B16_PLAN"] = "16,128,8" if m <= 16 else "32,128,8"
+    # not wsk: the tile kernel with K cut eight ways + the combine kernel
+    with switches(wsk="1" if wsk else "0", plan=None if wsk else ("16,128,8" if m <= 16 else "32,128,8")):
         dga.catlass_dynamic_matmul(x, w.t(), out, sync=True)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     return out
 
 
