@@ -63,6 +63,8 @@ BUILD_DEFAULT, BUILD_WSK_REGISTER, BUILD_BX_AIMAGE, BUILD_BX_IMAGE8, BUILD_BX_IM
 BUILD_BX_PERSISTENT, BUILD_BX_ONE_TILE, BUILD_BX_GROUPED, BUILD_BX_DECODE = 7, 8, 9, 10
 ROWS_A_ZERO_PADDED, ROWS_B_ZERO_PADDED = 1, 2   # dga_gemm_fp8_fp8_bf16_nt_strided flags
 CAST_UE8M0 = 1                                  # dga_cast_to_fp8_*_ex flag: block scales rounded up to powers of two
+ROUTER_SOFTMAX, ROUTER_SIGMOID = 0, 1           # dga_router_topk score_func
+ROUTER_RENORMALIZE = 1                          # dga_router_topk flag
 CONTIGUOUS_M_ALIGNMENT = 128
 
 
@@ -157,6 +159,10 @@ SIGNATURES = {
                                                 c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_combine_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "dga_combine_rows_weight_grad": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "dga_router_topk": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "dga_router_topk_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_float, c_void_p, c_int,
+                                         c_void_p]),
     "dga_catlass_dynamic_matmul_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "dga_catlass_dynamic_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                            c_void_p]),

@@ -1261,6 +1261,92 @@ def combine_tokens_weight_grad(src: torch.Tensor, grad: torch.Tensor, dest: torc
     return out
 
 
+_SCORE_FUNCS = {"softmax": _lib.ROUTER_SOFTMAX, "sigmoid": _lib.ROUTER_SIGMOID}
+
+
+def _router_func(score_func) -> int:
+    _require(score_func in _SCORE_FUNCS, 'score_func must be "softmax" or "sigmoid"')
+    return _SCORE_FUNCS[score_func]
+
+
+def router_topk(logits: torch.Tensor, k: int, score_func: str = "softmax", bias: Optional[torch.Tensor] = None, n_groups: int = 1,
+                topk_groups: int = 1, renormalize: bool = True, scale: float = 1.0, out=None, sync: bool = False):
+    """The gate of an MoE layer in one launch (dga_router_topk): logits [T, E] contiguous float32 / bfloat16 / float16 ->
+    (ids int32 [T, k], weights float32 [T, k], scores float32 [T, E]).  1 <= k <= E <= 1024, k <= 64, E % n_groups == 0,
+    1 <= topk_groups <= n_groups, topk_groups * (E / n_groups) >= k, groups of at least two experts when n_groups > 1.
+    scores = softmax(logits) or sigmoid(logits) row by row, in float32 against float64: |p - p64| <= (E + 128) 2^-24 p64 where
+    |x_i - max x| <= 16 (softmax), |s - s64| <= 2^-18 s64 where |x| <= 16 (sigmoid).  ids and weights are exact float32 functions of the
+    scores returned, so a numpy float32 reference on those scores matches bit for bit: sel = fl32(scores + bias) (bias float32 [E],
+    DeepSeek-V3's correction bias: selection only; a NaN sel counts as -inf); comparisons are IEEE >, equal values tie and the lower index
+    wins; with n_groups > 1 a group's value is fl32(largest sel + second largest sel) of its experts, the topk_groups largest groups stay
+    (ties: the lower group) and no expert of another group is chosen; ids[t] = the k largest sel of what may be chosen, in descending
+    order -- always k distinct values in [0, E), whatever the logits hold; r_j = scores[t, ids[t, j]]; renormalize:
+    D = ((r_0 + r_1) + ...) + r_{k-1}, w_j = fl32(fl32(r_j / D) * scale), else w_j = fl32(r_j * scale).  A row with a NaN or +inf, or
+    of nothing but -inf, may give NaN scores and weights.  out=(ids, weights, scores) takes the caller's tensors; every element of all three
+    is written.  ids.view(-1) is route_slots' keys (key_stride_bytes=4), weights feeds combine_tokens and row_scale=weights.view(-1) as it
+    is, scores is what router_topk_backward (and a balance loss) reads.  Nothing depends on the host: a captured graph follows the logits."""
+    _require(logits.dim() == 2 and logits.is_contiguous(), "logits must be a contiguous [T, E] tensor")
+    _require(logits.dtype in _CAST_DT, "logits must be float32, bfloat16 or float16")
+    func = _router_func(score_func)
+    _require(all(isinstance(v, int) for v in (k, n_groups, topk_groups)), "k, n_groups and topk_groups must be integers")
+    t_n, e = logits.shape
+    if bias is not None:
+        _require(bias.dtype == torch.float32 and tuple(bias.shape) == (e,) and bias.is_contiguous(), f"bias must be contiguous float32 [{e}]")
+    if out is None:
+        _require(k >= 1, "k must be >= 1")
+        ids = torch.empty((t_n, k), dtype=torch.int32, device=logits.device)
+        weights = torch.empty((t_n, k), dtype=torch.float32, device=logits.device)
+        scores = torch.empty((t_n, e), dtype=torch.float32, device=logits.device)
+    else:
+        _require(isinstance(out, (tuple, list)) and len(out) == 3 and all(isinstance(t, torch.Tensor) for t in out),
+                 "out must hold (ids, weights, scores)")
+        ids, weights, scores = out
+        _require(ids.dtype == torch.int32 and tuple(ids.shape) == (t_n, k) and ids.is_contiguous(), f"out ids must be contiguous int32 [{t_n}, {k}]")
+        _require(weights.dtype == torch.float32 and tuple(weights.shape) == (t_n, k) and weights.is_contiguous(),
+                 f"out weights must be contiguous float32 [{t_n}, {k}]")
+        _require(scores.dtype == torch.float32 and tuple(scores.shape) == (t_n, e) and scores.is_contiguous(),
+                 f"out scores must be contiguous float32 [{t_n}, {e}]")
+    with _device_guard(logits, ids, weights, scores, *((bias,) if bias is not None else ())):
+        rc = _lib.lib().dga_router_topk(logits.data_ptr(), _CAST_DT[logits.dtype], t_n, e, k, func, bias.data_ptr() if bias is not None else None,
+                                        n_groups, topk_groups, _lib.ROUTER_RENORMALIZE if renormalize else 0, float(scale), ids.data_ptr(),
+                                        weights.data_ptr(), scores.data_ptr(), _stream_ptr(logits))
+        _lib.check(rc, "router_topk")
+        if sync:
+            torch.cuda.current_stream(logits.device).synchronize()
+    return ids, weights, scores
+
+
+def router_topk_backward(dw: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, score_func: str, renormalize: bool = True,
+                         scale: float = 1.0, out: Optional[torch.Tensor] = None, sync: bool = False) -> torch.Tensor:
+    """The backward of router_topk (dga_router_topk_backward): dw float32 [T, k] (combine_tokens_weight_grad's output), scores float32
+    [T, E] and ids int32 [T, k] as the forward wrote them -> dlogits [T, E], float32 by default or bfloat16 / float16 through out (rounded
+    to nearest even); every element is written.  bias and the choice of groups get no gradient.  With r_j = scores[t, ids[t, j]] and D, w
+    as in the forward: g_j = (scale dw_j - sum_l dw_l w_l) / D with renormalize, else scale dw_j; ds_i = g_j at i = ids[t, j], else 0;
+    sigmoid: dlogits_i = ds_i s_i (1 - s_i), +0 off the selection; softmax: dlogits_i = s_i (ds_i - sum_l ds_l s_l).  float32 in a fixed
+    order without atomics -- two runs give the same bits --, |dlogits - ref64| <= (E + k + 8) 2^-24 M against float64 on the same scores,
+    M the same expression with every term replaced by its absolute value and (1 - s_i) by 1."""
+    func = _router_func(score_func)
+    _require(scores.dtype == torch.float32 and scores.dim() == 2 and scores.is_contiguous(), "scores must be a contiguous float32 [T, E] tensor")
+    t_n, e = scores.shape
+    _require(ids.dtype == torch.int32 and ids.dim() == 2 and ids.shape[0] == t_n and ids.is_contiguous(),
+             f"ids must be a contiguous int32 [{t_n}, k] tensor")
+    k = ids.shape[1]
+    _require(dw.dtype == torch.float32 and tuple(dw.shape) == (t_n, k) and dw.is_contiguous(), f"dw must be contiguous float32 [{t_n}, {k}]")
+    if out is None:
+        out = torch.empty((t_n, e), dtype=torch.float32, device=scores.device)
+    else:
+        _require(out.dtype in _CAST_DT and tuple(out.shape) == (t_n, e) and out.is_contiguous(),
+                 f"out must be contiguous [{t_n}, {e}], float32, bfloat16 or float16")
+    with _device_guard(dw, scores, ids, out):
+        rc = _lib.lib().dga_router_topk_backward(dw.data_ptr(), scores.data_ptr(), ids.data_ptr(), t_n, e, k, func,
+                                                 _lib.ROUTER_RENORMALIZE if renormalize else 0, float(scale), out.data_ptr(),
+                                                 _CAST_DT[out.dtype], _stream_ptr(scores))
+        _lib.check(rc, "router_topk_backward")
+        if sync:
+            torch.cuda.current_stream(scores.device).synchronize()
+    return out
+
+
 def _block_out(out, q_shape: tuple, sf_shape: tuple, device, q_name: str, sf_name: str):
     """_fused_out for the weight quantiser, whose codes and scales do not share their leading dimensions: (q q_shape bytes, sf sf_shape
     float32), torch.empty or the caller's out=(q, sf) checked."""

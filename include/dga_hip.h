@@ -650,6 +650,48 @@ int dga_combine_rows(const void *src, int src_dtype, int64_t src_rows, int64_t h
 int dga_combine_rows_weight_grad(const void *src, const void *grad, int dtype, int64_t src_rows, int64_t h, const int64_t *dest,
                                  int64_t tokens, int64_t k, float *dw, void *stream);
 
+/* The gate of an MoE layer in one launch: logits [tokens, experts] contiguous of logits_dtype (DGA_DT_FP32 / BF16 / FP16; the 16-bit
+ * types convert exactly) -> scores fp32 [tokens, experts], ids int32 [tokens, k], weights fp32 [tokens, k]; every element of the three is
+ * written.  ids is what dga_route_slots takes as keys (key_stride_bytes 4, pair t * k + j), weights what dga_combine_rows and the
+ * gathering quantiser's row_scale take, scores what dga_router_topk_backward and a balance loss read.  Two contracts:
+ *  (1) scores, against float64.  DGA_ROUTER_SOFTMAX: m = max x (exact), e_i = exp(x_i - m), p_i = e_i / sum e,
+ *      |p - p64| <= (experts + 128) 2^-24 p64 where |x_i - m| <= 16.  DGA_ROUTER_SIGMOID: s = 1 / (1 + exp(-x)),
+ *      |s - s64| <= 2^-18 s64 where |x| <= 16.  A row that holds a NaN or +inf, or nothing but -inf, may give NaN scores and weights.
+ *  (2) ids and weights are exact fp32 functions of the scores written, which a host reference in float32 reproduces bit for bit:
+ *      sel_i = fl32(scores_i + bias_i) (bias fp32 [experts], selection only; NULL: sel_i = scores_i); a NaN sel counts as -inf.
+ *      Comparisons are IEEE >: equal values (+0 and -0 too) tie, and the lower index wins.  n_groups > 1 (DeepSeek-V3's group-limited
+ *      routing): the experts form n_groups consecutive groups; a group's value is fl32(largest sel + second largest sel) of the group
+ *      (a NaN value counts as -inf); the topk_groups groups of largest value stay, ties to the lower group; no expert of another group is
+ *      chosen.  ids[t, 0 .. k-1] = the k largest sel among the experts that may be chosen, in descending order, ties to the lower index:
+ *      always k distinct values in [0, experts), whatever the logits hold.  r_j = scores[t, ids[t, j]] (no bias in a weight).
+ *      DGA_ROUTER_RENORMALIZE: D = ((r_0 + r_1) + ...) + r_{k-1} in that order, w_j = fl32(fl32(r_j / D) * scale), the division
+ *      correctly rounded; else w_j = fl32(r_j * scale).
+ * One wave per token, the row in registers, wave reductions only: no LDS, no atomics, nothing read back -- capturable.  It moves
+ * experts * (input bytes + 4) + 8 k bytes per token, once.
+ * DGA_E_SHAPE: a negative size, k < 1, k > experts, n_groups < 1, experts % n_groups != 0, topk_groups outside [1, n_groups],
+ * topk_groups * (experts / n_groups) < k, n_groups > 1 with groups of one expert;  tokens == 0 is DGA_OK with nothing touched;  then
+ * DGA_E_NULL (logits, ids, weights, scores), DGA_E_DTYPE, and DGA_E_RANGE for experts > DGA_ROUTER_MAX_EXPERTS, k > DGA_ROUTER_MAX_TOPK,
+ * an unknown score_func or flag, or more tokens than one grid holds (4 (2^31 - 1)). */
+enum { DGA_ROUTER_SOFTMAX = 0, DGA_ROUTER_SIGMOID = 1 };   /* score_func */
+#define DGA_ROUTER_RENORMALIZE 1                           /* flags */
+#define DGA_ROUTER_MAX_EXPERTS 1024
+#define DGA_ROUTER_MAX_TOPK 64
+int dga_router_topk(const void *logits, int logits_dtype, int64_t tokens, int64_t experts, int64_t k, int score_func, const float *bias,
+                    int64_t n_groups, int64_t topk_groups, int flags, float scale, int32_t *ids, float *weights, float *scores,
+                    void *stream);
+
+/* The backward of dga_router_topk: dw fp32 [tokens, k] (dga_combine_rows_weight_grad's output), scores and ids as the forward wrote them
+ * -> dlogits [tokens, experts] of dlogits_dtype (DGA_DT_FP32, or a 16-bit type rounded to nearest even); every element is written.  The
+ * bias and the choice of groups get no gradient.  r_j = scores[t, ids[t, j]], D and w_j as in the forward,
+ *   g_j = (scale dw_j - sum_l dw_l w_l) / D   (DGA_ROUTER_RENORMALIZE;  else g_j = scale dw_j),   ds_i = g_j at i = ids[t, j], else 0
+ *   DGA_ROUTER_SIGMOID: dlogits_i = ds_i s_i (1 - s_i), +0 off the selection;   DGA_ROUTER_SOFTMAX: dlogits_i = s_i (ds_i - sum_l ds_l s_l).
+ * fp32 in a fixed order, no floating-point atomics: two runs give the same bits.  Against float64 on the same fp32 scores:
+ * |dlogits - ref64| <= (experts + k + 8) 2^-24 M, M the same expression with every term replaced by its absolute value and (1 - s_i) by 1.
+ * An id outside [0, experts) reads nothing and contributes nothing.  Checks as in dga_router_topk (no group conditions; DGA_E_NULL: dw,
+ * scores, ids, dlogits). */
+int dga_router_topk_backward(const float *dw, const float *scores, const int32_t *ids, int64_t tokens, int64_t experts, int64_t k,
+                             int score_func, int flags, float scale, void *dlogits, int dlogits_dtype, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
