@@ -65,6 +65,7 @@ ROWS_A_ZERO_PADDED, ROWS_B_ZERO_PADDED = 1, 2   # dga_gemm_fp8_fp8_bf16_nt_strid
 CAST_UE8M0 = 1                                  # dga_cast_to_fp8_*_ex flag: block scales rounded up to powers of two
 ROUTER_SOFTMAX, ROUTER_SIGMOID = 0, 1           # dga_router_topk score_func
 ROUTER_RENORMALIZE = 1                          # dga_router_topk flag
+ROUTER_BALANCE_NORMALIZE = 1                    # dga_router_balance_loss flag
 CONTIGUOUS_M_ALIGNMENT = 128
 
 
@@ -163,6 +164,12 @@ SIGNATURES = {
                                 c_void_p, c_void_p]),
     "dga_router_topk_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_float, c_void_p, c_int,
                                          c_void_p]),
+    "dga_router_balance_loss_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "dga_router_balance_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "dga_router_balance_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_float,
+                                                 c_void_p, c_void_p, c_int, c_void_p]),
+    "dga_router_bias_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p]),
     "dga_catlass_dynamic_matmul_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "dga_catlass_dynamic_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                            c_void_p]),

@@ -1347,6 +1347,114 @@ def router_topk_backward(dw: torch.Tensor, scores: torch.Tensor, ids: torch.Tens
     return out
 
 
+def _balance_shape(scores: torch.Tensor, k, seq_len, alpha) -> Tuple[int, int, int, int, float]:
+    """The checks the balance entries share -> (T, E, L, B, coef); coef = alpha E / (k L^2), formed in double."""
+    _require(scores.dtype == torch.float32 and scores.dim() == 2 and scores.is_contiguous(), "scores must be a contiguous float32 [T, E] tensor")
+    t_n, e = scores.shape
+    seq = (t_n if t_n else 1) if seq_len is None else seq_len
+    _require(isinstance(k, int) and isinstance(seq, int) and k >= 1 and seq >= 1, "k and seq_len must be integers >= 1")
+    _require(t_n % seq == 0, f"seq_len must divide the {t_n} tokens")
+    return t_n, e, seq, t_n // seq, float(alpha) * e / (float(k) * seq * seq)
+
+
+def router_balance_loss_workspace_bytes(tokens: int, experts: int, seq_len: Optional[int] = None) -> int:
+    """Bytes of scratch router_balance_loss takes for this shape (dga_router_balance_loss_workspace_bytes): 8 B chunks E, one float32 and
+    one int32 partial [E] for each chunk of max(16, 4 ceil(T / 2048)) consecutive tokens of each of the B = T / seq_len segments."""
+    return int(_lib.lib().dga_router_balance_loss_workspace_bytes(tokens, experts, tokens if seq_len is None else seq_len))
+
+
+def router_balance_loss(scores: torch.Tensor, ids: torch.Tensor, seq_len: Optional[int] = None, alpha: float = 1.0, normalize: bool = False,
+                        out=None, sync: bool = False):
+    """The load-balancing loss of a router on router_topk's outputs (dga_router_balance_loss): scores float32 [T, E], ids int32 [T, k] ->
+    (loss float32 [B], counts int32 [B, E], psum float32 [B, E]) over B = T / seq_len segments of seq_len consecutive tokens (the default,
+    seq_len = T, is Switch / GShard's global loss; seq_len = a sequence's length is DeepSeek-V3's sequence-wise loss).  For segment b:
+    counts[b, e] = the pairs (t, j) of the segment with ids[t, j] == e, exact (an id outside [0, E) counts nowhere); p[t, e] =
+    scores[t, e] / sum_e scores[t, e] with normalize, else scores[t, e]; psum[b, e] = sum_t p[t, e]; loss[b] = coef sum_e counts psum
+    with coef = alpha E / (k seq_len^2) -- alpha sum_e f_e P_e, f_e = E / (k L) counts, P_e = psum / L.  In float32 against float64 on
+    the same scores, u = 2^-24, gamma(n) = n u / (1 - n u): |psum - P64| <= gamma(L + E + 1) P64, |loss - loss64| <= gamma(L + 2 E + 4)
+    loss64.  A NaN score makes its own segment's loss NaN and touches no other.  Fixed-order sums, no floating-point atomics: two runs give
+    the same bits.  out=(loss, counts, psum) takes the caller's tensors; every element of all three is written.  Nothing depends on the
+    host: the entry can be captured.  1 <= k <= E <= 1024, k <= 64."""
+    _require(ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous(), "ids must be a contiguous int32 [T, k] tensor")
+    t_n, e, seq, b_n, coef = _balance_shape(scores, ids.shape[1], seq_len, alpha)
+    _require(ids.shape[0] == t_n, f"ids must hold {t_n} rows")
+    if out is None:
+        loss = torch.empty((b_n,), dtype=torch.float32, device=scores.device)
+        counts = torch.empty((b_n, e), dtype=torch.int32, device=scores.device)
+        psum = torch.empty((b_n, e), dtype=torch.float32, device=scores.device)
+    else:
+        _require(isinstance(out, (tuple, list)) and len(out) == 3 and all(isinstance(t, torch.Tensor) for t in out),
+                 "out must hold (loss, counts, psum)")
+        loss, counts, psum = out
+        _require(loss.dtype == torch.float32 and tuple(loss.shape) == (b_n,) and loss.is_contiguous(), f"out loss must be contiguous float32 [{b_n}]")
+        _require(counts.dtype == torch.int32 and tuple(counts.shape) == (b_n, e) and counts.is_contiguous(),
+                 f"out counts must be contiguous int32 [{b_n}, {e}]")
+        _require(psum.dtype == torch.float32 and tuple(psum.shape) == (b_n, e) and psum.is_contiguous(),
+                 f"out psum must be contiguous float32 [{b_n}, {e}]")
+    with _device_guard(scores, ids, loss, counts, psum):
+        L = _lib.lib()
+        ws_ptr, ws_bytes = _scratch("balance", scores.device, int(L.dga_router_balance_loss_workspace_bytes(t_n, e, seq)))
+        rc = L.dga_router_balance_loss(scores.data_ptr(), ids.data_ptr(), t_n, e, ids.shape[1], seq,
+                                       _lib.ROUTER_BALANCE_NORMALIZE if normalize else 0, coef, loss.data_ptr(), counts.data_ptr(),
+                                       psum.data_ptr(), ws_ptr, ws_bytes, _stream_ptr(scores))
+        _lib.check(rc, "router_balance_loss")
+        if sync:
+            torch.cuda.current_stream(scores.device).synchronize()
+    return loss, counts, psum
+
+
+def router_balance_loss_backward(dloss: torch.Tensor, counts: torch.Tensor, scores: torch.Tensor, k: int, score_func: str,
+                                 seq_len: Optional[int] = None, alpha: float = 1.0, normalize: bool = False,
+                                 add_to: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, sync: bool = False) -> torch.Tensor:
+    """The backward of router_balance_loss into the logits (dga_router_balance_loss_backward): dloss float32 [B], counts int32 [B, E] and
+    scores float32 [T, E] as the forward took and wrote them (the counts carry no gradient), k, seq_len, alpha and normalize as in the
+    forward -> dlogits [T, E], float32 by default or bfloat16 / float16 through out (rounded to nearest even); every element is written.
+    q[b, e] = dloss[b] coef counts[b, e]; ds[t, i] = (q_i - sum_e q_e p_e) / S_t with normalize, else q_i; sigmoid: aux_i = ds_i s_i
+    (1 - s_i); softmax: aux_i = s_i (ds_i - sum_e ds_e s_e).  |aux - ref64| <= gamma(4 E + 8) M against float64 on the same inputs, M the
+    same expression with every term replaced by its absolute value and (1 - s_i) by 1.  add_to (float32 [T, E], what router_topk_backward
+    wrote; it may be out itself): the result is fl32(add_to + aux), bit for bit the sum of add_to and the entry's own float32 result
+    without it, so the step's dlogits is complete after this call.  One wave per token, fixed order, no atomics."""
+    func = _router_func(score_func)
+    t_n, e, seq, b_n, coef = _balance_shape(scores, k, seq_len, alpha)
+    _require(dloss.dtype == torch.float32 and tuple(dloss.shape) == (b_n,) and dloss.is_contiguous(), f"dloss must be contiguous float32 [{b_n}]")
+    _require(counts.dtype == torch.int32 and tuple(counts.shape) == (b_n, e) and counts.is_contiguous(),
+             f"counts must be contiguous int32 [{b_n}, {e}]")
+    if add_to is not None:
+        _require(add_to.dtype == torch.float32 and tuple(add_to.shape) == (t_n, e) and add_to.is_contiguous(),
+                 f"add_to must be contiguous float32 [{t_n}, {e}]")
+    if out is None:
+        out = torch.empty((t_n, e), dtype=torch.float32, device=scores.device)
+    else:
+        _require(out.dtype in _CAST_DT and tuple(out.shape) == (t_n, e) and out.is_contiguous(),
+                 f"out must be contiguous [{t_n}, {e}], float32, bfloat16 or float16")
+    with _device_guard(dloss, counts, scores, out, *((add_to,) if add_to is not None else ())):
+        rc = _lib.lib().dga_router_balance_loss_backward(dloss.data_ptr(), counts.data_ptr(), scores.data_ptr(), t_n, e, k, seq, func,
+                                                         _lib.ROUTER_BALANCE_NORMALIZE if normalize else 0, coef,
+                                                         add_to.data_ptr() if add_to is not None else None, out.data_ptr(),
+                                                         _CAST_DT[out.dtype], _stream_ptr(scores))
+        _lib.check(rc, "router_balance_loss_backward")
+        if sync:
+            torch.cuda.current_stream(scores.device).synchronize()
+    return out
+
+
+def router_bias_update(bias: torch.Tensor, counts: torch.Tensor, rate: float, sync: bool = False) -> torch.Tensor:
+    """DeepSeek-V3's auxiliary-loss-free balancing step, in place on router_topk's bias float32 [E] (dga_router_bias_update), from
+    router_balance_loss's counts int32 [B, E]: n_e = sum_b counts[b, e]; sgn_e = sign(sum_e' n_e' - E n_e), compared as integers (+1 below
+    the mean load, -1 above, 0 exactly at it); bias[e] = fl32(bias[e] + fl32(rate sgn_e)), which numpy float32 reproduces bit for bit.
+    One small launch, capturable: the next router_topk reads the new bias.  Returns bias."""
+    _require(bias.dtype == torch.float32 and bias.dim() == 1 and bias.is_contiguous(), "bias must be a contiguous float32 [E] tensor")
+    e = bias.shape[0]
+    _require(counts.dtype == torch.int32 and counts.dim() == 2 and counts.shape[1] == e and counts.is_contiguous(),
+             f"counts must be a contiguous int32 [B, {e}] tensor")
+    with _device_guard(bias, counts):
+        rc = _lib.lib().dga_router_bias_update(bias.data_ptr(), counts.data_ptr(), counts.shape[0], e, float(rate), _stream_ptr(bias))
+        _lib.check(rc, "router_bias_update")
+        if sync:
+            torch.cuda.current_stream(bias.device).synchronize()
+    return bias
+
+
 def _block_out(out, q_shape: tuple, sf_shape: tuple, device, q_name: str, sf_name: str):
     """_fused_out for the weight quantiser, whose codes and scales do not share their leading dimensions: (q q_shape bytes, sf sf_shape
     float32), torch.empty or the caller's out=(q, sf) checked."""

@@ -19,45 +19,15 @@
 #include "dga_hip.h"
 #include "dga_internal.hpp"
 #include "dga_cast_device.hpp"
+#include "dga_router_device.hpp"
 
 #pragma clang fp contract(off)
 
 namespace dga {
 
-constexpr int ROUTER_WAVES = 4;          // tokens per workgroup
 constexpr float kLog2E = 1.4426950408889634f;
 
-// ---- wave reductions on DPP alone.  Steps 0 .. 3 exchange inside a row of 16 lanes (quad permutes, then the two mirrors, as row16_max):
-// after them every lane holds its row's result.  Steps 4 and 5 hand a row's last lane to the rows after it (row_bcast15 into rows 1 and 3,
-// row_bcast31 into rows 2 and 3; a lane outside the mask receives `idle`, the merge's identity), so that lane 63 ends with the wave's result,
-// which wave_result then gives to every lane.  The merges are commutative and associative; their order is fixed by the lane pattern.
-template <int STEP> __device__ __forceinline__ int lane_xchg(int x, int idle)
-{
-    if constexpr (STEP == 0) return __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);        // quad_perm [1,0,3,2]
-    else if constexpr (STEP == 1) return __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    else if constexpr (STEP == 2) return __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false);  // row_half_mirror
-    else if constexpr (STEP == 3) return __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false);  // row_mirror
-    else if constexpr (STEP == 4) return __builtin_amdgcn_update_dpp(idle, x, 0x142, 0xA, 0xF, false);   // row_bcast15 -> rows 1, 3
-    else return __builtin_amdgcn_update_dpp(idle, x, 0x143, 0xC, 0xF, false);                            // row_bcast31 -> rows 2, 3
-}
-template <int STEP> __device__ __forceinline__ float lane_xchg(float x, float idle)
-{
-    return __builtin_bit_cast(float, lane_xchg<STEP>(__builtin_bit_cast(int, x), __builtin_bit_cast(int, idle)));
-}
-__device__ __forceinline__ int wave_result(int x) { return __builtin_amdgcn_readlane(x, 63); }
-__device__ __forceinline__ float wave_result(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63)); }
-
-template <int STEP = 0> __device__ __forceinline__ float wave_max(float x)
-{
-    if constexpr (STEP == 6) return wave_result(x);
-    else return wave_max<STEP + 1>(__builtin_fmaxf(x, lane_xchg<STEP>(x, -__builtin_inff())));
-}
-// (V - 1 additions inside a lane, then these six: two runs give the same bits)
-template <int STEP = 0> __device__ __forceinline__ float wave_sum(float x)
-{
-    if constexpr (STEP == 6) return wave_result(x);
-    else return wave_sum<STEP + 1>(x + lane_xchg<STEP>(x, 0.f));
-}
+// (lane_xchg, wave_result, wave_max and wave_sum: dga_router_device.hpp)
 // What the k rounds of arg-max compare, as one unsigned 64-bit key: the high word orders the values as IEEE > does (-0 is +0 first, so the
 // two tie; no value is a NaN) and is never 0, the low word is ~index, so of two equal values the lower index is the larger key.  Key 0 is
 // "nothing": an expert that cannot (or can no longer) be chosen, and the idle input of a reduction step.
@@ -103,72 +73,7 @@ __device__ __forceinline__ float group_value(float a1, float a2)
     return gv == gv ? gv : -__builtin_inff();
 }
 
-// ---- the lane's V consecutive elements of a row of e, experts i0 .. i0 + V - 1, at element index base + i0 of p
-template <typename T> struct RouterElem;
-template <> struct RouterElem<float> {
-    typedef float Raw;
-    static __device__ __forceinline__ float up(Raw r) { return r; }
-    static __device__ __forceinline__ Raw down(float v) { return v; }
-};
-template <> struct RouterElem<Bf16Tag> {
-    typedef uint16_t Raw;
-    static __device__ __forceinline__ float up(Raw r) { return __uint_as_float((uint32_t)r << 16); }
-    static __device__ __forceinline__ Raw down(float v)   // round to nearest even (v_cvt_pk_bf16_f32)
-    {
-        typedef float v2f __attribute__((ext_vector_type(2)));
-        typedef __bf16 v2b __attribute__((ext_vector_type(2)));
-        return (uint16_t)__builtin_bit_cast(uint32_t, __builtin_convertvector((v2f{v, 0.f}), v2b));
-    }
-};
-template <> struct RouterElem<F16Tag> {
-    typedef _Float16 Raw;
-    static __device__ __forceinline__ float up(Raw r) { return (float)r; }
-    static __device__ __forceinline__ Raw down(float v) { return (_Float16)v; }
-};
-
-// vec: the caller vouches that p is aligned to a lane's V elements and that e % V == 0.  Elements at and beyond e read as `pad`.
-template <typename T, int V>
-__device__ __forceinline__ void load_lane(const void *p, int64_t base, int i0, int e, bool vec, float pad, float (&v)[V])
-{
-    typedef typename RouterElem<T>::Raw Raw;
-    const Raw *q = (const Raw *)p + base + i0;
-    if constexpr (V > 1) {
-        if (vec) {
-            typedef Raw RawV __attribute__((ext_vector_type(V)));
-            RawV w;
-#pragma unroll
-            for (int c = 0; c < V; ++c) w[c] = Raw{};
-            if (i0 < e) w = *(const RawV *)q;
-#pragma unroll
-            for (int c = 0; c < V; ++c) v[c] = i0 < e ? RouterElem<T>::up(w[c]) : pad;
-            return;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < V; ++c) {
-        v[c] = pad;
-        if (i0 + c < e) v[c] = RouterElem<T>::up(q[c]);
-    }
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_lane(void *p, int64_t base, int i0, int e, bool vec, const float (&v)[V])
-{
-    typedef typename RouterElem<T>::Raw Raw;
-    Raw *q = (Raw *)p + base + i0;
-    if constexpr (V > 1) {
-        if (vec) {
-            typedef Raw RawV __attribute__((ext_vector_type(V)));
-            RawV w;
-#pragma unroll
-            for (int c = 0; c < V; ++c) w[c] = RouterElem<T>::down(v[c]);
-            if (i0 < e) *(RawV *)q = w;
-            return;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < V; ++c)
-        if (i0 + c < e) q[c] = RouterElem<T>::down(v[c]);
-}
+// (load_lane and store_lane: dga_router_device.hpp)
 
 // The widest build's unrolled loops over a lane's 16 elements: left alone the scheduler issues all their comparisons first, and the 16 to 48
 // lane masks push the kernel's pointers out of the scalar registers.  A fence after each element keeps a mask's life to its element.
@@ -407,16 +312,6 @@ __global__ void __launch_bounds__(64 * ROUTER_WAVES) router_topk_backward_kernel
     store_lane<O, V>(dlogits, base, i0, e, vec_out, out);
 }
 
-// V for a row of e <= 1024 experts: the power of two with 64 V >= e -> f(integral_constant<int, V>)
-template <typename F> inline int dispatch_lane_width(int64_t e, F &&f)
-{
-    if (e <= 64) return f(std::integral_constant<int, 1>{});
-    if (e <= 128) return f(std::integral_constant<int, 2>{});
-    if (e <= 256) return f(std::integral_constant<int, 4>{});
-    if (e <= 512) return f(std::integral_constant<int, 8>{});
-    return f(std::integral_constant<int, 16>{});
-}
-
 // the checks the two entries share, in the combine entries' order: shape, then (after nothing-to-do, pointers and dtype, which are the
 // entry's own) what a launch cannot take
 inline int router_shape(int64_t tokens, int64_t e, int64_t k)
@@ -433,12 +328,6 @@ inline int router_range(int64_t tokens, int64_t e, int64_t k, int score_func, in
     grid = static_cast<unsigned>(groups);
     return DGA_OK;
 }
-// a lane's V elements of `bytes` each go as one vector: the tensor starts on such a vector and every row holds a whole number of them
-inline bool router_vec(const void *p, int64_t e, int v, int bytes)
-{
-    return reinterpret_cast<uintptr_t>(p) % (static_cast<uintptr_t>(v) * bytes) == 0 && e % v == 0;
-}
-
 }  // namespace dga
 
 extern "C" int dga_router_topk(const void *logits, int logits_dtype, int64_t tokens, int64_t experts, int64_t k, int score_func,

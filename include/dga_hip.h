@@ -692,6 +692,51 @@ int dga_router_topk(const void *logits, int logits_dtype, int64_t tokens, int64_
 int dga_router_topk_backward(const float *dw, const float *scores, const int32_t *ids, int64_t tokens, int64_t experts, int64_t k,
                              int score_func, int flags, float scale, void *dlogits, int dlogits_dtype, void *stream);
 
+/* The load-balancing loss of a router over dga_router_topk's outputs: scores fp32 [tokens, experts] and ids int32 [tokens, k], both
+ * contiguous; the tokens form B = tokens / seq_len segments of seq_len consecutive tokens (seq_len = tokens: Switch / GShard's global
+ * loss; seq_len = a sequence: DeepSeek-V3's sequence-wise loss).  For segment b, with u = 2^-24 and gamma(n) = n u / (1 - n u):
+ *   counts[b, e] = #{(t, j) : t in b, ids[t, j] == e}                   int32 [B, experts], exact; an id outside [0, experts) counts nowhere
+ *   p[t, e]      = scores[t, e] / S_t, S_t = sum_e scores[t, e]         (DGA_ROUTER_BALANCE_NORMALIZE;  else p = scores)
+ *   psum[b, e]   = sum_{t in b} p[t, e]                                 fp32 [B, experts], |psum - P64| <= gamma(seq_len + experts + 1) P64
+ *   loss[b]      = coef * sum_e counts[b, e] * psum[b, e]               fp32 [B], |loss - loss64| <= gamma(seq_len + 2 experts + 4) loss64
+ * against float64 on the same fp32 scores (scores >= 0).  coef is the caller's: alpha * experts / (k seq_len^2) gives
+ * alpha sum_e f_e P_e with f_e = experts / (k seq_len) counts and P_e = psum / seq_len.  Every element of the three outputs is written.
+ * A NaN score makes its own segment's psum (that expert's) and loss NaN and touches no other segment.  Two launches, no floating-point
+ * atomics, nothing read back (capturable): a workgroup adds a chunk of max(16, 4 ceil(tokens / 2048)) consecutive tokens of one segment
+ * into a partial of the workspace, fp32 and int32 [B, chunks, experts] with chunks = ceil(seq_len / that); one workgroup per segment
+ * then adds the partials in an order the shape alone fixes, so two runs give the same bits.  The callee never allocates:
+ * dga_router_balance_loss_workspace_bytes gives the size, 8 B chunks experts (0 for a shape the entry refuses or an empty one).
+ * DGA_E_SHAPE: a negative size, k < 1, k > experts, seq_len < 1, tokens % seq_len != 0;  tokens == 0 is DGA_OK with nothing touched;
+ * then DGA_E_NULL (scores, ids, loss, counts, psum, workspace), and DGA_E_RANGE for experts > DGA_ROUTER_MAX_EXPERTS,
+ * k > DGA_ROUTER_MAX_TOPK, an unknown flag, more than 2^31 - 1 partials, or a workspace that is too small or not 4-byte aligned. */
+#define DGA_ROUTER_BALANCE_NORMALIZE 1                     /* flags */
+size_t dga_router_balance_loss_workspace_bytes(int64_t tokens, int64_t experts, int64_t seq_len);
+int dga_router_balance_loss(const float *scores, const int32_t *ids, int64_t tokens, int64_t experts, int64_t k, int64_t seq_len, int flags,
+                            float coef, float *loss, int32_t *counts, float *psum, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The backward of dga_router_balance_loss into the logits: dloss fp32 [B], counts and scores as above (the counts carry no gradient) ->
+ * dlogits [tokens, experts] of dlogits_dtype (DGA_DT_FP32, or a 16-bit type rounded to nearest even); every element is written.  For a
+ * token t of segment b, in fp32, every operation rounded on its own:
+ *   q_e  = fl(fl(dloss[b] * coef) * fl(counts[b, e]))
+ *   ds_i = (q_i - sum_e q_e p_e) / S_t   (DGA_ROUTER_BALANCE_NORMALIZE;  else ds_i = q_i)
+ *   DGA_ROUTER_SIGMOID: aux_i = ds_i s_i (1 - s_i);   DGA_ROUTER_SOFTMAX: aux_i = s_i (ds_i - sum_e ds_e s_e)
+ * |aux - ref64| <= gamma(4 experts + 8) M against float64 on the same inputs, M the same expression with every term replaced by its
+ * absolute value and (1 - s_i) by 1.  add_to (fp32 [tokens, experts] or NULL; it may be dlogits itself): the result is
+ * fl(add_to + aux), bit for bit the sum of add_to and what the entry writes as fp32 without it -- dga_router_topk_backward's output
+ * becomes the step's whole dlogits without another pass.  One wave per token, fixed order, no atomics: two runs give the same bits.
+ * Checks as in dga_router_balance_loss (DGA_E_NULL: dloss, counts, scores, dlogits; then DGA_E_DTYPE; DGA_E_RANGE also for an unknown
+ * score_func and for more tokens than one grid holds). */
+int dga_router_balance_loss_backward(const float *dloss, const int32_t *counts, const float *scores, int64_t tokens, int64_t experts, int64_t k,
+                                     int64_t seq_len, int score_func, int flags, float coef, const float *add_to, void *dlogits,
+                                     int dlogits_dtype, void *stream);
+
+/* DeepSeek-V3's auxiliary-loss-free balancing step, in place on bias fp32 [experts] (what dga_router_topk adds for the selection), from
+ * counts int32 [segments, experts]:  n_e = sum_b counts[b, e] (int64),  sgn_e = sign(sum_e' n_e' - experts * n_e), compared as integers --
+ * +1 for an expert below the mean load, -1 above, 0 exactly at it --,  bias[e] = fl(bias[e] + fl(rate * sgn_e)).  A host reference in
+ * float32 reproduces it bit for bit.  One launch of one workgroup, capturable.  DGA_E_SHAPE: a negative size;  segments == 0 or
+ * experts == 0 is DGA_OK with nothing touched;  then DGA_E_NULL (bias, counts) and DGA_E_RANGE for experts > DGA_ROUTER_MAX_EXPERTS. */
+int dga_router_bias_update(float *bias, const int32_t *counts, int64_t segments, int64_t experts, float rate, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
