@@ -30,7 +30,8 @@ _FP8 = getattr(torch, "float8_e4m3fn", None)
 
 # Host time per call matters for the short shapes of the reference's sweep list (a 64 x 32768 x 512 GEMM is 6 us of device
 # time): the helpers below keep a call at a handful of Python-level operations -- no tensor views, no stream / device objects,
-# no message formatting unless a check fails (scripts/host_overhead.py: 12.5 -> 5 us per call).
+# no message formatting unless a check fails (12.5 -> 5 us per call, profiles/r03_host_overhead.txt; scripts/api_host_time.py times the
+# wrappers of today, profiles/api_host_time.txt).
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -52,9 +53,10 @@ def _fail(msg: str):
     raise DGAError(-2, "host assert", msg)
 
 
-def _require(cond: bool, msg: str):
+def _require(cond: bool, msg: str, *args):
+    """A check with a wording of its own: `msg % args` is formed when it fails, never before."""
     if not cond:
-        _fail(msg)
+        _fail(msg % args if args else str(msg))
 
 
 def _fp8_bytes(t: torch.Tensor) -> torch.Tensor:
@@ -62,6 +64,65 @@ def _fp8_bytes(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != _FP8 and t.dtype != torch.uint8:
         _fail(f"fp8 operand must be float8_e4m3fn or uint8 bytes, got {t.dtype}")
     return t
+
+
+# What the operator wrappers share ("Adding an operator's Python wrapper"): every argument check before the device guard, every
+# message built only when its check fails, outputs from torch.empty.
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def _want(t: torch.Tensor, what, dtype, shape: tuple, prefix: str = "") -> None:
+    """One tensor argument: of `dtype` (one dtype, a collection of them, None = not checked), exactly `shape`, contiguous -- or
+    "<prefix><what> must be contiguous <dtype> <shape>"."""
+    if t.shape != shape or not t.is_contiguous() or not (
+            dtype is None or t.dtype == dtype or (not isinstance(dtype, torch.dtype) and t.dtype in dtype)):
+        names = "" if dtype is None else " or ".join(str(d)[6:] for d in ([dtype] if isinstance(dtype, torch.dtype) else dtype)) + " "
+        _fail("%s%s must be contiguous %s%s" % (prefix, what, names, list(shape)))
+
+
+def _outputs(out, specs, device, label):
+    """The outputs of a wrapper, specs = ((name, dtype, shape), ...): torch.empty, or the caller's out= -- `label` is the message for a tuple
+    of another length or a member that is no tensor -- with every member through _want as "out <name>".  dtype uint8 means fp8 codes: bytes
+    when allocated (_as_fp8 re-tags them on the way out), uint8 or float8_e4m3fn when they are the caller's."""
+    if out is None:
+        return [torch.empty(shape, dtype=dtype, device=device) for _, dtype, shape in specs]
+    if not isinstance(out, (tuple, list)) or len(out) != len(specs):
+        _fail(str(label))
+    for t in out:
+        if not isinstance(t, torch.Tensor):
+            _fail(str(label))
+    for t, (name, dtype, shape) in zip(out, specs):
+        if dtype == torch.uint8:
+            _fp8_bytes(t)
+            dtype = None
+        _want(t, name, dtype, shape, "out ")
+    return out
+
+
+def _nested_out(out, rowwise: bool):
+    """out= of a transposing quantiser split into (out of the transposed pair, out of the row-wise pair): (qt, sft) or, with rowwise,
+    ((qt, sft), (q, sf))."""
+    if out is None:
+        return None, None
+    _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be ((qt, sft), (q, sf))" if rowwise else "out must be (qt, sft)")
+    return out if rowwise else (out, None)
+
+
+def _as_fp8(q: torch.Tensor) -> torch.Tensor:
+    """Code bytes as float8_e4m3fn (a view: the caller's own tensor when it already is)."""
+    return q.view(_FP8) if q.dtype == torch.uint8 else q
+
+
+def _row_masks(masked_m: Optional[torch.Tensor], m_indices: Optional[torch.Tensor], groups: int, rows: int) -> None:
+    """The row masks of the quantisers: masked_m int32 [groups], m_indices int32 [rows]."""
+    if masked_m is not None:
+        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
+                 "masked_m must be a contiguous int32 [%d]", groups)
+    if m_indices is not None:
+        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
+                 "m_indices must be a contiguous int32 [%d]", rows)
 
 
 _WORKSPACES = {}   # (kind, device index, stream handle) -> uint8 tensor
@@ -174,8 +235,9 @@ _DEFAULT_POLICY = _DefaultPolicy()
 
 def _with_policy(t: Tiling, strict: bool, policy: Optional[str] = None) -> Tiling:
     """A copy of the tiling with the arithmetic policy's dispatchPolicyTag (strict=True is policy="strict")."""
-    _require(policy is None or policy in ARITHMETIC_POLICIES, f"policy must be one of {sorted(ARITHMETIC_POLICIES)}")
-    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r" % (policy,))
+    if policy is not None and policy not in ARITHMETIC_POLICIES:
+        _fail(f"policy must be one of {sorted(ARITHMETIC_POLICIES)}")
+    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r", policy)
     tag = POLICY_STRICT if strict else ARITHMETIC_POLICIES.get(policy)
     if policy == "fast_ue8m0" and not strict:
         _require((t.dispatchPolicyTag & 15) not in (POLICY_STRICT, POLICY_BF16_EXACT), "policy='fast_ue8m0' needs a fast-path tiling")
@@ -210,6 +272,19 @@ def _device_guard(*ts: torch.Tensor):
     return _NO_GUARD if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
+def _launch(name: str, tensors, call, sync: bool = False) -> None:
+    """The tail of a wrapper whose checks have passed: the device guard over `tensors` (None for an absent optional one), rc = call(library,
+    stream) on the current stream of the first tensor's device -- scratch is allocated in there, behind the guard --, the status check, and
+    the synchronise sync=True asks for.  (The dense and grouped GEMM entries keep this inline: a closure per call is host time there.)"""
+    first = tensors[0]
+    with _device_guard(*[t for t in tensors if t is not None]):
+        rc = call(_lib.lib(), _stream_ptr(first))
+        if rc:
+            _lib.check(rc, name)
+        if sync:
+            torch.cuda.current_stream(first.device).synchronize()
+
+
 _PLANS = {}        # what a GEMM call without an explicit tiling resolves to: key -> Tiling (with the policy's tag)
 
 
@@ -226,21 +301,27 @@ def _planned(index: int, m: int, n: int, k: int, groups: int, expected_m: int, c
     key = (index, m, n, k, groups, expected_m, contiguous, strict, policy)
     t = _PLANS.get(key)
     if t is None:
-        if len(_PLANS) > 4096:
-            _PLANS.clear()
-        _require(policy is None or policy in ARITHMETIC_POLICIES, f"policy (or $DGA_DEFAULT_POLICY) must be one of {sorted(ARITHMETIC_POLICIES)}")
+        if policy is not None and policy not in ARITHMETIC_POLICIES:
+            _fail(f"policy (or $DGA_DEFAULT_POLICY) must be one of {sorted(ARITHMETIC_POLICIES)}")
         if policy == "auto":   # the exact arithmetic where the decode kernel carries it, the fast path elsewhere
             _require(not strict, "strict=True contradicts policy='auto'")
-            tb = tiling(m, n, k, policy="bf16_exact") if groups == 1 and not contiguous else None
-            if tb is not None and tb.kernelSerial == 6:   # DGA_KERNEL_SPLITK_WORKGROUP
-                t = tb
-            else:
+            t = tiling(m, n, k, policy="bf16_exact") if groups == 1 and not contiguous else None
+            if t is None or t.kernelSerial != 6:   # DGA_KERNEL_SPLITK_WORKGROUP
                 t = tiling(m, n, k, groups=groups, expected_m=expected_m, contiguous=contiguous)
-            _PLANS[key] = t
-            return t
-        t = tiling(m, n, k, groups=groups, expected_m=expected_m, contiguous=contiguous,
-                   policy="bf16_exact" if policy in ("bf16_exact", "bf16_exact_ue8m0") else None)
-        t = _PLANS[key] = _with_policy(t, strict, policy)
+        else:
+            t = tiling(m, n, k, groups=groups, expected_m=expected_m, contiguous=contiguous,
+                       policy="bf16_exact" if policy in ("bf16_exact", "bf16_exact_ue8m0") else None)
+            t = _with_policy(t, strict, policy)
+        _remember(key, t)
+    return t
+
+
+def _remember(key, t: Tiling) -> Tiling:
+    """A plan into _PLANS, on a miss (the hit is the caller's own _PLANS.get: a call that finds its plan pays nothing for this).  The dict
+    is emptied rather than grown past 4096 plans."""
+    if len(_PLANS) > 4096:
+        _PLANS.clear()
+    _PLANS[key] = t
     return t
 
 
@@ -279,6 +360,14 @@ def tiling(m: int, n: int, k: int, groups: int = 1, expected_m: int = 0, contigu
         return t
     _lib.check(_lib.lib().dga_tiling(ctypes.byref(p), ctypes.byref(t)), "tiling")
     return _with_policy(t, False, policy) if policy else t
+
+
+def _default_tiling(entry: str, p: Problem) -> Tiling:
+    """The C entry dga_<entry>(problem, tiling) behind tiling_fp32_out, tiling_wgrad and tiling_k_grouped_wgrad (tiling() itself runs on
+    every call of the contiguous grouped GEMM and stays inline)."""
+    t = Tiling()
+    _lib.check(getattr(_lib.lib(), "dga_" + entry)(ctypes.byref(p), ctypes.byref(t)), entry)
+    return t
 
 
 def tiling_check(t: Tiling) -> int:
@@ -327,7 +416,7 @@ def select_kernel_with_predictor(m: int, n: int, k: int, method: str = "greedy",
     """SelectKernelWithPredictor: (tiling, predicted_us, native_us); falls back to the heuristic tiling when the model
     is absent, the candidate list is short or the promised gain is below the threshold (get_best_config.py:587-621).  `method` /
     `topk`: the reference predictor's selection strategy (select_tiling_strategy, get_best_config.py:431-525)."""
-    _require(method in SELECTION_METHODS, f"method: one of {sorted(SELECTION_METHODS)}")
+    _require(method in SELECTION_METHODS, "method: one of %s", sorted(SELECTION_METHODS))
     t = Tiling()
     p = _problem(m, n, k)
     a, b = ctypes.c_float(0), ctypes.c_float(0)
@@ -342,7 +431,7 @@ def select_tiling_strategy(preds, tiles, method: str = "greedy", topk: int = 10,
     (mTile, nTile, kTile): returns (picked index, members of the winning cluster -- topk_dbscan only, else []).  The reference draws a
     random member of that cluster; this library takes its fastest (random_state = 0) or member random_state % size."""
     import numpy as np
-    _require(method in SELECTION_METHODS, f"method: one of {sorted(SELECTION_METHODS)}")
+    _require(method in SELECTION_METHODS, "method: one of %s", sorted(SELECTION_METHODS))
     pr = np.ascontiguousarray(preds, dtype=np.float32)
     tl = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 3) if tiles is not None else np.zeros((pr.size, 3), np.int32)
     _require(tl.shape[0] == pr.size, "one tile triple per prediction")
@@ -452,6 +541,24 @@ def _dense_fp8_operands(a, sfa, b, sfb, out, out_dtype, out_name: str, sfb_rows:
     return m, n, k, lda, ldb
 
 
+def _zero_padded_flags(a: torch.Tensor, b: torch.Tensor, zero_padded: Optional[Tuple[bool, bool]]) -> int:
+    """The ROWS_*_ZERO_PADDED flags of a call on row-strided operands: the caller's promise, else the mark the aligned_rows quantisers leave."""
+    if zero_padded is None:
+        zero_padded = (getattr(a, "_dga_zero_padded", False), getattr(b, "_dga_zero_padded", False))
+    return (_lib.ROWS_A_ZERO_PADDED if zero_padded[0] else 0) | (_lib.ROWS_B_ZERO_PADDED if zero_padded[1] else 0)
+
+
+def _accumuland(c: torch.Tensor, shape: tuple, out: torch.Tensor) -> None:
+    """The c of the fp32-output GEMMs: contiguous float32 of out's `shape`, and out itself or clear of it."""
+    if c.dtype != torch.float32 or tuple(c.shape) != shape or not c.is_contiguous():
+        if len(shape) == 3:    # (the k-grouped entry words it in one message, the dense entries fault by fault)
+            _fail("c must be a contiguous float32 %s" % list(shape))
+        _fail("c must be float32" if c.dtype != torch.float32 else "c must be contiguous" if tuple(c.shape) == shape else "c must be [%d,%d]" % shape)
+    lo, hi, nbytes = c.data_ptr(), out.data_ptr(), 4 * out.numel()
+    if lo != hi and c.device == out.device and lo < hi + nbytes and hi < lo + nbytes:
+        _fail("c must be out itself or not overlap it")
+
+
 def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torch.Tensor, torch.Tensor],
                          out: torch.Tensor, tiling_: Optional[Tiling] = None, sync: bool = False,
                          strict: bool = False, policy: Optional[str] = None,
@@ -476,8 +583,6 @@ def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
     b, sfb = rhs
     m, n, k, lda, ldb = _dense_fp8_operands(a, sfa, b, sfb, out, torch.bfloat16, "bfloat16")
     strided = lda != k or ldb != k
-    if zero_padded is None:
-        zero_padded = (bool(getattr(a, "_dga_zero_padded", False)), bool(getattr(b, "_dga_zero_padded", False)))
     with _device_guard(a, b, sfa, sfb, out):
         index = out.device.index
         if tiling_ is None:
@@ -487,7 +592,7 @@ def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
         stream = _stream_of(index)
         ws_ptr, ws_bytes = _workspace(tiling_, out.device, stream)
         if strided:
-            flags = (_lib.ROWS_A_ZERO_PADDED if zero_padded[0] else 0) | (_lib.ROWS_B_ZERO_PADDED if zero_padded[1] else 0)
+            flags = _zero_padded_flags(a, b, zero_padded)
             rc = _lib.lib().dga_gemm_fp8_fp8_bf16_nt_strided(a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(),
                                                              out.data_ptr(), m, n, k, flags, ctypes.byref(tiling_), ws_ptr,
                                                              ws_bytes, stream)
@@ -503,10 +608,7 @@ def gemm_fp8_fp8_bf16_nt(lhs: Tuple[torch.Tensor, torch.Tensor], rhs: Tuple[torc
 def tiling_fp32_out(m: int, n: int, k: int) -> Tiling:
     """dga_tiling_fp32_out: the default tiling of gemm_fp8_fp8_fp32_nt -- the bf16-exact pick, with names of builds that have no fp32
     epilogue mapped onto the in-register build of the same tile; the strict tag under $DGA_DEFAULT_POLICY=strict."""
-    t = Tiling()
-    p = _problem(m, n, k, 1, 0)
-    _lib.check(_lib.lib().dga_tiling_fp32_out(ctypes.byref(p), ctypes.byref(t)), "tiling_fp32_out")
-    return t
+    return _default_tiling("tiling_fp32_out", _problem(m, n, k, 1, 0))
 
 
 def tiling_check_fp32_out(t: Tiling) -> int:
@@ -538,10 +640,7 @@ def tiling_wgrad(m: int, n: int, k: int) -> Tiling:
     """dga_tiling_wgrad: the default tiling of wgrad_gemm_fp8_fp8_fp32_nt -- tiling_fp32_out's pick, with the builds that have no
     per-row-sfb form (workgroup split-K and its decode / register builds, one-launch Stream-K) mapped onto the same tile's two-launch
     split-K or plain raster; the strict tag under $DGA_DEFAULT_POLICY=strict."""
-    t = Tiling()
-    p = _problem(m, n, k, 1, 0)
-    _lib.check(_lib.lib().dga_tiling_wgrad(ctypes.byref(p), ctypes.byref(t)), "tiling_wgrad")
-    return t
+    return _default_tiling("tiling_wgrad", _problem(m, n, k, 1, 0))
 
 
 def tiling_check_wgrad(t: Tiling) -> int:
@@ -571,9 +670,7 @@ def _planned_fp32_out(index: int, m: int, n: int, k: int, strict: bool, policy: 
     key = ("wgrad" if sfb_rows else "fp32_out", index, m, n, k, strict, policy)
     t = _PLANS.get(key)
     if t is None:
-        if len(_PLANS) > 4096:
-            _PLANS.clear()
-        t = _PLANS[key] = _with_policy((tiling_wgrad if sfb_rows else tiling_fp32_out)(m, n, k), strict, policy)
+        t = _remember(key, _with_policy((tiling_wgrad if sfb_rows else tiling_fp32_out)(m, n, k), strict, policy))
     return t
 
 
@@ -581,25 +678,14 @@ def _fp32_out_call(name: str, lhs, rhs, out, c, tiling_, sync, strict, policy, z
     """gemm_fp8_fp8_fp32_nt (sfb_rows=False) and wgrad_gemm_fp8_fp8_fp32_nt (sfb_rows=True): checks, plan, launch."""
     a, sfa = lhs
     b, sfb = rhs
-    _require(policy is None or policy in _FP32_OUT_POLICIES, f"{name}: policy must be one of {list(_FP32_OUT_POLICIES)}")
-    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r" % (policy,))
+    _require(policy is None or policy in _FP32_OUT_POLICIES, "%s: policy must be one of %s", name, list(_FP32_OUT_POLICIES))
+    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r", policy)
     m, n, k, lda, ldb = _dense_fp8_operands(a, sfa, b, sfb, out, torch.float32, "float32", sfb_rows)
     if k == 0:
         lda = ldb = 0   # (a zero-width view has no meaningful row stride: nothing is read, out = c)
     if c is not None:
-        if c.dtype != torch.float32:
-            _fail("c must be float32")
-        if c.dim() != 2 or c.shape[0] != m or c.shape[1] != n:
-            _fail(f"c must be [{m},{n}]")
-        if not c.is_contiguous():
-            _fail("c must be contiguous")
-        if c.data_ptr() != out.data_ptr() and c.device == out.device and m * n > 0:
-            lo, hi = c.data_ptr(), out.data_ptr()
-            if lo < hi + 4 * m * n and hi < lo + 4 * m * n:
-                _fail("c must be out itself or not overlap it")
-    strided = lda != k or ldb != k
-    if zero_padded is None:
-        zero_padded = (bool(getattr(a, "_dga_zero_padded", False)), bool(getattr(b, "_dga_zero_padded", False)))
+        _accumuland(c, (m, n), out)
+    flags = _zero_padded_flags(a, b, zero_padded) if lda != k or ldb != k else 0
     with _device_guard(a, b, sfa, sfb, out, *(() if c is None else (c,))):
         index = out.device.index
         if tiling_ is None:
@@ -608,9 +694,6 @@ def _fp32_out_call(name: str, lhs, rhs, out, c, tiling_, sync, strict, policy, z
             tiling_ = _with_policy(tiling_, strict, policy)
         stream = _stream_of(index)
         ws_ptr, ws_bytes = _workspace(tiling_, out.device, stream)
-        flags = 0
-        if strided:
-            flags = (_lib.ROWS_A_ZERO_PADDED if zero_padded[0] else 0) | (_lib.ROWS_B_ZERO_PADDED if zero_padded[1] else 0)
         entry = _lib.lib().dga_wgrad_gemm_fp8_fp8_fp32_nt if sfb_rows else _lib.lib().dga_gemm_fp8_fp8_fp32_nt
         rc = entry(a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(), None if c is None else c.data_ptr(),
                    out.data_ptr(), m, n, k, flags, ctypes.byref(tiling_), ws_ptr, ws_bytes, stream)
@@ -624,10 +707,7 @@ def tiling_k_grouped_wgrad(m: int, n: int, k_total: int, groups: int) -> Tiling:
     """dga_tiling_k_grouped_wgrad: the default tiling of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt -- a rule on the G x tiles(M, N) raster
     (the persistent 128 x 256 build where it fills the CUs, else a one-tile build whose raster does), no split-K, no workspace, no
     tiling-cache lookup; the strict tag under $DGA_DEFAULT_POLICY=strict."""
-    t = Tiling()
-    p = _problem(m, n, k_total, groups, 0)
-    _lib.check(_lib.lib().dga_tiling_k_grouped_wgrad(ctypes.byref(p), ctypes.byref(t)), "tiling_k_grouped_wgrad")
-    return t
+    return _default_tiling("tiling_k_grouped_wgrad", _problem(m, n, k_total, groups, 0))
 
 
 def tiling_check_k_grouped_wgrad(t: Tiling) -> int:
@@ -658,8 +738,8 @@ def k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor],
     name = "k_grouped_wgrad_gemm_fp8_fp8_fp32_nt"
     a, sfa = lhs
     b, sfb = rhs
-    _require(policy is None or policy in _FP32_OUT_POLICIES, f"{name}: policy must be one of {list(_FP32_OUT_POLICIES)}")
-    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r" % (policy,))
+    _require(policy is None or policy in _FP32_OUT_POLICIES, "%s: policy must be one of %s", name, list(_FP32_OUT_POLICIES))
+    _require(not (strict and policy not in (None, "strict")), "strict=True contradicts policy=%r", policy)
     _fp8_bytes(a); _fp8_bytes(b)
     if a.dim() != 2 or b.dim() != 2:
         _fail("A and B must be rank 2")
@@ -701,12 +781,7 @@ def k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor],
         if ks_tensor.device != out.device:
             _fail("ks_tensor must live on the operands' device")
     if c is not None:
-        if c.dtype != torch.float32 or tuple(c.shape) != (g, m, n) or not c.is_contiguous():
-            _fail(f"c must be a contiguous float32 [{g}, {m}, {n}]")
-        if c.data_ptr() != out.data_ptr() and c.device == out.device and g * m * n > 0:
-            lo, hi, nbytes = c.data_ptr(), out.data_ptr(), 4 * g * m * n
-            if lo < hi + nbytes and hi < lo + nbytes:
-                _fail("c must be out itself or not overlap it")
+        _accumuland(c, (g, m, n), out)
     with _device_guard(a, b, sfa, sfb, out, *(() if c is None else (c,)), *(() if ks_tensor is None else (ks_tensor,))):
         index = out.device.index
         if tiling_ is None:
@@ -714,15 +789,13 @@ def k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(lhs: Tuple[torch.Tensor, torch.Tensor],
             key = ("k_grouped_wgrad", index, m, n, k_total, g, strict, policy)
             tiling_ = _PLANS.get(key)
             if tiling_ is None:
-                if len(_PLANS) > 4096:
-                    _PLANS.clear()
-                tiling_ = _PLANS[key] = _with_policy(tiling_k_grouped_wgrad(m, n, k_total, g), strict, policy)
+                tiling_ = _remember(key, _with_policy(tiling_k_grouped_wgrad(m, n, k_total, g), strict, policy))
         else:
             tiling_ = _with_policy(tiling_, strict, policy)
         if ks_tensor is None:
             ks_tensor = torch.tensor(ks, dtype=torch.int32, device=out.device)
         rc = _lib.lib().dga_k_grouped_wgrad_gemm_fp8_fp8_fp32_nt(
-            a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(), None if c is None else c.data_ptr(),
+            a.data_ptr(), lda, sfa.data_ptr(), b.data_ptr(), ldb, sfb.data_ptr(), _ptr(c),
             out.data_ptr(), ks_tensor.data_ptr(), g, m, n, k_total, 0, ctypes.byref(tiling_), None, 0, _stream_of(index))
         if rc:
             _lib.check(rc, name)
@@ -829,7 +902,7 @@ def m_grouped_gemm_fp8_fp8_bf16_nt_masked_indexed(a_rows: torch.Tensor, sfa_src:
     kb, nb = (k + 127) // 128, (n + 127) // 128
     _require(a_rows.shape[1] >= k and out_rows.shape[1] >= n and out_rows.dtype == torch.bfloat16, "row widths")
     _require(out_rows.shape[0] >= rows, "out_rows must have a row for every source row")
-    _require(tuple(sfb.shape) == (g, nb, kb) and sfb.dtype == torch.float32, f"sfb must be [{g},{nb},{kb}] f32")
+    _require(tuple(sfb.shape) == (g, nb, kb) and sfb.dtype == torch.float32, "sfb must be [%d,%d,%d] f32", g, nb, kb)
     _require(row_index.dtype == torch.int64 and row_index.numel() >= g * m_max and row_index.is_contiguous(), "row_index int64[G*m_max]")
     _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (g,), "masked_m must be int32 [G]")
     _require(sfa_byte_offset % 4 == 0 and sfa_ld >= kb, "scale rows must be float-aligned")
@@ -899,8 +972,8 @@ def m_grouped_gemm_fp8_fp8_bf16_nt_contiguous(lhs, rhs, out: torch.Tensor, m_ind
     _require(k == k2, "k mismatch")
     _require(tuple(out.shape) == (msum, n) and out.dtype == torch.bfloat16, "out must be [Msum,N] bfloat16")
     kb, nb = (k + 127) // 128, (n + 127) // 128
-    _require(tuple(sfa.shape) == (msum, kb) and sfa.dtype == torch.float32, f"sfa must be [{msum},{kb}] f32")
-    _require(tuple(sfb.shape) == (g, nb, kb) and sfb.dtype == torch.float32, f"sfb must be [{g},{nb},{kb}] f32")
+    _require(tuple(sfa.shape) == (msum, kb) and sfa.dtype == torch.float32, "sfa must be [%d,%d] f32", msum, kb)
+    _require(tuple(sfb.shape) == (g, nb, kb) and sfb.dtype == torch.float32, "sfb must be [%d,%d,%d] f32", g, nb, kb)
     _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (msum,), "m_indices must be int32 [Msum]")
     for t in (a, b, sfa, sfb, out, m_indices):
         _require(t.is_contiguous(), "operands must be contiguous")
@@ -931,17 +1004,9 @@ def _cast(fn_name: str, x: torch.Tensor, block_rows: int, aligned_rows: bool = F
     ldq = (k + 127) // 128 * 128 if aligned_rows else k   # whole 128-byte lines: a row's k blocks never straddle two
     q = torch.empty((rows, ldq), dtype=torch.uint8, device=x.device)
     sf = torch.empty(((rows + block_rows - 1) // block_rows, (k + 127) // 128), dtype=torch.float32, device=x.device)
-    with _device_guard(x):
-        if use_ue8m0:     # block scales rounded up to powers of two (dga_cast_to_fp8_*_ex, DGA_CAST_UE8M0)
-            rc = getattr(_lib.lib(), fn_name + "_ex")(x.data_ptr(), _CAST_DT[x.dtype], rows, k, q.data_ptr(), ldq, sf.data_ptr(),
-                                                      _lib.CAST_UE8M0, _stream_ptr(x))
-        elif ldq != k:
-            rc = getattr(_lib.lib(), fn_name + "_ld")(x.data_ptr(), _CAST_DT[x.dtype], rows, k, q.data_ptr(), ldq, sf.data_ptr(),
-                                                      _stream_ptr(x))
-        else:
-            rc = getattr(_lib.lib(), fn_name)(x.data_ptr(), _CAST_DT[x.dtype], rows, k, q.data_ptr(), sf.data_ptr(),
-                                              _stream_ptr(x))
-        _lib.check(rc, fn_name)
+    # (the _ex entry alone: the C entries without ldq or flags are the same call with k and 0.  DGA_CAST_UE8M0: scales rounded up to 2^n)
+    _launch(fn_name, (x,), lambda L, stream: getattr(L, fn_name + "_ex")(
+        x.data_ptr(), _CAST_DT[x.dtype], rows, k, q.data_ptr(), ldq, sf.data_ptr(), _lib.CAST_UE8M0 if use_ue8m0 else 0, stream))
     q = q.view(torch.float8_e4m3fn)
     if ldq != k:
         q = q[:, :k]
@@ -976,35 +1041,22 @@ def _fused_layout(x: torch.Tensor, masked_m: Optional[torch.Tensor], m_indices: 
     int32 [rows]; the last dimension a multiple of `multiple` (`last`: its name in the messages -- per_token_cast_to_fp8_transposed has no
     halves).  Returns (H, the leading dimensions, groups, rows per group)."""
     _require(masked_m is None or m_indices is None, "masked_m and m_indices exclude each other")
-    want_dim = 3 if masked_m is not None else 2
-    _require(x.dim() == want_dim and x.is_contiguous(),
-             f"x must be a contiguous [G, Mmax, {last}] tensor with masked_m" if masked_m is not None else f"x must be a contiguous [rows, {last}] tensor")
+    if masked_m is not None:
+        _require(x.dim() == 3 and x.is_contiguous(), "x must be a contiguous [G, Mmax, %s] tensor with masked_m", last)
+    else:
+        _require(x.dim() == 2 and x.is_contiguous(), "x must be a contiguous [rows, %s] tensor", last)
     _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
     if multiple != 1:    # (1: per_token_cast_to_fp8_transposed, any width)
         _require(x.shape[-1] % multiple == 0, _FUSED_LAST_DIM[multiple])
     lead = tuple(x.shape[:-1])
     groups, rows = (lead if masked_m is not None else (1, lead[0]))
-    if masked_m is not None:
-        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
-                 f"masked_m must be a contiguous int32 [{groups}]")
-    if m_indices is not None:
-        _require(m_indices.dtype == torch.int32 and tuple(m_indices.shape) == (rows,) and m_indices.is_contiguous(),
-                 f"m_indices must be a contiguous int32 [{rows}]")
+    _row_masks(masked_m, m_indices, groups, rows)
     return x.shape[-1] // 2, lead, groups, rows
 
 
-def _fused_out(out, lead: tuple, width: int, blocks: int, device, q_name: str, sf_name: str):
-    """(q [lead, width] bytes, sf [lead, blocks] float32) of a fused quantiser: torch.empty, or the caller's out=(q, sf) checked."""
-    if out is None:
-        return (torch.empty(lead + (width,), dtype=torch.uint8, device=device),
-                torch.empty(lead + (blocks,), dtype=torch.float32, device=device))
-    _require(isinstance(out, (tuple, list)) and len(out) == 2, f"out must be ({q_name}, {sf_name})")
-    q, sf = out
-    _fp8_bytes(q)
-    _require(tuple(q.shape) == lead + (width,) and q.is_contiguous(), f"out {q_name} must be contiguous {list(lead + (width,))}")
-    _require(sf.dtype == torch.float32 and tuple(sf.shape) == lead + (blocks,) and sf.is_contiguous(),
-             f"out {sf_name} must be contiguous float32 {list(lead + (blocks,))}")
-    return q, sf
+def _row_pair(lead: tuple, width: int, q_name: str = "q", sf_name: str = "sf"):
+    """_outputs' specs of per-token codes [lead, width] and their 1x128 scales."""
+    return (q_name, torch.uint8, lead + (width,)), (sf_name, torch.float32, lead + ((width + 127) // 128,))
 
 
 def silu_and_mul_per_token_cast_to_fp8(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
@@ -1022,16 +1074,11 @@ def silu_and_mul_per_token_cast_to_fp8(x: torch.Tensor, masked_m: Optional[torch
     a value.  For gate >= 20 the result is the quantiser's on fl32(gate * up) bit for bit, for |gate| <= 16 the fp32 product is
     within relative 2^-18 of the real-number value; use_ue8m0 as in per_token_cast_to_fp8."""
     h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 2)
-    q, sf = _fused_out(out, lead, h, (h + 127) // 128, x.device, "q", "sf")
-    with _device_guard(x, q, sf, *(t for t in (masked_m, m_indices) if t is not None)):
-        rc = _lib.lib().dga_silu_mul_cast_to_fp8_1x128(
-            x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
-            m_indices.data_ptr() if m_indices is not None else None, q.data_ptr(), sf.data_ptr(),
-            _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
-        _lib.check(rc, "silu_and_mul_per_token_cast_to_fp8")
-        if sync:
-            torch.cuda.current_stream(x.device).synchronize()
-    return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
+    q, sf = _outputs(out, _row_pair(lead, h), x.device, "out must be (q, sf)")
+    _launch("silu_and_mul_per_token_cast_to_fp8", (x, q, sf, masked_m, m_indices), lambda L, stream: L.dga_silu_mul_cast_to_fp8_1x128(
+        x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, _ptr(masked_m), _ptr(m_indices), q.data_ptr(), sf.data_ptr(),
+        _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+    return _as_fp8(q), sf
 
 
 def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
@@ -1052,22 +1099,17 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
     on [fl32(grad_h * up) | fl32(grad_h * gate)] bit for bit; for |gate| <= 16 dup is within relative 2^-18 and dgate within
     2^-17 |grad_h up| (s + |gate| s (1 - s)) of the real-number value."""
     h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 256)
-    _require(tuple(grad_h.shape) == lead + (h,) and grad_h.is_contiguous(), f"grad_h must be contiguous {list(lead + (h,))}")
+    _want(grad_h, "grad_h", None, lead + (h,))
     _require(grad_h.dtype == x.dtype, "grad_h must have x's dtype")
-    q, sf = _fused_out(out, lead, 2 * h, 2 * h // 128, x.device, "dq", "dsf")
+    q, sf = _outputs(out, _row_pair(lead, 2 * h, "dq", "dsf"), x.device, "out must be (dq, dsf)")
     if grad_x_out is not None:
-        _require(tuple(grad_x_out.shape) == tuple(x.shape) and grad_x_out.is_contiguous(), f"grad_x_out must be contiguous {list(x.shape)}")
+        _want(grad_x_out, "grad_x_out", None, tuple(x.shape))
         _require(grad_x_out.dtype == x.dtype, "grad_x_out must have x's dtype")
-    with _device_guard(x, grad_h, q, sf, *(t for t in (masked_m, m_indices, grad_x_out) if t is not None)):
-        rc = _lib.lib().dga_silu_mul_bwd_cast_to_fp8_1x128(
-            x.data_ptr(), grad_h.data_ptr(), _CAST_DT[x.dtype], groups, rows, h,
-            masked_m.data_ptr() if masked_m is not None else None, m_indices.data_ptr() if m_indices is not None else None,
-            q.data_ptr(), sf.data_ptr(), grad_x_out.data_ptr() if grad_x_out is not None else None,
-            _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(x))
-        _lib.check(rc, "silu_and_mul_backward_per_token_cast_to_fp8")
-        if sync:
-            torch.cuda.current_stream(x.device).synchronize()
-    return (q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf
+    _launch("silu_and_mul_backward_per_token_cast_to_fp8", (x, grad_h, q, sf, masked_m, m_indices, grad_x_out),
+            lambda L, stream: L.dga_silu_mul_bwd_cast_to_fp8_1x128(
+                x.data_ptr(), grad_h.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, _ptr(masked_m), _ptr(m_indices), q.data_ptr(),
+                sf.data_ptr(), _ptr(grad_x_out), _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+    return _as_fp8(q), sf
 
 
 def _cast_transposed(c_name: str, name: str, x, h: int, lead: tuple, groups: int, rows: int, masked_m, m_indices, rowwise: bool,
@@ -1077,40 +1119,28 @@ def _cast_transposed(c_name: str, name: str, x, h: int, lead: tuple, groups: int
     (x, masked_m, m_indices) -- call(fn, qt, ldqt, sft, q, sf, flags, stream) -> rc, q and sf pointers or None; also: its further tensors."""
     t_n = groups * rows
     ldqt = (t_n + 127) // 128 * 128 if aligned_rows else t_n
-    tb_n, hb_n = (t_n + 127) // 128, (h + 127) // 128
-    if out is not None:
-        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be ((qt, sft), (q, sf))" if rowwise else "out must be (qt, sft)")
-    out_t, out_r = (out if rowwise else (out, None)) if out is not None else (None, None)
+    out_t, out_r = _nested_out(out, rowwise)
+    sft_shape = (h, (t_n + 127) // 128)
     if out_t is None:
         qt = torch.empty((h, ldqt), dtype=torch.uint8, device=x.device)[:, :t_n]
-        sft = torch.empty((h, tb_n), dtype=torch.float32, device=x.device)
-    else:
+        sft = torch.empty(sft_shape, dtype=torch.float32, device=x.device)
+    else:    # (qt is the one output that need not be contiguous: its rows are ldqt bytes apart)
         _require(isinstance(out_t, (tuple, list)) and len(out_t) == 2, "out must hold (qt, sft)")
         qt, sft = out_t
         _fp8_bytes(qt)
         _require(tuple(qt.shape) == (h, t_n) and (t_n <= 1 or qt.stride(1) == 1) and (h <= 1 or qt.stride(0) == ldqt),
-                 f"out qt must be [{h}, {t_n}] with rows {ldqt} bytes apart")
-        _require(sft.dtype == torch.float32 and tuple(sft.shape) == (h, tb_n) and sft.is_contiguous(),
-                 f"out sft must be contiguous float32 [{h}, {tb_n}]")
-    q, sf = _fused_out(out_r, lead, h, hb_n, x.device, "q", "sf") if rowwise else (None, None)
-    with _device_guard(x, qt, sft, *also, *(t for t in (masked_m, m_indices, q, sf) if t is not None)):
-        fn, flags = getattr(_lib.lib(), c_name), _lib.CAST_UE8M0 if use_ue8m0 else 0
-        if call is not None:
-            rc = call(fn, qt.data_ptr(), ldqt, sft.data_ptr(), q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, flags,
-                      _stream_ptr(x))
-        else:
-            rc = fn(x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, masked_m.data_ptr() if masked_m is not None else None,
-                    m_indices.data_ptr() if m_indices is not None else None, qt.data_ptr(), ldqt, sft.data_ptr(),
-                    q.data_ptr() if rowwise else None, sf.data_ptr() if rowwise else None, flags, _stream_ptr(x))
-        _lib.check(rc, name)
-        if sync:
-            torch.cuda.current_stream(x.device).synchronize()
+                 "out qt must be [%d, %d] with rows %d bytes apart", h, t_n, ldqt)
+        _want(sft, "sft", torch.float32, sft_shape, "out ")
+    q, sf = _outputs(out_r, _row_pair(lead, h), x.device, "out must be (q, sf)") if rowwise else (None, None)
+    flags = _lib.CAST_UE8M0 if use_ue8m0 else 0
+    if call is None:
+        call = lambda fn, *outputs: fn(x.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, _ptr(masked_m), _ptr(m_indices), *outputs)
+    _launch(name, (x, qt, sft, *also, masked_m, m_indices, q, sf), lambda L, stream: call(
+        getattr(L, c_name), qt.data_ptr(), ldqt, sft.data_ptr(), _ptr(q), _ptr(sf), flags, stream), sync)
     qt = qt.view(torch.float8_e4m3fn)   # (always a new tensor object: the promise below is never left on a tensor of the caller's)
     if ldqt != t_n:
         qt._dga_zero_padded = True      # (as _cast: the tails are zero, and views made from qt do not carry the promise)
-    if not rowwise:
-        return qt, sft
-    return (qt, sft), ((q if q.dtype != torch.uint8 else q.view(torch.float8_e4m3fn)), sf)
+    return ((qt, sft), (_as_fp8(q), sf)) if rowwise else (qt, sft)
 
 
 def per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Optional[torch.Tensor] = None, m_indices: Optional[torch.Tensor] = None,
@@ -1183,22 +1213,18 @@ def gather_per_token_cast_to_fp8_transposed(src: torch.Tensor, index: torch.Tens
              "index must be a contiguous int64 [G, Mmax] tensor with masked_m" if masked_m is not None else "index must be a contiguous int64 [T] tensor")
     lead = tuple(index.shape)
     groups, rows = (lead if masked_m is not None else (1, lead[0]))
-    if masked_m is not None:
-        _require(masked_m.dtype == torch.int32 and tuple(masked_m.shape) == (groups,) and masked_m.is_contiguous(),
-                 f"masked_m must be a contiguous int32 [{groups}]")
+    _row_masks(masked_m, None, groups, rows)
     s_n, h = src.shape
     if row_scale is not None:
         _require(row_scale.dtype == torch.float32 and row_scale.numel() == s_n * index_div and row_scale.is_contiguous(),
-                 f"row_scale must be contiguous float32 with {s_n * index_div} elements")
-    call = lambda fn, qt, ldqt, sft, q, sf, flags, stream: fn(
-        src.data_ptr(), _CAST_DT[src.dtype], s_n, h, index.data_ptr(), index_div, row_scale.data_ptr() if row_scale is not None else None,
-        groups, rows, masked_m.data_ptr() if masked_m is not None else None, qt, ldqt, sft, q, sf, flags, stream)
+                 "row_scale must be contiguous float32 with %d elements", s_n * index_div)
+    call = lambda fn, *outputs: fn(src.data_ptr(), _CAST_DT[src.dtype], s_n, h, index.data_ptr(), index_div, _ptr(row_scale), groups, rows,
+                                   _ptr(masked_m), *outputs)
     return _cast_transposed("dga_gather_cast_to_fp8_1x128_transposed", "gather_per_token_cast_to_fp8_transposed", src, h, lead, groups, rows,
-                            masked_m, None, rowwise, aligned_rows, use_ue8m0, out, sync, call=call,
-                            also=(index,) + ((row_scale,) if row_scale is not None else ()))
+                            masked_m, None, rowwise, aligned_rows, use_ue8m0, out, sync, call=call, also=(index, row_scale))
 
 
-def _combine_layout(name: str, src: torch.Tensor, dest: torch.Tensor):
+def _combine_layout(src: torch.Tensor, dest: torch.Tensor):
     """The checks combine_tokens and combine_tokens_weight_grad share: src [S, H], dest int64 [T, k] with k >= 1.  Returns (S, H, T, k)."""
     _require(src.dim() == 2 and src.is_contiguous(), "src must be a contiguous [S, H] tensor")
     _require(src.dtype in _CAST_DT, "src must be float32, bfloat16 or float16")
@@ -1217,22 +1243,16 @@ def combine_tokens(src: torch.Tensor, dest: torch.Tensor, weights: Optional[torc
     (route_slots marks dropped rows with -1), a token without a valid choice gets a row of +0, and every element of out is written.  The
     definition is numpy float32 arithmetic, so a host reference matches bit for bit.  weights=None is the backward of the dispatch,
     dX[t] = sum_j dX_slots[dest[t, j]]."""
-    s_n, h, t_n, k = _combine_layout("combine_tokens", src, dest)
+    s_n, h, t_n, k = _combine_layout(src, dest)
     if weights is not None:
-        _require(weights.dtype == torch.float32 and tuple(weights.shape) == (t_n, k) and weights.is_contiguous(),
-                 f"weights must be contiguous float32 [{t_n}, {k}]")
+        _want(weights, "weights", torch.float32, (t_n, k))
     if out is None:
         out = torch.empty((t_n, h), dtype=src.dtype, device=src.device)
     else:
-        _require(tuple(out.shape) == (t_n, h) and out.is_contiguous(), f"out must be contiguous [{t_n}, {h}]")
+        _want(out, "out", None, (t_n, h))
         _require(out.dtype in (src.dtype, torch.float32), "out must have src's dtype or float32")
-    with _device_guard(src, dest, out, *((weights,) if weights is not None else ())):
-        rc = _lib.lib().dga_combine_rows(src.data_ptr(), _CAST_DT[src.dtype], s_n, h, dest.data_ptr(),
-                                         weights.data_ptr() if weights is not None else None, t_n, k, out.data_ptr(), _CAST_DT[out.dtype],
-                                         _stream_ptr(src))
-        _lib.check(rc, "combine_tokens")
-        if sync:
-            torch.cuda.current_stream(src.device).synchronize()
+    _launch("combine_tokens", (src, dest, out, weights), lambda L, stream: L.dga_combine_rows(
+        src.data_ptr(), _CAST_DT[src.dtype], s_n, h, dest.data_ptr(), _ptr(weights), t_n, k, out.data_ptr(), _CAST_DT[out.dtype], stream), sync)
     return out
 
 
@@ -1242,22 +1262,20 @@ def combine_tokens_weight_grad(src: torch.Tensor, grad: torch.Tensor, dest: torc
     float32 [T, k].  src [S, H] and grad [T, H] contiguous, of one dtype (float32 / bfloat16 / float16), dest int64 [T, k].  Products and
     sums are float32 in a fixed order -- no floating-point atomics, two runs give the same bits --, |dw - exact| <= (H + 2) 2^-24 sum_c
     |src grad|.  A choice whose dest is outside [0, S) gets +0; every element of dw is written; grad[t] is read once per 8 choices."""
-    s_n, h, t_n, k = _combine_layout("combine_tokens_weight_grad", src, dest)
-    _require(grad.dim() == 2 and tuple(grad.shape) == (t_n, h) and grad.is_contiguous(), f"grad must be contiguous [{t_n}, {h}]")
+    s_n, h, t_n, k = _combine_layout(src, dest)
+    _want(grad, "grad", None, (t_n, h))
     _require(grad.dtype == src.dtype, "grad must have src's dtype")
     if out is None:
         out = torch.empty((t_n, k), dtype=torch.float32, device=src.device)
     else:
-        _require(out.dtype == torch.float32 and tuple(out.shape) == (t_n, k) and out.is_contiguous(),
-                 f"out must be contiguous float32 [{t_n}, {k}]")
-    with _device_guard(src, grad, dest, out):
+        _want(out, "out", torch.float32, (t_n, k))
+
+    def call(L, stream):
         if h == 0:
             out.zero_()   # (the C entry touches nothing for an empty row)
-        rc = _lib.lib().dga_combine_rows_weight_grad(src.data_ptr(), grad.data_ptr(), _CAST_DT[src.dtype], s_n, h, dest.data_ptr(), t_n, k,
-                                                     out.data_ptr(), _stream_ptr(src))
-        _lib.check(rc, "combine_tokens_weight_grad")
-        if sync:
-            torch.cuda.current_stream(src.device).synchronize()
+        return L.dga_combine_rows_weight_grad(src.data_ptr(), grad.data_ptr(), _CAST_DT[src.dtype], s_n, h, dest.data_ptr(), t_n, k,
+                                              out.data_ptr(), stream)
+    _launch("combine_tokens_weight_grad", (src, grad, dest, out), call, sync)
     return out
 
 
@@ -1267,6 +1285,15 @@ _SCORE_FUNCS = {"softmax": _lib.ROUTER_SOFTMAX, "sigmoid": _lib.ROUTER_SIGMOID}
 def _router_func(score_func) -> int:
     _require(score_func in _SCORE_FUNCS, 'score_func must be "softmax" or "sigmoid"')
     return _SCORE_FUNCS[score_func]
+
+
+def _dlogits_out(out: Optional[torch.Tensor], t_n: int, e: int, device) -> torch.Tensor:
+    """dlogits [T, E] of the two backward entries: float32 from torch.empty, or the caller's out in any of the three float types."""
+    if out is None:
+        return torch.empty((t_n, e), dtype=torch.float32, device=device)
+    _require(out.dtype in _CAST_DT and tuple(out.shape) == (t_n, e) and out.is_contiguous(),
+             "out must be contiguous [%d, %d], float32, bfloat16 or float16", t_n, e)
+    return out
 
 
 def router_topk(logits: torch.Tensor, k: int, score_func: str = "softmax", bias: Optional[torch.Tensor] = None, n_groups: int = 1,
@@ -1291,28 +1318,14 @@ def router_topk(logits: torch.Tensor, k: int, score_func: str = "softmax", bias:
     _require(all(isinstance(v, int) for v in (k, n_groups, topk_groups)), "k, n_groups and topk_groups must be integers")
     t_n, e = logits.shape
     if bias is not None:
-        _require(bias.dtype == torch.float32 and tuple(bias.shape) == (e,) and bias.is_contiguous(), f"bias must be contiguous float32 [{e}]")
+        _want(bias, "bias", torch.float32, (e,))
     if out is None:
         _require(k >= 1, "k must be >= 1")
-        ids = torch.empty((t_n, k), dtype=torch.int32, device=logits.device)
-        weights = torch.empty((t_n, k), dtype=torch.float32, device=logits.device)
-        scores = torch.empty((t_n, e), dtype=torch.float32, device=logits.device)
-    else:
-        _require(isinstance(out, (tuple, list)) and len(out) == 3 and all(isinstance(t, torch.Tensor) for t in out),
-                 "out must hold (ids, weights, scores)")
-        ids, weights, scores = out
-        _require(ids.dtype == torch.int32 and tuple(ids.shape) == (t_n, k) and ids.is_contiguous(), f"out ids must be contiguous int32 [{t_n}, {k}]")
-        _require(weights.dtype == torch.float32 and tuple(weights.shape) == (t_n, k) and weights.is_contiguous(),
-                 f"out weights must be contiguous float32 [{t_n}, {k}]")
-        _require(scores.dtype == torch.float32 and tuple(scores.shape) == (t_n, e) and scores.is_contiguous(),
-                 f"out scores must be contiguous float32 [{t_n}, {e}]")
-    with _device_guard(logits, ids, weights, scores, *((bias,) if bias is not None else ())):
-        rc = _lib.lib().dga_router_topk(logits.data_ptr(), _CAST_DT[logits.dtype], t_n, e, k, func, bias.data_ptr() if bias is not None else None,
-                                        n_groups, topk_groups, _lib.ROUTER_RENORMALIZE if renormalize else 0, float(scale), ids.data_ptr(),
-                                        weights.data_ptr(), scores.data_ptr(), _stream_ptr(logits))
-        _lib.check(rc, "router_topk")
-        if sync:
-            torch.cuda.current_stream(logits.device).synchronize()
+    ids, weights, scores = _outputs(out, (("ids", torch.int32, (t_n, k)), ("weights", torch.float32, (t_n, k)), ("scores", torch.float32, (t_n, e))),
+                                    logits.device, "out must hold (ids, weights, scores)")
+    _launch("router_topk", (logits, ids, weights, scores, bias), lambda L, stream: L.dga_router_topk(
+        logits.data_ptr(), _CAST_DT[logits.dtype], t_n, e, k, func, _ptr(bias), n_groups, topk_groups, _lib.ROUTER_RENORMALIZE if renormalize else 0,
+        float(scale), ids.data_ptr(), weights.data_ptr(), scores.data_ptr(), stream), sync)
     return ids, weights, scores
 
 
@@ -1329,21 +1342,13 @@ def router_topk_backward(dw: torch.Tensor, scores: torch.Tensor, ids: torch.Tens
     _require(scores.dtype == torch.float32 and scores.dim() == 2 and scores.is_contiguous(), "scores must be a contiguous float32 [T, E] tensor")
     t_n, e = scores.shape
     _require(ids.dtype == torch.int32 and ids.dim() == 2 and ids.shape[0] == t_n and ids.is_contiguous(),
-             f"ids must be a contiguous int32 [{t_n}, k] tensor")
+             "ids must be a contiguous int32 [%d, k] tensor", t_n)
     k = ids.shape[1]
-    _require(dw.dtype == torch.float32 and tuple(dw.shape) == (t_n, k) and dw.is_contiguous(), f"dw must be contiguous float32 [{t_n}, {k}]")
-    if out is None:
-        out = torch.empty((t_n, e), dtype=torch.float32, device=scores.device)
-    else:
-        _require(out.dtype in _CAST_DT and tuple(out.shape) == (t_n, e) and out.is_contiguous(),
-                 f"out must be contiguous [{t_n}, {e}], float32, bfloat16 or float16")
-    with _device_guard(dw, scores, ids, out):
-        rc = _lib.lib().dga_router_topk_backward(dw.data_ptr(), scores.data_ptr(), ids.data_ptr(), t_n, e, k, func,
-                                                 _lib.ROUTER_RENORMALIZE if renormalize else 0, float(scale), out.data_ptr(),
-                                                 _CAST_DT[out.dtype], _stream_ptr(scores))
-        _lib.check(rc, "router_topk_backward")
-        if sync:
-            torch.cuda.current_stream(scores.device).synchronize()
+    _want(dw, "dw", torch.float32, (t_n, k))
+    out = _dlogits_out(out, t_n, e, scores.device)
+    _launch("router_topk_backward", (scores, dw, ids, out), lambda L, stream: L.dga_router_topk_backward(
+        dw.data_ptr(), scores.data_ptr(), ids.data_ptr(), t_n, e, k, func, _lib.ROUTER_RENORMALIZE if renormalize else 0, float(scale),
+        out.data_ptr(), _CAST_DT[out.dtype], stream), sync)
     return out
 
 
@@ -1353,7 +1358,7 @@ def _balance_shape(scores: torch.Tensor, k, seq_len, alpha) -> Tuple[int, int, i
     t_n, e = scores.shape
     seq = (t_n if t_n else 1) if seq_len is None else seq_len
     _require(isinstance(k, int) and isinstance(seq, int) and k >= 1 and seq >= 1, "k and seq_len must be integers >= 1")
-    _require(t_n % seq == 0, f"seq_len must divide the {t_n} tokens")
+    _require(t_n % seq == 0, "seq_len must divide the %d tokens", t_n)
     return t_n, e, seq, t_n // seq, float(alpha) * e / (float(k) * seq * seq)
 
 
@@ -1377,29 +1382,15 @@ def router_balance_loss(scores: torch.Tensor, ids: torch.Tensor, seq_len: Option
     host: the entry can be captured.  1 <= k <= E <= 1024, k <= 64."""
     _require(ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous(), "ids must be a contiguous int32 [T, k] tensor")
     t_n, e, seq, b_n, coef = _balance_shape(scores, ids.shape[1], seq_len, alpha)
-    _require(ids.shape[0] == t_n, f"ids must hold {t_n} rows")
-    if out is None:
-        loss = torch.empty((b_n,), dtype=torch.float32, device=scores.device)
-        counts = torch.empty((b_n, e), dtype=torch.int32, device=scores.device)
-        psum = torch.empty((b_n, e), dtype=torch.float32, device=scores.device)
-    else:
-        _require(isinstance(out, (tuple, list)) and len(out) == 3 and all(isinstance(t, torch.Tensor) for t in out),
-                 "out must hold (loss, counts, psum)")
-        loss, counts, psum = out
-        _require(loss.dtype == torch.float32 and tuple(loss.shape) == (b_n,) and loss.is_contiguous(), f"out loss must be contiguous float32 [{b_n}]")
-        _require(counts.dtype == torch.int32 and tuple(counts.shape) == (b_n, e) and counts.is_contiguous(),
-                 f"out counts must be contiguous int32 [{b_n}, {e}]")
-        _require(psum.dtype == torch.float32 and tuple(psum.shape) == (b_n, e) and psum.is_contiguous(),
-                 f"out psum must be contiguous float32 [{b_n}, {e}]")
-    with _device_guard(scores, ids, loss, counts, psum):
-        L = _lib.lib()
+    _require(ids.shape[0] == t_n, "ids must hold %d rows", t_n)
+    loss, counts, psum = _outputs(out, (("loss", torch.float32, (b_n,)), ("counts", torch.int32, (b_n, e)), ("psum", torch.float32, (b_n, e))),
+                                  scores.device, "out must hold (loss, counts, psum)")
+
+    def call(L, stream):
         ws_ptr, ws_bytes = _scratch("balance", scores.device, int(L.dga_router_balance_loss_workspace_bytes(t_n, e, seq)))
-        rc = L.dga_router_balance_loss(scores.data_ptr(), ids.data_ptr(), t_n, e, ids.shape[1], seq,
-                                       _lib.ROUTER_BALANCE_NORMALIZE if normalize else 0, coef, loss.data_ptr(), counts.data_ptr(),
-                                       psum.data_ptr(), ws_ptr, ws_bytes, _stream_ptr(scores))
-        _lib.check(rc, "router_balance_loss")
-        if sync:
-            torch.cuda.current_stream(scores.device).synchronize()
+        return L.dga_router_balance_loss(scores.data_ptr(), ids.data_ptr(), t_n, e, ids.shape[1], seq, _lib.ROUTER_BALANCE_NORMALIZE if normalize else 0,
+                                         coef, loss.data_ptr(), counts.data_ptr(), psum.data_ptr(), ws_ptr, ws_bytes, stream)
+    _launch("router_balance_loss", (scores, ids, loss, counts, psum), call, sync)
     return loss, counts, psum
 
 
@@ -1416,25 +1407,14 @@ def router_balance_loss_backward(dloss: torch.Tensor, counts: torch.Tensor, scor
     without it, so the step's dlogits is complete after this call.  One wave per token, fixed order, no atomics."""
     func = _router_func(score_func)
     t_n, e, seq, b_n, coef = _balance_shape(scores, k, seq_len, alpha)
-    _require(dloss.dtype == torch.float32 and tuple(dloss.shape) == (b_n,) and dloss.is_contiguous(), f"dloss must be contiguous float32 [{b_n}]")
-    _require(counts.dtype == torch.int32 and tuple(counts.shape) == (b_n, e) and counts.is_contiguous(),
-             f"counts must be contiguous int32 [{b_n}, {e}]")
+    _want(dloss, "dloss", torch.float32, (b_n,))
+    _want(counts, "counts", torch.int32, (b_n, e))
     if add_to is not None:
-        _require(add_to.dtype == torch.float32 and tuple(add_to.shape) == (t_n, e) and add_to.is_contiguous(),
-                 f"add_to must be contiguous float32 [{t_n}, {e}]")
-    if out is None:
-        out = torch.empty((t_n, e), dtype=torch.float32, device=scores.device)
-    else:
-        _require(out.dtype in _CAST_DT and tuple(out.shape) == (t_n, e) and out.is_contiguous(),
-                 f"out must be contiguous [{t_n}, {e}], float32, bfloat16 or float16")
-    with _device_guard(dloss, counts, scores, out, *((add_to,) if add_to is not None else ())):
-        rc = _lib.lib().dga_router_balance_loss_backward(dloss.data_ptr(), counts.data_ptr(), scores.data_ptr(), t_n, e, k, seq, func,
-                                                         _lib.ROUTER_BALANCE_NORMALIZE if normalize else 0, coef,
-                                                         add_to.data_ptr() if add_to is not None else None, out.data_ptr(),
-                                                         _CAST_DT[out.dtype], _stream_ptr(scores))
-        _lib.check(rc, "router_balance_loss_backward")
-        if sync:
-            torch.cuda.current_stream(scores.device).synchronize()
+        _want(add_to, "add_to", torch.float32, (t_n, e))
+    out = _dlogits_out(out, t_n, e, scores.device)
+    _launch("router_balance_loss_backward", (scores, dloss, counts, out, add_to), lambda L, stream: L.dga_router_balance_loss_backward(
+        dloss.data_ptr(), counts.data_ptr(), scores.data_ptr(), t_n, e, k, seq, func, _lib.ROUTER_BALANCE_NORMALIZE if normalize else 0, coef,
+        _ptr(add_to), out.data_ptr(), _CAST_DT[out.dtype], stream), sync)
     return out
 
 
@@ -1446,28 +1426,10 @@ def router_bias_update(bias: torch.Tensor, counts: torch.Tensor, rate: float, sy
     _require(bias.dtype == torch.float32 and bias.dim() == 1 and bias.is_contiguous(), "bias must be a contiguous float32 [E] tensor")
     e = bias.shape[0]
     _require(counts.dtype == torch.int32 and counts.dim() == 2 and counts.shape[1] == e and counts.is_contiguous(),
-             f"counts must be a contiguous int32 [B, {e}] tensor")
-    with _device_guard(bias, counts):
-        rc = _lib.lib().dga_router_bias_update(bias.data_ptr(), counts.data_ptr(), counts.shape[0], e, float(rate), _stream_ptr(bias))
-        _lib.check(rc, "router_bias_update")
-        if sync:
-            torch.cuda.current_stream(bias.device).synchronize()
+             "counts must be a contiguous int32 [B, %d] tensor", e)
+    _launch("router_bias_update", (bias, counts), lambda L, stream: L.dga_router_bias_update(
+        bias.data_ptr(), counts.data_ptr(), counts.shape[0], e, float(rate), stream), sync)
     return bias
-
-
-def _block_out(out, q_shape: tuple, sf_shape: tuple, device, q_name: str, sf_name: str):
-    """_fused_out for the weight quantiser, whose codes and scales do not share their leading dimensions: (q q_shape bytes, sf sf_shape
-    float32), torch.empty or the caller's out=(q, sf) checked."""
-    if out is None:
-        return torch.empty(q_shape, dtype=torch.uint8, device=device), torch.empty(sf_shape, dtype=torch.float32, device=device)
-    _require(isinstance(out, (tuple, list)) and len(out) == 2 and all(isinstance(t, torch.Tensor) for t in out),
-             f"out must hold ({q_name}, {sf_name})")
-    q, sf = out
-    _fp8_bytes(q)
-    _require(tuple(q.shape) == q_shape and q.is_contiguous(), f"out {q_name} must be contiguous {list(q_shape)}")
-    _require(sf.dtype == torch.float32 and tuple(sf.shape) == sf_shape and sf.is_contiguous(),
-             f"out {sf_name} must be contiguous float32 {list(sf_shape)}")
-    return q, sf
 
 
 def per_block_cast_to_fp8_transposed(w: torch.Tensor, rowwise: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):
@@ -1487,22 +1449,14 @@ def per_block_cast_to_fp8_transposed(w: torch.Tensor, rowwise: bool = False, use
     groups = lead[0] if lead else 1
     n, k = w.shape[-2:]
     nb, kb = (n + 127) // 128, (k + 127) // 128
-    if out is not None:
-        _require(isinstance(out, (tuple, list)) and len(out) == 2, "out must be ((qt, sft), (q, sf))" if rowwise else "out must be (qt, sft)")
-    out_t, out_r = (out if rowwise else (out, None)) if out is not None else (None, None)
-    qt, sft = _block_out(out_t, lead + (k, n), lead + (kb, nb), w.device, "qt", "sft")
-    q, sf = _block_out(out_r, lead + (n, k), lead + (nb, kb), w.device, "q", "sf") if rowwise else (None, None)
-    with _device_guard(w, qt, sft, *(t for t in (q, sf) if t is not None)):
-        rc = _lib.lib().dga_cast_to_fp8_128x128_transposed(
-            w.data_ptr(), _CAST_DT[w.dtype], groups, n, k, qt.data_ptr(), sft.data_ptr(), q.data_ptr() if rowwise else None,
-            sf.data_ptr() if rowwise else None, _lib.CAST_UE8M0 if use_ue8m0 else 0, _stream_ptr(w))
-        _lib.check(rc, "per_block_cast_to_fp8_transposed")
-        if sync:
-            torch.cuda.current_stream(w.device).synchronize()
-    f8 = lambda t: t if t.dtype != torch.uint8 else t.view(torch.float8_e4m3fn)
-    if not rowwise:
-        return f8(qt), sft
-    return (f8(qt), sft), (f8(q), sf)
+    out_t, out_r = _nested_out(out, rowwise)
+    qt, sft = _outputs(out_t, (("qt", torch.uint8, lead + (k, n)), ("sft", torch.float32, lead + (kb, nb))), w.device, "out must hold (qt, sft)")
+    q, sf = _outputs(out_r, (("q", torch.uint8, lead + (n, k)), ("sf", torch.float32, lead + (nb, kb))), w.device,
+                     "out must hold (q, sf)") if rowwise else (None, None)
+    _launch("per_block_cast_to_fp8_transposed", (w, qt, sft, q, sf), lambda L, stream: L.dga_cast_to_fp8_128x128_transposed(
+        w.data_ptr(), _CAST_DT[w.dtype], groups, n, k, qt.data_ptr(), sft.data_ptr(), _ptr(q), _ptr(sf), _lib.CAST_UE8M0 if use_ue8m0 else 0,
+        stream), sync)
+    return ((_as_fp8(qt), sft), (_as_fp8(q), sf)) if rowwise else (_as_fp8(qt), sft)
 
 
 def route_tokens(expert_ids: torch.Tensor, groups: int):
@@ -1510,10 +1464,8 @@ def route_tokens(expert_ids: torch.Tensor, groups: int):
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")
     counts = torch.empty((groups,), dtype=torch.int64, device=expert_ids.device)
     pos = torch.empty((expert_ids.numel(),), dtype=torch.int64, device=expert_ids.device)
-    with _device_guard(expert_ids):
-        rc = _lib.lib().dga_route_tokens(expert_ids.data_ptr(), expert_ids.numel(), groups, counts.data_ptr(), pos.data_ptr(),
-                                         _stream_ptr(expert_ids))
-        _lib.check(rc, "route_tokens")
+    _launch("route_tokens", (expert_ids,), lambda L, stream: L.dga_route_tokens(
+        expert_ids.data_ptr(), expert_ids.numel(), groups, counts.data_ptr(), pos.data_ptr(), stream))
     return counts, pos
 
 
@@ -1531,13 +1483,10 @@ def route_slots(keys: torch.Tensor, key_stride_bytes: int, rows: int, buckets: i
     _require(counts.dtype == torch.int32 and counts.numel() >= buckets and counts.is_contiguous(), "counts int32[buckets]")
     _require(dest.dtype == torch.int64 and dest.numel() >= rows and dest.is_contiguous(), "dest int64[rows]")
     _require(overflow.dtype == torch.int32 and overflow.numel() >= 1, "overflow int32[1]")
-    with _device_guard(keys, counts, dest, overflow):
-        rc = _lib.lib().dga_route_slots(keys.data_ptr() + keys_byte_offset, key_stride_bytes, rows, key_div, key_sub, key_mul,
-                                        buckets, cap, counts.data_ptr(), 1 if zero_counts else 0, dest.data_ptr(),
-                                        (tags.data_ptr() + tags_byte_offset) if tags is not None else None,
-                                        tag_stride_bytes, overflow.data_ptr(),
-                                        inverse.data_ptr() if inverse is not None else None, inverse_base, _stream_ptr(dest))
-        _lib.check(rc, "route_slots")
+    _launch("route_slots", (dest, keys, counts, overflow), lambda L, stream: L.dga_route_slots(
+        keys.data_ptr() + keys_byte_offset, key_stride_bytes, rows, key_div, key_sub, key_mul, buckets, cap, counts.data_ptr(),
+        1 if zero_counts else 0, dest.data_ptr(), (tags.data_ptr() + tags_byte_offset) if tags is not None else None, tag_stride_bytes,
+        overflow.data_ptr(), _ptr(inverse), inverse_base, stream))
 
 
 def copy_rows(dst: torch.Tensor, src: torch.Tensor, dst_index: Optional[torch.Tensor] = None,
@@ -1551,12 +1500,9 @@ def copy_rows(dst: torch.Tensor, src: torch.Tensor, dst_index: Optional[torch.Te
     for ix in (dst_index, src_index):
         if ix is not None:
             _require(ix.dtype == torch.int64 and ix.is_contiguous() and ix.numel() >= n, "index must be int64[rows]")
-    with _device_guard(dst, src):
-        rc = _lib.lib().dga_copy_rows(dst.data_ptr() + dst_byte_offset, dst.stride(0) * dst.element_size(),
-                                      dst_index.data_ptr() if dst_index is not None else None,
-                                      src.data_ptr() + src_byte_offset, src.stride(0) * src.element_size(),
-                                      src_index.data_ptr() if src_index is not None else None, rb, n, _stream_ptr(dst))
-        _lib.check(rc, "copy_rows")
+    _launch("copy_rows", (dst, src), lambda L, stream: L.dga_copy_rows(
+        dst.data_ptr() + dst_byte_offset, dst.stride(0) * dst.element_size(), _ptr(dst_index),
+        src.data_ptr() + src_byte_offset, src.stride(0) * src.element_size(), _ptr(src_index), rb, n, stream))
 
 
 def copy_rows2(dst0, src0, bytes0, dst1, src1, bytes1, dst_index=None, src_index=None, rows=None,
@@ -1568,12 +1514,9 @@ def copy_rows2(dst0, src0, bytes0, dst1, src1, bytes1, dst_index=None, src_index
     n = rows if rows is not None else (dst_index.numel() if dst_index is not None else
                                        src_index.numel() if src_index is not None else src0.shape[0])
     rs = lambda t: t.stride(0) * t.element_size()
-    with _device_guard(dst0, src0, dst1, src1):
-        rc = _lib.lib().dga_copy_rows2(dst0.data_ptr() + dst0_off, rs(dst0), src0.data_ptr() + src0_off, rs(src0), bytes0,
-                                       dst1.data_ptr() + dst1_off, rs(dst1), src1.data_ptr() + src1_off, rs(src1), bytes1,
-                                       dst_index.data_ptr() if dst_index is not None else None,
-                                       src_index.data_ptr() if src_index is not None else None, n, _stream_ptr(dst0))
-        _lib.check(rc, "copy_rows2")
+    _launch("copy_rows2", (dst0, src0, dst1, src1), lambda L, stream: L.dga_copy_rows2(
+        dst0.data_ptr() + dst0_off, rs(dst0), src0.data_ptr() + src0_off, rs(src0), bytes0,
+        dst1.data_ptr() + dst1_off, rs(dst1), src1.data_ptr() + src1_off, rs(src1), bytes1, _ptr(dst_index), _ptr(src_index), n, stream))
 
 
 # ----------------------------------------------------------------------------- the framework's 16-bit entry points

@@ -1,0 +1,72 @@
+"""Host time per call of the Python wrappers (deepgemm_ascend_amd/api.py), in the manner of profiles/r03_host_overhead.txt: each row issues
+2000 back-to-back calls on the current stream and synchronises once at the end; "host" is the wall time of the issuing loop per call.  A row is
+warmed up first (plans, scratch and the allocator's blocks exist) and measured in three such windows: the fastest is the figure, all three
+are printed (their spread is this measurement's noise within one process; between two processes, run it twice).  The shapes are short on
+purpose -- the device finishes a call before the host has issued the next, so the loop never waits for the queue.
+Usage: python scripts/api_host_time.py [--calls 2000] [--windows 3]        (results: profiles/api_host_time.txt)"""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+import deepgemm_ascend_amd as dga  # noqa: E402
+
+
+def rows():
+    """(label, call) for every row; the tensors live in the closures."""
+    dev = "cuda"
+    bf = lambda *shape: torch.randn(*shape, device=dev).to(torch.bfloat16)
+    m, n, k = 64, 32768, 512
+    a, b, out = dga.per_token_cast_to_fp8(bf(m, k)), dga.per_block_cast_to_fp8(bf(n, k)), torch.empty(m, n, dtype=torch.bfloat16, device=dev)
+    yield f"gemm_fp8_fp8_bf16_nt {m}x{n}x{k}, tiling looked up", lambda: dga.gemm_fp8_fp8_bf16_nt(a, b, out)
+
+    g, mmax, n, k = 4, 64, 512, 512
+    qa, sfa = dga.per_token_cast_to_fp8(bf(g * mmax, k))
+    qb, sfb = dga.per_block_cast_to_fp8_transposed(bf(g, k, n))   # [G, N, K] codes, [G, N/128, K/128] scales
+    lhs, rhs = (qa.view(g, mmax, k), sfa.view(g, mmax, -1)), (qb, sfb)
+    outg, masked = torch.empty(g, mmax, n, dtype=torch.bfloat16, device=dev), torch.tensor([64, 1, 33, 0], dtype=torch.int32, device=dev)
+    yield (f"m_grouped_gemm_fp8_fp8_bf16_nt_masked G{g} Mmax{mmax} N{n} K{k}",
+           lambda: dga.m_grouped_gemm_fp8_fp8_bf16_nt_masked(lhs, rhs, outg, masked, mmax))
+
+    x = bf(64, 2 * 512)
+    q_sf = dga.silu_and_mul_per_token_cast_to_fp8(x)
+    yield "silu_and_mul_per_token_cast_to_fp8 64x(2x512)", lambda: dga.silu_and_mul_per_token_cast_to_fp8(x)
+    yield "silu_and_mul_per_token_cast_to_fp8 64x(2x512), out=", lambda: dga.silu_and_mul_per_token_cast_to_fp8(x, out=q_sf)
+
+    logits = torch.randn(64, 256, device=dev)
+    gate = dga.router_topk(logits, 8)
+    yield "router_topk T64 E256 k8", lambda: dga.router_topk(logits, 8)
+    yield "router_topk T64 E256 k8, out=", lambda: dga.router_topk(logits, 8, out=gate)
+
+    src, weights = bf(64 * 8, 512), gate[1]
+    dest = torch.randperm(64 * 8, device=dev).view(64, 8)
+    yield "combine_tokens T64 k8 H512", lambda: dga.combine_tokens(src, dest, weights)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=2000)
+    ap.add_argument("--windows", type=int, default=3)
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    for label, call in rows():
+        for _ in range(200):
+            call()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(args.windows):
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                call()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            us.append((t1 - t0) / args.calls * 1e6)
+        print(f"{label:<64}: host {min(us):6.2f} us/call issued   (windows: {' '.join(f'{u:.2f}' for u in us)})", flush=True)
+
+
+if __name__ == "__main__":
+    main()
