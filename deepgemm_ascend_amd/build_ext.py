@@ -1,6 +1,6 @@
 """Builds the `deep_gemm_cpp` torch extension in-tree (deepgemm_ascend_amd/deep_gemm_cpp*.so) from
 csrc/python_api_amd.cpp -- the MI355X counterpart of the reference's pybind module
-(/root/reference/deep_gemm_ascend/framework/csrc/python_api.cpp:30-36; its CMake build links torch_npu + ACL,
+(deep_gemm_ascend/framework/csrc/python_api.cpp:30-36; its CMake build links torch_npu + ACL,
 framework/CMakeLists.txt:44-47).  One hipcc invocation on host code: no hipify pass, no JIT cache outside the tree.
 The module links libdga_hip.so next to it (rpath $ORIGIN)."""
 from __future__ import annotations

@@ -3,8 +3,12 @@
 warmed up first (plans, scratch and the allocator's blocks exist) and measured in three such windows: the fastest is the figure, all three
 are printed (their spread is this measurement's noise within one process; between two processes, run it twice).  The shapes are short on
 purpose -- the device finishes a call before the host has issued the next, so the loop never waits for the queue.
-Usage: python scripts/api_host_time.py [--calls 2000] [--windows 3]        (results: profiles/api_host_time.txt)"""
+--ext times the pybind extension deep_gemm_cpp (csrc/python_api_amd.cpp) in the same way: the built module in the package, or the one at
+PATH (a build of another commit, to compare with; its file may have any name, and it finds libdga_hip.so beside itself).
+Usage: python scripts/api_host_time.py [--calls 2000] [--windows 3]        (results: profiles/api_host_time.txt)
+       python scripts/api_host_time.py --ext [PATH]                        (results: profiles/ext_host_time.txt)"""
 import argparse
+import importlib.util
 import sys
 import time
 from pathlib import Path
@@ -47,13 +51,54 @@ def rows():
     yield "combine_tokens T64 k8 H512", lambda: dga.combine_tokens(src, dest, weights)
 
 
+def load_ext(path):
+    if not path:
+        from deepgemm_ascend_amd import deep_gemm_cpp
+        return deep_gemm_cpp
+    spec = importlib.util.spec_from_file_location("deep_gemm_cpp", path)
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
+def ext_rows(d):
+    """The same, through the bindings of the extension module d: positional tensors, outputs allocated by the caller of the GEMMs."""
+    dev = "cuda"
+    bf = lambda *shape: torch.randn(*shape, device=dev).to(torch.bfloat16)
+    m, n, k = 64, 32768, 512
+    (a, sfa), (b, sfb), out = d.per_token_cast_to_fp8(bf(m, k)), d.per_block_cast_to_fp8(bf(n, k)), torch.empty(m, n, dtype=torch.bfloat16, device=dev)
+    yield f"gemm_fp8_fp8_bf16_nt {m}x{n}x{k}", lambda: d.gemm_fp8_fp8_bf16_nt(a, sfa, b, sfb, out)
+
+    g, mmax, n, k = 4, 64, 512, 512
+    qa, sa = d.per_token_cast_to_fp8(bf(g * mmax, k))
+    qb, sb = d.per_block_cast_to_fp8_transposed(bf(g, k, n))
+    qa, sa = qa.view(g, mmax, k), sa.view(g, mmax, -1)
+    outg, masked = torch.empty(g, mmax, n, dtype=torch.bfloat16, device=dev), torch.tensor([64, 1, 33, 0], dtype=torch.int32, device=dev)
+    yield (f"m_grouped_gemm_fp8_fp8_bf16_nt_masked G{g} Mmax{mmax} N{n} K{k}",
+           lambda: d.m_grouped_gemm_fp8_fp8_bf16_nt_masked(qa, sa, qb, sb, outg, masked, mmax))
+
+    m, n, k = 64, 512, 512
+    (a2, sfa2), (b2, sfb2), acc = d.per_token_cast_to_fp8(bf(m, k)), d.per_block_cast_to_fp8(bf(n, k)), torch.zeros(m, n, device=dev)
+    yield f"gemm_fp8_fp8_fp32_nt {m}x{n}x{k}, c=out", lambda: d.gemm_fp8_fp8_fp32_nt(a2, sfa2, b2, sfb2, acc, acc)
+
+    x = bf(64, 2 * 512)
+    yield "silu_and_mul_per_token_cast_to_fp8 64x(2x512)", lambda: d.silu_and_mul_per_token_cast_to_fp8(x)
+    xt = bf(64, 512)
+    yield "per_token_cast_to_fp8_transposed 64x512", lambda: d.per_token_cast_to_fp8_transposed(xt)
+
+    src, weights = bf(64 * 8, 512), torch.rand(64, 8, device=dev)
+    dest = torch.randperm(64 * 8, device=dev).view(64, 8)
+    yield "combine_tokens T64 k8 H512", lambda: d.combine_tokens(src, dest, weights)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--ext", nargs="?", const="", default=None, metavar="PATH")
     args = ap.parse_args()
     torch.manual_seed(0)
-    for label, call in rows():
+    for label, call in rows() if args.ext is None else ext_rows(load_ext(args.ext)):
         for _ in range(200):
             call()
         torch.cuda.synchronize()
