@@ -170,6 +170,11 @@ SIGNATURES = {
     "dga_router_balance_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_float,
                                                  c_void_p, c_void_p, c_int, c_void_p]),
     "dga_router_bias_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p]),
+    "dga_rms_norm_cast_to_fp8_1x128": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int, c_void_p]),
+    "dga_rms_norm_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_int64, c_void_p]),
+    "dga_rms_norm_backward_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "dga_catlass_dynamic_matmul_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "dga_catlass_dynamic_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                            c_void_p]),

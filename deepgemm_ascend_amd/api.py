@@ -16,6 +16,7 @@ PyTorch is used only for device memory and the current stream.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 from typing import Optional, Sequence, Tuple
@@ -1430,6 +1431,117 @@ def router_bias_update(bias: torch.Tensor, counts: torch.Tensor, rate: float, sy
     _launch("router_bias_update", (bias, counts), lambda L, stream: L.dga_router_bias_update(
         bias.data_ptr(), counts.data_ptr(), counts.shape[0], e, float(rate), stream), sync)
     return bias
+
+
+RmsNormCast = collections.namedtuple("RmsNormCast", ("q", "sf", "norm", "residual", "rstd"))
+RMS_NORM_MAX_H = 16384
+
+
+def _norm_operands(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int]:
+    """The row tensor and the weight the two norm entries share, checked -> (T, H)."""
+    _require(x.dim() == 2 and x.is_contiguous(), "%s must be a contiguous [T, H] tensor", what)
+    _require(x.dtype in _CAST_DT, "%s must be float32, bfloat16 or float16", what)
+    t_n, h = x.shape
+    _require(1 <= h <= RMS_NORM_MAX_H, "H must be in [1, %d]", RMS_NORM_MAX_H)
+    _want(weight, "weight", (x.dtype, torch.float32), (h,))
+    return t_n, h
+
+
+def rms_norm_per_token_cast_to_fp8(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, residual: Optional[torch.Tensor] = None,
+                                   quantize: bool = True, norm_out: bool = False, out=None, use_ue8m0: bool = False,
+                                   sync: bool = False) -> RmsNormCast:
+    """The norm in front of an MoE block fused into the quantiser of what reads it (dga_rms_norm_cast_to_fp8_1x128): x [T, H] contiguous
+    float32 / bfloat16 / float16, weight [H] of x's dtype or float32, residual None or like x, 1 <= H <= 16384, eps >= 0 finite -> the named
+    tuple (q, sf, norm, residual, rstd), None for what was not asked.  Per row, in float32, every operation rounded on its own:
+      z = x, or with residual the STORED residual out = RNE(fl(x + residual)) -- what rms_norm_backward reads;
+      rstd ~ (mean(z^2) + eps)^(-1/2), float32 [T], always returned: |rstd - exact| <= (H / 2 + 6) 2^-24 exact against float64 on z, its sum
+      in an order (H, dtype) alone fixes -- a row's result does not depend on T or on where the row sits, and two runs give the same bits;
+      y = fl(fl(z rstd) weight), a NaN replaced by the one NaN 0x7FC00000;  norm = RNE(y) in x's dtype (norm_out=True);
+      (q, sf) = per_token_cast_to_fp8(y, use_ue8m0=...) on the float32 y, byte for byte (quantize=True): y never passes through 16 bits.
+    Everything below rstd is an exact float32 function of the rstd returned.  Nothing is rescaled: squares that overflow give rstd = 0 and
+    y = +-0; a NaN makes its own row's rstd NaN and its codes 0x7F and touches no other row.  One of quantize and norm_out must be set
+    (norm_out alone is a fused add + RMSNorm).  out: a mapping or an RmsNormCast with the caller's tensors under the same names (q uint8
+    or float8_e4m3fn; residual may be the input residual or x: in place); what it leaves out is allocated.  One launch, capturable."""
+    t_n, h = _norm_operands(x, weight, "x")
+    if residual is not None:
+        _want(residual, "residual", x.dtype, (t_n, h))
+    eps = float(eps)
+    _require(eps >= 0.0 and eps != float("inf"), "eps must be finite and >= 0")
+    _require(quantize or norm_out, "one of quantize and norm_out must be set")
+    given = {} if out is None else out._asdict() if isinstance(out, RmsNormCast) else out
+    _require(isinstance(given, dict) and all(k in RmsNormCast._fields and (v is None or isinstance(v, torch.Tensor)) for k, v in given.items()),
+             "out must map q, sf, norm, residual, rstd to tensors")
+    asked = {"q": quantize, "sf": quantize, "norm": norm_out, "residual": residual is not None, "rstd": True}
+    specs = {"q": (torch.uint8, (t_n, h)), "sf": (torch.float32, (t_n, (h + 127) // 128)), "norm": (x.dtype, (t_n, h)),
+             "residual": (x.dtype, (t_n, h)), "rstd": (torch.float32, (t_n,))}
+    o = {}
+    for name, (dtype, shape) in specs.items():
+        t = given.get(name)
+        if not asked[name]:
+            _require(t is None, "out %s is given but not asked for", name)
+            o[name] = None
+        elif t is None:
+            o[name] = torch.empty(shape, dtype=dtype, device=x.device)
+        else:
+            if name == "q":
+                _fp8_bytes(t)
+            _want(t, name, None if name == "q" else dtype, shape, "out ")
+            o[name] = t
+    _launch("rms_norm_per_token_cast_to_fp8", (x, weight, residual) + tuple(o.values()), lambda L, stream: L.dga_rms_norm_cast_to_fp8_1x128(
+        x.data_ptr(), _ptr(residual), _CAST_DT[x.dtype], weight.data_ptr(), _CAST_DT[weight.dtype], t_n, h, eps, _ptr(o["q"]), _ptr(o["sf"]),
+        _ptr(o["norm"]), _ptr(o["residual"]), o["rstd"].data_ptr(), _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+    if o["q"] is not None:
+        o["q"] = _as_fp8(o["q"])
+    return RmsNormCast(**o)
+
+
+def rms_norm_backward_workspace_bytes(rows: int, h: int) -> int:
+    """Bytes of scratch rms_norm_backward takes for dweight (dga_rms_norm_backward_workspace_bytes): 4 chunks H, one float32 partial [H] for
+    each chunk of max(8, ceil(T / 1024)) consecutive rows."""
+    return int(_lib.lib().dga_rms_norm_backward_workspace_bytes(rows, h))
+
+
+def rms_norm_backward(grad_y: torch.Tensor, z: torch.Tensor, weight: torch.Tensor, rstd: torch.Tensor,
+                      grad_residual: Optional[torch.Tensor] = None, out=None, out_dtype: Optional[torch.dtype] = None,
+                      need_dweight: bool = True, sync: bool = False):
+    """The backward of rms_norm_per_token_cast_to_fp8's norm (dga_rms_norm_backward): grad_y and z [T, H] of one dtype, z what the forward
+    normalised (x, or its residual output), weight as in the forward, rstd float32 [T] the forward's own -> (dx, dweight).  With
+    x^ = z rstd, g = grad_y weight, c = sum_i g_i x^_i / H:  dx = rstd (g - x^ c), in z's dtype or float32 (out_dtype, or out's);
+    dweight[j] = sum_t grad_y[t, j] x^[t, j], float32 [H], overwritten (None with need_dweight=False).  All in float32; against float64 on the
+    same inputs, u = 2^-24, A = sum_i |g_i x^_i| / H:  |dx - exact| <= u rstd (4 |g| + |x^| (6 |c| + (H + 8) A)) for the float32 dx, of
+    which the 16-bit dx is the RNE;  |dweight - exact| <= (T + 4) u sum_t |grad_y x^|.  grad_residual (dx's dtype and shape, the gradient
+    arriving on the residual stream; it may be out's dx itself): dx = RNE(fl(dx + grad_residual)), bit for bit the separate sum.  Every sum
+    runs in an order (T, H, dtype) alone fixes, without floating-point atomics: two runs give the same bits, and a row's dx does not depend
+    on where the row sits.  out=(dx, dweight) takes the caller's tensors (dweight None with need_dweight=False).  Capturable."""
+    t_n, h = _norm_operands(z, weight, "z")
+    _want(grad_y, "grad_y", z.dtype, (t_n, h))
+    _want(rstd, "rstd", torch.float32, (t_n,))
+    dx = dweight = None
+    if out is not None:
+        _require(isinstance(out, (tuple, list)) and len(out) == 2 and isinstance(out[0], torch.Tensor)
+                 and (isinstance(out[1], torch.Tensor) if need_dweight else out[1] is None), "out must be (dx, dweight)")
+        dx, dweight = out
+        _require(out_dtype is None or out_dtype == dx.dtype, "out_dtype contradicts out")
+    dx_dtype = dx.dtype if dx is not None else z.dtype if out_dtype is None else out_dtype
+    _require(dx_dtype in (z.dtype, torch.float32), "dx must be of z's dtype or float32")
+    if dx is None:
+        dx = torch.empty((t_n, h), dtype=dx_dtype, device=z.device)
+    else:
+        _want(dx, "dx", dx_dtype, (t_n, h), "out ")
+    if need_dweight and dweight is None:
+        dweight = torch.empty((h,), dtype=torch.float32, device=z.device)
+    elif need_dweight:
+        _want(dweight, "dweight", torch.float32, (h,), "out ")
+    if grad_residual is not None:
+        _want(grad_residual, "grad_residual", dx_dtype, (t_n, h))
+
+    def call(L, stream):
+        ws_ptr, ws_bytes = _scratch("rms_norm", z.device, int(L.dga_rms_norm_backward_workspace_bytes(t_n, h)) if need_dweight else 0)
+        return L.dga_rms_norm_backward(grad_y.data_ptr(), z.data_ptr(), _CAST_DT[z.dtype], weight.data_ptr(), _CAST_DT[weight.dtype],
+                                       rstd.data_ptr(), _ptr(grad_residual), t_n, h, dx.data_ptr(), _CAST_DT[dx_dtype], _ptr(dweight), ws_ptr,
+                                       ws_bytes, stream)
+    _launch("rms_norm_backward", (z, grad_y, weight, rstd, grad_residual, dx, dweight), call, sync)
+    return dx, dweight
 
 
 def per_block_cast_to_fp8_transposed(w: torch.Tensor, rowwise: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):

@@ -1,5 +1,5 @@
 // What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_cast_transposed_block.hip, dga_gather_cast_transposed.hip, dga_silu_mul_cast.hip,
-// dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip; dga_combine.hip takes the element types' loads and stores).
+// dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip, dga_rms_norm.hip; dga_combine.hip takes the element types' loads and stores).
 // Device: the e4m3fn conversion, the 16-lane DPP row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition
 // (oracle/: quant_1x128); the bounded 8-element loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels'
 // row locator, refined sigmoid and silu(g) * u with its fp64-rounded block amax; the transposing kernels' row masks and the gathering one's

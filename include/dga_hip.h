@@ -737,6 +737,48 @@ int dga_router_balance_loss_backward(const float *dloss, const int32_t *counts, 
  * experts == 0 is DGA_OK with nothing touched;  then DGA_E_NULL (bias, counts) and DGA_E_RANGE for experts > DGA_ROUTER_MAX_EXPERTS. */
 int dga_router_bias_update(float *bias, const int32_t *counts, int64_t segments, int64_t experts, float rate, void *stream);
 
+/* The norm in front of an MoE block fused into the quantiser of everything that reads it: n = rms_norm(x + residual) * weight and
+ * per-token 1x128 codes of n in one pass over the row (csrc/dga_rms_norm.hip).  x and residual (or NULL) [rows, h] contiguous of x_dtype
+ * (DGA_DT_FP32 / BF16 / FP16; T below), weight [h] of w_dtype = x_dtype or DGA_DT_FP32, 1 <= h <= DGA_RMS_NORM_MAX_H, eps >= 0 finite.
+ * Per row, every operation in fp32 and rounded on its own (fl):
+ *   z[i]            = x[i]                                       without residual;
+ *   residual_out[i] = RNE_T(fl(x[i] + residual[i])),  z[i] = that stored value     with it (residual_out may be residual or x)
+ *   rstd            ~ (mean(z^2) + eps)^(-1/2),  |rstd - exact| <= (h / 2 + 6) 2^-24 exact against float64 on the same z; the sum of
+ *                   squares runs in an order that (h, x_dtype) alone fixes -- never the row count, the row's place or an atomic
+ *   y[i]            = fl(fl(z[i] * rstd) * weight[i]), a NaN replaced by the one NaN 0x7FC00000;  norm_out[i] = RNE_T(y[i])
+ *   (q, sf)         = what dga_cast_to_fp8_1x128_ex gives on the fp32 tensor y with the same flags, byte for byte and bit for bit;
+ *                   y is never rounded to 16 bits in front of the quantiser
+ * everything below rstd an exact function of the rstd [rows] fp32 the call returns (always written).  Nothing is rescaled: where the
+ * squares overflow rstd = 0 and y = +-0 (NaN at an infinite z), as in an fp32 torch expression; a NaN in a row makes that row's rstd NaN
+ * and its codes 0x7F, and touches no other row; subnormals are kept.  q and sf are both given or both NULL; one of (q, sf) and norm_out must
+ * be given (norm_out alone: a plain fused add + RMSNorm); residual_out is given iff residual is.  One launch, nothing read back
+ * (capturable).  Checks, in dga_cast_to_fp8_1x128_ex's order: DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a negative size,
+ * h > DGA_RMS_NORM_MAX_H (the row no longer fits in registers);  rows == 0 or h == 0 is DGA_OK with nothing launched;  then DGA_E_NULL
+ * (x, weight, rstd, and the pairings above), DGA_E_DTYPE, and DGA_E_RANGE for a negative, NaN or infinite eps and for more rows than one
+ * grid holds. */
+#define DGA_RMS_NORM_MAX_H 16384
+int dga_rms_norm_cast_to_fp8_1x128(const void *x, const void *residual, int x_dtype, const void *weight, int w_dtype, int64_t rows, int64_t h,
+                                   float eps, void *q, float *sf, void *norm_out, void *residual_out, float *rstd, int flags, void *stream);
+
+/* Its backward.  grad_y and z [rows, h] contiguous of dtype, z what the forward normalised (x, or residual_out), weight as above, rstd the
+ * forward's own output.  With x^ = fl(z rstd), g = fl(grad_y w), c = fl(sum_i g_i x^_i / h), all in fp32:
+ *   dx[t, i]   = fl(rstd * fl(g_i - fl(x^_i c)))                  dx_dtype = dtype or DGA_DT_FP32; the 16-bit dx is RNE of the fp32 one
+ *   dweight[j] = sum_t grad_y[t, j] x^[t, j]                      fp32 [h], overwritten; NULL: not computed
+ * grad_residual (NULL, or [rows, h] of dx_dtype; it may be dx itself): dx = RNE(fl(dx + grad_residual)), bit for bit the separate sum.
+ * Against float64 on the same inputs with rstd as given, u = 2^-24, A = sum_i |g_i x^_i| / h:
+ *   |dx - exact| <= u rstd (4 |g| + |x^| (6 |c| + (h + 8) A))   (fp32 dx),     |dweight[j] - exact| <= (rows + 4) u sum_t |grad_y x^|.
+ * Every sum runs in an order (rows, h, dtype) alone fixes, without floating-point atomics: two runs give the same bits, and a row's dx
+ * does not depend on where the row sits.  dweight takes two launches: groups of lanes add chunks of max(8, ceil(rows / 1024)) consecutive
+ * rows into the workspace, fp32 [chunks, h]; a second kernel adds a column's partials in ascending order (four runs, then the runs).
+ * dga_rms_norm_backward_workspace_bytes gives the size (0 for a shape the entry refuses or an empty one); the workspace is needed only
+ * with dweight.  DGA_E_SHAPE: a negative size, h > DGA_RMS_NORM_MAX_H;  rows == 0 or h == 0 is DGA_OK with nothing launched;  then
+ * DGA_E_NULL (grad_y, z, weight, rstd, dx; workspace with dweight), DGA_E_DTYPE, DGA_E_RANGE for more rows than one grid holds, and
+ * DGA_E_WORKSPACE for a workspace that is too small or not 16-byte aligned. */
+int dga_rms_norm_backward(const void *grad_y, const void *z, int dtype, const void *weight, int w_dtype, const float *rstd,
+                          const void *grad_residual, int64_t rows, int64_t h, void *dx, int dx_dtype, float *dweight, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+int64_t dga_rms_norm_backward_workspace_bytes(int64_t rows, int64_t h);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
