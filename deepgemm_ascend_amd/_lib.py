@@ -156,6 +156,8 @@ SIGNATURES = {
                                                   c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_cast_to_fp8_128x128_transposed": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                            c_void_p]),
+    "dga_adamw_cast_to_fp8_128x128_transposed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_float,
+                                                 c_float, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_gather_cast_to_fp8_1x128_transposed": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                                 c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_combine_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),

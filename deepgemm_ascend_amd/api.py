@@ -1571,6 +1571,80 @@ def per_block_cast_to_fp8_transposed(w: torch.Tensor, rowwise: bool = False, use
     return ((_as_fp8(qt), sft), (_as_fp8(q), sf)) if rowwise else (_as_fp8(qt), sft)
 
 
+def adamw_step_scalars(step: int, lr: float, beta1: float, beta2: float, grad_scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                       device=None) -> torch.Tensor:
+    """What adamw_per_block_cast_to_fp8_transposed reads of a step: float32 [4] = {lr, bc1, bc2s, grad_scale} with bc1 = 1 - beta1^step and
+    bc2s = sqrt(1 - beta2^step), formed on the host in float64 and rounded once to float32.  step >= 1.  grad_scale is where a caller puts
+    1 / loss_scale or a clip coefficient.  Without out= a new tensor on `device` (default: the current HIP device, the host without one); with
+    out= (contiguous float32 [4], any device) the values are copied into it on the current stream, which is how a captured graph is given
+    its next step."""
+    step = int(step)
+    _require(step >= 1, "step must be >= 1")
+    b1, b2 = float(beta1), float(beta2)
+    _require(0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0, "beta1 and beta2 must be in [0, 1)")
+    host = torch.tensor([float(lr), 1.0 - b1 ** step, (1.0 - b2 ** step) ** 0.5, float(grad_scale)], dtype=torch.float64).to(torch.float32)
+    if out is None:
+        return host.to(device if device is not None else "cuda" if torch.cuda.is_available() else "cpu")
+    _require(isinstance(out, torch.Tensor), "out must be a tensor")
+    _want(out, "step_scalars", torch.float32, (4,), "out ")
+    out.copy_(host)
+    return out
+
+
+def adamw_per_block_cast_to_fp8_transposed(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad: torch.Tensor, step_scalars: torch.Tensor,
+                                           beta1: float = 0.9, beta2: float = 0.95, eps: float = 1e-8, weight_decay: float = 0.0,
+                                           rowwise: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):
+    """The optimizer step of grouped expert weights and per_block_cast_to_fp8_transposed of the result in one pass
+    (dga_adamw_cast_to_fp8_128x128_transposed): w [G, N, K] or [N, K] contiguous float32 master weights, m and v like w and both float32 or
+    both bfloat16, grad like w in float32 or bfloat16 (read only), step_scalars a contiguous float32 [4] DEVICE tensor {lr, bc1, bc2s,
+    grad_scale} (adamw_step_scalars) that the kernel reads -- nothing of a step's changing state is a launch argument, so one captured graph
+    runs weight gradient -> optimizer -> the next forward at every step.  w, m and v are updated in place; no two of w, m, v and grad may
+    share memory.  Per element in float32, every
+    operation rounded on its own, beta1, beta2, eps and weight_decay rounded to float32 first:
+      g   = fl(grad grad_scale)
+      m'  = fl(fl(beta1 m) + fl(fl(1 - beta1) g))
+      v'  = fl(fl(beta2 v) + fl(fl(fl(1 - beta2) g) g))
+      den = fl(fl(sqrt(v') / bc2s) + eps)
+      w'  = fl(fl(w fl(1 - fl(lr weight_decay))) - fl(fl(lr / bc1) fl(m' / den)))
+    with IEEE square root and division and subnormals kept: numpy in float32 reproduces w', m' and v' bit for bit.  m' and v' are stored
+    round-to-nearest-even in their dtype, the update uses the unrounded ones.  Returns (qt, sft), or with rowwise ((qt, sft), (q, sf)):
+    exactly per_block_cast_to_fp8_transposed(w, rowwise=..., use_ue8m0=...) on the w the call leaves behind, byte for byte; out= as there.
+    A NaN or infinite gradient poisons its own element of w, m and v only; eps = 0 with v' = 0 gives NaN, as torch does."""
+    _require(isinstance(w, torch.Tensor) and w.dim() in (2, 3) and w.is_contiguous() and w.dtype == torch.float32,
+             "w must be a contiguous float32 [N, K] or [G, N, K] tensor")
+    shape = tuple(w.shape)
+    moments = (torch.float32, torch.bfloat16)
+    for t, what in ((m, "m"), (v, "v"), (grad, "grad"), (step_scalars, "step_scalars")):
+        _require(isinstance(t, torch.Tensor), "%s must be a tensor", what)
+    _want(m, "m", moments, shape)
+    _want(v, "v", moments, shape)
+    _require(m.dtype == v.dtype, "m and v must be of one dtype")
+    _want(grad, "grad", moments, shape)
+    _want(step_scalars, "step_scalars", torch.float32, (4,))
+    # (updated in place, a lane's elements read before they are written: two of them on the same memory would make the result depend on
+    # the order of the workgroups)
+    spans = [(what, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t, what in ((w, "w"), (m, "m"), (v, "v"), (grad, "grad"))]
+    for i, (a, a0, a1) in enumerate(spans):
+        for b, b0, b1 in spans[i + 1:]:
+            _require(a0 >= b1 or b0 >= a1, "%s and %s must not share memory", a, b)
+    b1, b2, e, wd = (ctypes.c_float(float(x)).value for x in (beta1, beta2, eps, weight_decay))
+    _require(0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0, "beta1 and beta2 must be in [0, 1) as float32")
+    _require(0.0 <= e < float("inf") and 0.0 <= wd < float("inf"), "eps and weight_decay must be finite and >= 0")
+    lead = shape[:-2]
+    groups = lead[0] if lead else 1
+    n, k = shape[-2:]
+    nb, kb = (n + 127) // 128, (k + 127) // 128
+    out_t, out_r = _nested_out(out, rowwise)
+    qt, sft = _outputs(out_t, (("qt", torch.uint8, lead + (k, n)), ("sft", torch.float32, lead + (kb, nb))), w.device, "out must hold (qt, sft)")
+    q, sf = _outputs(out_r, (("q", torch.uint8, lead + (n, k)), ("sf", torch.float32, lead + (nb, kb))), w.device,
+                     "out must hold (q, sf)") if rowwise else (None, None)
+    _launch("adamw_per_block_cast_to_fp8_transposed", (w, m, v, grad, step_scalars, qt, sft, q, sf),
+            lambda L, stream: L.dga_adamw_cast_to_fp8_128x128_transposed(
+                w.data_ptr(), m.data_ptr(), v.data_ptr(), _CAST_DT[m.dtype], grad.data_ptr(), _CAST_DT[grad.dtype], step_scalars.data_ptr(),
+                b1, b2, e, wd, groups, n, k, qt.data_ptr(), sft.data_ptr(), _ptr(q), _ptr(sf), _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+    return ((_as_fp8(qt), sft), (_as_fp8(q), sf)) if rowwise else (_as_fp8(qt), sft)
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

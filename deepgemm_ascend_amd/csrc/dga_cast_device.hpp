@@ -1,7 +1,7 @@
-// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_cast_transposed_block.hip, dga_gather_cast_transposed.hip, dga_silu_mul_cast.hip,
+// What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_cast_transposed_block.hip, dga_adamw_cast.hip, dga_gather_cast_transposed.hip, dga_silu_mul_cast.hip,
 // dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip, dga_rms_norm.hip; dga_combine.hip takes the element types' loads and stores).
 // Device: the e4m3fn conversion, the 16-lane DPP row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition
-// (oracle/: quant_1x128); the bounded 8-element loads and stores of the three types (Elem, load8_bounded, Store8, store_codes8); the fused kernels'
+// (oracle/: quant_1x128); the bounded 8-element loads and stores of the three types (Elem, load8_bounded, Store8, store1, store8_bounded, store_codes8); the fused kernels'
 // row locator, refined sigmoid and silu(g) * u with its fp64-rounded block amax; the transposing kernels' row masks and the gathering one's
 // table reads.  Host, at the end:
 // the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
@@ -235,6 +235,30 @@ template <> struct Store8<F16Tag> {
     }
 };
 
+// one fp32 value -> one element of T at element index i, round to nearest even (Store8's conversions, one element at a time)
+template <typename T> __device__ __forceinline__ void store1(void *p, int64_t i, float v);
+template <> __device__ __forceinline__ void store1<float>(void *p, int64_t i, float v) { ((float *)p)[i] = v; }
+template <> __device__ __forceinline__ void store1<Bf16Tag>(void *p, int64_t i, float v)
+{
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    typedef __bf16 v2b __attribute__((ext_vector_type(2)));
+    ((uint16_t *)p)[i] = (uint16_t)__builtin_bit_cast(uint32_t, __builtin_convertvector((v2f{v, 0.f}), v2b));
+}
+template <> __device__ __forceinline__ void store1<F16Tag>(void *p, int64_t i, float v) { ((_Float16 *)p)[i] = (_Float16)v; }
+
+// Store8's bounded form, the counterpart of load8_bounded (dga_rms_norm.hip, dga_adamw_cast.hip): columns c0 .. c0 + 7 of a row of n,
+// nothing at or beyond n
+template <typename T> __device__ __forceinline__ void store8_bounded(void *p, int64_t i, const float (&v)[8], bool vec, int64_t c0, int64_t n)
+{
+    if (vec && c0 + 8 <= n) {
+        Store8<T>::run(p, i, v, true);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (c0 + j < n) store1<T>(p, i + j, v[j]);
+    }
+}
+
 // The lane's 8 codes (w0: the first four, w1: the rest) to q, the place of columns c0 .. c0 + 7 of a row of n columns.  One 8-byte store when
 // the caller vouches for the alignment (vec) and all 8 are inside the row, else byte by byte below n.  (c0, n) = (0, 8): all 8 are inside.
 __device__ __forceinline__ void store_codes8(uint8_t *q, uint32_t w0, uint32_t w1, bool vec, int64_t c0, int64_t n)
@@ -327,6 +351,98 @@ __device__ __forceinline__ void rows_valid8(int64_t r0, int64_t t_n, int64_t mma
     } else {
 #pragma unroll
         for (int p = 0; p < 8; ++p) ok[p] = r0 + p <= last;
+    }
+}
+
+// ---- the 128x128 transposing quantisers (dga_cast_transposed_block.hip, dga_adamw_cast.hip): 256 lanes on one 128x128 tile of one group
+
+// Where a lane stands: workgroup blk of groups x nb_n x kb_n tiles, walked along k, then n, then the groups; 16 lanes share a row, the lane
+// holds columns c0 .. c0 + 7 of rows r0 .. r0 + 7, and g0 is the group's first element in [n, k] and in [k, n].
+struct BlockTileAt {
+    uint32_t g, nb, kb;
+    int64_t c0, r0, g0;
+};
+__device__ __forceinline__ BlockTileAt block_tile_at(uint32_t blk, int t, int64_t n, int64_t k, uint32_t nb_n, uint32_t kb_n)
+{
+    const int sub = t & 15, rg = t >> 4;
+    const uint32_t per_group = nb_n * kb_n;   // (the grid, groups * per_group, fits 31 bits)
+    const uint32_t g = blk / per_group, in_g = blk - g * per_group;
+    const uint32_t nb = in_g / kb_n, kb = in_g - nb * kb_n;
+    const int64_t c0 = (int64_t)kb * 128 + sub * 8;   // the lane's 8 columns
+    const int64_t r0 = (int64_t)nb * 128 + rg * 8;    // ... and its 8 rows
+    const int64_t g0 = (int64_t)g * n * k;            // the group's first element, in w and q_row (row-major [n, k]) and in qt ([k, n])
+    return BlockTileAt{g, nb, kb, c0, r0, g0};
+}
+
+// From the lane's 64 values v[pass][column] (zeros at rows where !ok[p] and at columns at and beyond k) to everything the tile writes:
+//   tile maximum       in the lane over its 64 values (abs_for_max: no NaN of any kind reaches a maximum), over the wave by six cross-lane
+//                      moves, over the 4 waves through red: one scale, written to sft[g, kb, nb] and to sf_row[g, nb, kb]
+//   row-wise codes     quant8 on each pass's 8 columns -- cast_128x128_kernel's groups of 8 -- stored directly: a 16-lane group writes 128
+//                      contiguous bytes of a row of q_row
+//   transposed codes   quant8 on the lane's 8 rows of each of its 8 columns -- cast_128x128_kernel's groups of 8 on w^T --, then
+//                      cast_1x128_transposed_kernel's 16 KB tile [128 columns][16 slots of 8 rows], slot r of column c at slot r ^ (c / 8)
+//                      (its comment has the bank arithmetic): one 8-byte LDS store per column, one 8-byte load per lane and output row, and a
+//                      16-lane group stores 128 contiguous bytes of a row of qt
+// Codes of rows at and beyond n and of columns at and beyond k are never stored.  One text for both kernels: the same values give the same
+// bytes.
+template <bool ROWWISE>
+__device__ __forceinline__ void quant_block_tile_transposed(const float (&v)[8][8], const bool (&ok)[8], const BlockTileAt &a, int t,
+                                                            uint8_t *qt, float *sft, uint8_t *q_row, float *sf_row, int64_t n, int64_t k,
+                                                            uint32_t nb_n, uint32_t kb_n, bool vec_qt, bool vec_row, bool ue8m0)
+{
+    __shared__ float red[4];
+    __shared__ uint64_t tile[128 * 16];
+    const int sub = t & 15, rg = t >> 4;
+    const uint32_t g = a.g, nb = a.nb, kb = a.kb;
+    const int64_t c0 = a.c0, r0 = a.r0, g0 = a.g0;
+    float amax = 0.f;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = __builtin_fmaxf(amax, abs_for_max(v[p][j]));
+    }
+#pragma unroll
+    for (int msk = 1; msk < 64; msk <<= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, msk, 64));
+    if ((t & 63) == 0) red[t >> 6] = amax;
+    __syncthreads();
+    const float s = block_scale(__builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3])), ue8m0);
+    if (t == 0) {
+        sft[((int64_t)g * kb_n + kb) * nb_n + nb] = s;
+        if (ROWWISE) sf_row[((int64_t)g * nb_n + nb) * kb_n + kb] = s;
+    }
+    if (ROWWISE) {
+        // The same scale as a value the compiler cannot see through.  With one visible scale it computes the 64 quotients once for both
+        // passes and keeps them beside the 64 inputs (the general path needs those): 212 VGPRs, 2 waves per SIMD, in
+        // cast_128x128_transposed_kernel.  Two passes of quant8 as in cast_1x128_transposed_kernel, whose two passes have different
+        // scales anyway: 108 (fp32) / 112 VGPRs and 4 waves per SIMD there, 136 .. 142 and 3 waves in the optimizer's kernel.
+        float s_row = s;
+        asm volatile("" : "+v"(s_row));
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            if (!ok[p]) continue;   // (uniform over the 16 lanes of the row)
+            uint32_t w0, w1;
+            quant8(v[p], s_row, w0, w1);
+            store_codes8(q_row + g0 + (r0 + p) * k + c0, w0, w1, vec_row, c0, k);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float e[8];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) e[p] = v[p][j];
+        uint32_t w0, w1;
+        quant8(e, s, w0, w1);
+        tile[(sub * 8 + j) * 16 + (rg ^ sub)] = (uint64_t)w0 | ((uint64_t)w1 << 32);
+    }
+    __syncthreads();
+    const int64_t tc = (int64_t)nb * 128 + sub * 8;   // the first of the 8 rows of w this lane stores, of column rg + 16 i
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int ch = rg + 16 * i;
+        const int64_t c = (int64_t)kb * 128 + ch;
+        if (c >= k) break;
+        const uint64_t wv = tile[ch * 16 + (sub ^ (ch >> 3))];
+        store_codes8(qt + g0 + c * n + tc, (uint32_t)wv, (uint32_t)(wv >> 32), vec_qt, tc, n);
     }
 }
 

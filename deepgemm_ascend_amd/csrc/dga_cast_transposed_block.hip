@@ -19,23 +19,17 @@ namespace dga {
 // One workgroup per tile of 128 rows x 128 columns of one group; workgroups that follow each other walk along k (whole rows of w are read
 // side by side), then along n, then over the groups.  cast_1x128_transposed_kernel's register shape: 16 lanes share a row, 8 consecutive
 // columns per lane (256 contiguous bytes of bf16 per row), and row group rg = t / 16 holds the 8 CONSECUTIVE rows 8 rg .. 8 rg + 7, one per
-// pass: 64 fp32 values per lane, and the 8 codes of one column in a lane are 8 neighbouring bytes of qt.
-//   tile maximum       in the lane over its 64 values (abs_for_max: no NaN of any kind reaches a maximum), over the wave by six cross-lane
-//                      moves, over the 4 waves through red: one scale, written to sft[g, kb, nb] and to sf_row[g, nb, kb]
-//   row-wise codes     quant8 on each pass's 8 columns -- cast_128x128_kernel's groups of 8 -- stored directly: a 16-lane group writes 128
-//                      contiguous bytes of a row of q_row
-//   transposed codes   quant8 on the lane's 8 rows of each of its 8 columns -- cast_128x128_kernel's groups of 8 on w^T --, then
-//                      cast_1x128_transposed_kernel's 16 KB tile [128 columns][16 slots of 8 rows], slot r of column c at slot r ^ (c / 8)
-//                      (its comment has the bank arithmetic): one 8-byte LDS store per column, one 8-byte load per lane and output row, and a
-//                      16-lane group stores 128 contiguous bytes of a row of qt
+// pass: 64 fp32 values per lane, and the 8 codes of one column in a lane are 8 neighbouring bytes of qt.  From those 64 values on -- the
+// tile maximum, the scale, the row-wise and the transposed codes -- the text is quant_block_tile_transposed's (dga_cast_device.hpp), which
+// dga_adamw_cast.hip calls too.
 // Rows at and beyond n and columns at and beyond k are zeros that are never loaded, and their codes are never stored.
 template <typename T, bool ROWWISE>
 __global__ void __launch_bounds__(256) cast_128x128_transposed_kernel(const void *w, uint8_t *qt, float *sft, uint8_t *q_row, float *sf_row,
                                                                       int64_t n, int64_t k, uint32_t nb_n, uint32_t kb_n, bool vec_in,
                                                                       bool vec_qt, bool vec_row, bool ue8m0)
 {
-    __shared__ float red[4];
-    __shared__ uint64_t tile[128 * 16];
+    // block_tile_at's text, written out: through the helper the same arithmetic allocates 86 VGPRs instead of 77 in the builds without the
+    // row-wise output (5 waves per SIMD instead of 6) and 110 instead of 108 in the fp32 row-wise one
     const int t = threadIdx.x, sub = t & 15, rg = t >> 4;
     const uint32_t per_group = nb_n * kb_n;   // (the grid, groups * per_group, fits 31 bits)
     const uint32_t g = blockIdx.x / per_group, in_g = blockIdx.x - g * per_group;
@@ -43,6 +37,7 @@ __global__ void __launch_bounds__(256) cast_128x128_transposed_kernel(const void
     const int64_t c0 = (int64_t)kb * 128 + sub * 8;   // the lane's 8 columns
     const int64_t r0 = (int64_t)nb * 128 + rg * 8;    // ... and its 8 rows
     const int64_t g0 = (int64_t)g * n * k;            // the group's first element, in w and q_row (row-major [n, k]) and in qt ([k, n])
+    const BlockTileAt at{g, nb, kb, c0, r0, g0};
     bool ok[8];
 #pragma unroll
     for (int p = 0; p < 8; ++p) ok[p] = r0 + p < n;
@@ -60,54 +55,7 @@ __global__ void __launch_bounds__(256) cast_128x128_transposed_kernel(const void
 #pragma unroll
         for (int p = 0; p < 8; ++p) load8_bounded<T>(w, g0 + (r0 + p) * k + c0, v[p], vec_in, c0, k, ok[p]);
     }
-    float amax = 0.f;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) amax = __builtin_fmaxf(amax, abs_for_max(v[p][j]));
-    }
-#pragma unroll
-    for (int msk = 1; msk < 64; msk <<= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, msk, 64));
-    if ((t & 63) == 0) red[t >> 6] = amax;
-    __syncthreads();
-    const float s = block_scale(__builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3])), ue8m0);
-    if (t == 0) {
-        sft[((int64_t)g * kb_n + kb) * nb_n + nb] = s;
-        if (ROWWISE) sf_row[((int64_t)g * nb_n + nb) * kb_n + kb] = s;
-    }
-    if (ROWWISE) {
-        // The same scale as a value the compiler cannot see through.  With one visible scale it computes the 64 quotients once for both
-        // passes and keeps them beside the 64 inputs (the general path needs those): 212 VGPRs, 2 waves per SIMD.  Two passes of quant8
-        // as in cast_1x128_transposed_kernel, whose two passes have different scales anyway: 108 (fp32) / 114 VGPRs, 4 waves per SIMD.
-        float s_row = s;
-        asm volatile("" : "+v"(s_row));
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            if (!ok[p]) continue;   // (uniform over the 16 lanes of the row)
-            uint32_t w0, w1;
-            quant8(v[p], s_row, w0, w1);
-            store_codes8(q_row + g0 + (r0 + p) * k + c0, w0, w1, vec_row, c0, k);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float e[8];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) e[p] = v[p][j];
-        uint32_t w0, w1;
-        quant8(e, s, w0, w1);
-        tile[(sub * 8 + j) * 16 + (rg ^ sub)] = (uint64_t)w0 | ((uint64_t)w1 << 32);
-    }
-    __syncthreads();
-    const int64_t tc = (int64_t)nb * 128 + sub * 8;   // the first of the 8 rows of w this lane stores, of column rg + 16 i
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int ch = rg + 16 * i;
-        const int64_t c = (int64_t)kb * 128 + ch;
-        if (c >= k) break;
-        const uint64_t wv = tile[ch * 16 + (sub ^ (ch >> 3))];
-        store_codes8(qt + g0 + c * n + tc, (uint32_t)wv, (uint32_t)(wv >> 32), vec_qt, tc, n);
-    }
+    quant_block_tile_transposed<ROWWISE>(v, ok, at, t, qt, sft, q_row, sf_row, n, k, nb_n, kb_n, vec_qt, vec_row, ue8m0);
 }
 
 }  // namespace dga

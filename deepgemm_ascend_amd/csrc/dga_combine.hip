@@ -21,16 +21,6 @@
 
 namespace dga {
 
-// one fp32 value -> one element of T at element index i, round to nearest even (Store8's conversions, one element at a time)
-template <typename T> __device__ __forceinline__ void store1(void *p, int64_t i, float v);
-template <> __device__ __forceinline__ void store1<float>(void *p, int64_t i, float v) { ((float *)p)[i] = v; }
-template <> __device__ __forceinline__ void store1<Bf16Tag>(void *p, int64_t i, float v)
-{
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    typedef __bf16 v2b __attribute__((ext_vector_type(2)));
-    ((uint16_t *)p)[i] = (uint16_t)__builtin_bit_cast(uint32_t, __builtin_convertvector((v2f{v, 0.f}), v2b));
-}
-template <> __device__ __forceinline__ void store1<F16Tag>(void *p, int64_t i, float v) { ((_Float16 *)p)[i] = (_Float16)v; }
 
 constexpr int COMBINE_J = 4;   // choices whose rows are in flight together
 

@@ -90,23 +90,6 @@ __device__ __forceinline__ typename Elem<T>::Raw load8_raw_bounded(const void *p
     return Pack8<T>::run(v);
 }
 
-template <typename T> __device__ __forceinline__ void store1(void *p, int64_t i, float v);
-template <> __device__ __forceinline__ void store1<float>(void *p, int64_t i, float v) { ((float *)p)[i] = v; }
-template <> __device__ __forceinline__ void store1<Bf16Tag>(void *p, int64_t i, float v) { ((__bf16 *)p)[i] = (__bf16)v; }
-template <> __device__ __forceinline__ void store1<F16Tag>(void *p, int64_t i, float v) { ((_Float16 *)p)[i] = (_Float16)v; }
-
-// Store8's bounded form, the counterpart of load8_bounded: columns c0 .. c0 + 7 of a row of n, nothing at or beyond n
-template <typename T> __device__ __forceinline__ void store8_bounded(void *p, int64_t i, const float (&v)[8], bool vec, int64_t c0, int64_t n)
-{
-    if (vec && c0 + 8 <= n) {
-        Store8<T>::run(p, i, v, true);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (c0 + j < n) store1<T>(p, i + j, v[j]);
-    }
-}
-
 // a tensor that is of type T or fp32, decided at run time by a uniform flag (weight, dx, grad_residual): one kernel build serves both
 template <typename T> __device__ __forceinline__ void load8_either(const void *p, bool f32, int64_t i, float (&v)[8], bool vec, int64_t c0, int64_t n, bool ok = true)
 {

@@ -557,6 +557,35 @@ int dga_silu_mul_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_
 int dga_cast_to_fp8_128x128_transposed(const void *w, int w_dtype, int64_t groups, int64_t n, int64_t k,
                                        void *qt, float *sft, void *q_row, float *sf_row, int flags, void *stream);
 
+/* The optimizer step of those weights fused into that quantiser (csrc/dga_adamw_cast.hip): AdamW on the fp32 master weights w [groups,
+ * n, k] with their moments m and v (same shape, both of moment_dtype = DGA_DT_FP32 or DGA_DT_BF16) and the weight gradient grad (same
+ * shape, grad_dtype = DGA_DT_FP32 or DGA_DT_BF16, read only), all contiguous; w, m and v are updated in place, and no two of w, m, v and
+ * grad may overlap in memory (not checked here: the entry sees pointers; the Python wrapper refuses it).  step_scalars: four fp32
+ * values on the device, {lr, bc1, bc2s, grad_scale}, read by the kernel -- bc1 = 1 - beta1^step, bc2s = sqrt(1 - beta2^step); nothing of
+ * a step's changing state is a launch argument, so one captured graph serves every step.  Per element, every operation in fp32 and
+ * rounded on its own (fl), sqrt and / the IEEE correctly rounded ones, subnormals kept:
+ *   g   = fl(grad * grad_scale)
+ *   m'  = fl(fl(beta1 * m) + fl(fl(1 - beta1) * g))
+ *   v'  = fl(fl(beta2 * v) + fl(fl(fl(1 - beta2) * g) * g))
+ *   den = fl(fl(sqrt(v') / bc2s) + eps)
+ *   w1  = fl(w * fl(1 - fl(lr * weight_decay)))
+ *   w'  = fl(w1 - fl(fl(lr / bc1) * fl(m' / den)))
+ * w' is stored as fp32, m' and v' RNE in moment_dtype; the update uses the unrounded m' and v'.  A float32 reference reproduces all
+ * three bit for bit (a NaN is a NaN: its sign and payload are the hardware's).  The codes are an exact function of the w left behind:
+ *   (qt, sft) and, if given, (q_row, sf_row) = what dga_cast_to_fp8_128x128_transposed writes for that w with the same flags, byte
+ *   for byte and bit for bit;  shapes, the pairing of q_row / sf_row and flags as there, every element of every output written.
+ * A NaN or infinite gradient poisons its own element of w, m and v and no other (the tile's amax ignores NaN; the element's code is
+ * sign | 0x7F); eps = 0 with v' = 0 gives 0 / 0 = NaN; grad_scale = 0 and lr = 0 are ordinary inputs.  Rows at and beyond n and
+ * columns at and beyond k are neither read nor written; k % 8 != 0 or a pointer short of 16 (codes: 8) bytes takes the bounded
+ * element-wise path for that tensor.  One launch, nothing allocated, nothing read back (capturable).  Checks in this order:
+ * DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a negative size, exactly one of q_row / sf_row;  groups, n or k zero is DGA_OK with
+ * nothing launched;  then DGA_E_NULL (w, m, v, grad, step_scalars, qt, sft), DGA_E_DTYPE (fp16 moments or gradient included), and
+ * DGA_E_RANGE for a beta outside [0, 1), an eps or weight_decay that is negative, NaN or infinite, and more tiles than one grid holds. */
+int dga_adamw_cast_to_fp8_128x128_transposed(void *w, void *m, void *v, int moment_dtype, const void *grad, int grad_dtype,
+                                             const float *step_scalars, float beta1, float beta2, float eps, float weight_decay,
+                                             int64_t groups, int64_t n, int64_t k, void *qt, float *sft, void *q_row, float *sf_row,
+                                             int flags, void *stream);
+
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
 /* struct Config in declaration order (get_best_config.hpp:12-31), 28 uint32. */
