@@ -7,7 +7,7 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint16, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint16, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
 _PKG = Path(__file__).resolve().parent
@@ -158,6 +158,12 @@ SIGNATURES = {
                                            c_void_p]),
     "dga_adamw_cast_to_fp8_128x128_transposed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_float,
                                                  c_float, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dga_adamw_cast_to_fp8_128x128_transposed_skip": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_float,
+                                                      c_float, c_float, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_int, c_void_p, c_void_p]),
+    "dga_grad_sumsq_workspace_bytes": (c_int64, [c_int, c_void_p]),
+    "dga_grad_sumsq": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "dga_grad_clip_scalars": (c_int, [c_void_p, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dga_gather_cast_to_fp8_1x128_transposed": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                                 c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_combine_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),

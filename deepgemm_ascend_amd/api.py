@@ -1593,7 +1593,8 @@ def adamw_step_scalars(step: int, lr: float, beta1: float, beta2: float, grad_sc
 
 def adamw_per_block_cast_to_fp8_transposed(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad: torch.Tensor, step_scalars: torch.Tensor,
                                            beta1: float = 0.9, beta2: float = 0.95, eps: float = 1e-8, weight_decay: float = 0.0,
-                                           rowwise: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):
+                                           rowwise: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False,
+                                           skip: Optional[torch.Tensor] = None):
     """The optimizer step of grouped expert weights and per_block_cast_to_fp8_transposed of the result in one pass
     (dga_adamw_cast_to_fp8_128x128_transposed): w [G, N, K] or [N, K] contiguous float32 master weights, m and v like w and both float32 or
     both bfloat16, grad like w in float32 or bfloat16 (read only), step_scalars a contiguous float32 [4] DEVICE tensor {lr, bc1, bc2s,
@@ -1609,7 +1610,11 @@ def adamw_per_block_cast_to_fp8_transposed(w: torch.Tensor, m: torch.Tensor, v: 
     with IEEE square root and division and subnormals kept: numpy in float32 reproduces w', m' and v' bit for bit.  m' and v' are stored
     round-to-nearest-even in their dtype, the update uses the unrounded ones.  Returns (qt, sft), or with rowwise ((qt, sft), (q, sf)):
     exactly per_block_cast_to_fp8_transposed(w, rowwise=..., use_ue8m0=...) on the w the call leaves behind, byte for byte; out= as there.
-    A NaN or infinite gradient poisons its own element of w, m and v only; eps = 0 with v' = 0 gives NaN, as torch does."""
+    A NaN or infinite gradient poisons its own element of w, m and v only; eps = 0 with v' = 0 gives NaN, as torch does.
+    skip (a contiguous int32 [1] device tensor, typically grad_clip_scalars', read by the kernel): where skip[0] != 0 nothing is stored to w,
+    m and v -- their bits stay, whatever grad holds -- and the codes are per_block_cast_to_fp8_transposed of the unchanged w, every element
+    of every output written; where it is 0, and without skip, every bit of every result is the same as ever.  The step number stays the
+    caller's: it reads skip back when convenient and does not advance step after a skipped one."""
     _require(isinstance(w, torch.Tensor) and w.dim() in (2, 3) and w.is_contiguous() and w.dtype == torch.float32,
              "w must be a contiguous float32 [N, K] or [G, N, K] tensor")
     shape = tuple(w.shape)
@@ -1630,6 +1635,9 @@ def adamw_per_block_cast_to_fp8_transposed(w: torch.Tensor, m: torch.Tensor, v: 
     b1, b2, e, wd = (ctypes.c_float(float(x)).value for x in (beta1, beta2, eps, weight_decay))
     _require(0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0, "beta1 and beta2 must be in [0, 1) as float32")
     _require(0.0 <= e < float("inf") and 0.0 <= wd < float("inf"), "eps and weight_decay must be finite and >= 0")
+    if skip is not None:
+        _require(isinstance(skip, torch.Tensor), "skip must be a tensor")
+        _want(skip, "skip", torch.int32, (1,))
     lead = shape[:-2]
     groups = lead[0] if lead else 1
     n, k = shape[-2:]
@@ -1638,11 +1646,121 @@ def adamw_per_block_cast_to_fp8_transposed(w: torch.Tensor, m: torch.Tensor, v: 
     qt, sft = _outputs(out_t, (("qt", torch.uint8, lead + (k, n)), ("sft", torch.float32, lead + (kb, nb))), w.device, "out must hold (qt, sft)")
     q, sf = _outputs(out_r, (("q", torch.uint8, lead + (n, k)), ("sf", torch.float32, lead + (nb, kb))), w.device,
                      "out must hold (q, sf)") if rowwise else (None, None)
-    _launch("adamw_per_block_cast_to_fp8_transposed", (w, m, v, grad, step_scalars, qt, sft, q, sf),
-            lambda L, stream: L.dga_adamw_cast_to_fp8_128x128_transposed(
+    _launch("adamw_per_block_cast_to_fp8_transposed", (w, m, v, grad, step_scalars, qt, sft, q, sf, skip),
+            lambda L, stream: L.dga_adamw_cast_to_fp8_128x128_transposed_skip(
                 w.data_ptr(), m.data_ptr(), v.data_ptr(), _CAST_DT[m.dtype], grad.data_ptr(), _CAST_DT[grad.dtype], step_scalars.data_ptr(),
-                b1, b2, e, wd, groups, n, k, qt.data_ptr(), sft.data_ptr(), _ptr(q), _ptr(sf), _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+                b1, b2, e, wd, groups, n, k, qt.data_ptr(), sft.data_ptr(), _ptr(q), _ptr(sf), _lib.CAST_UE8M0 if use_ue8m0 else 0,
+                _ptr(skip), stream), sync)
     return ((_as_fp8(qt), sft), (_as_fp8(q), sf)) if rowwise else (_as_fp8(qt), sft)
+
+
+GradClip = collections.namedtuple("GradClip", ("norm", "coef", "skip"))
+GradClipNorm = collections.namedtuple("GradClipNorm", ("norm", "coef", "skip", "sumsq"))
+_GRAD_DT = {torch.float32: _lib.DT_FP32, torch.bfloat16: _lib.DT_BF16}
+
+
+def grad_sumsq_workspace_bytes(numels: Sequence[int]) -> int:
+    """Bytes of device scratch grad_sumsq needs for tensors of these element counts (dga_grad_sumsq_workspace_bytes): one float64 partial
+    per chunk of 16384 consecutive elements of one tensor; 0 for a list the entry refuses."""
+    numels = [int(x) for x in numels]
+    return int(_lib.lib().dga_grad_sumsq_workspace_bytes(len(numels), (ctypes.c_int64 * max(len(numels), 1))(*numels)))
+
+
+def _sumsq_args(tensors, out, accumulate: bool):
+    """grad_sumsq's checks -> (the list, out or None)."""
+    if isinstance(tensors, torch.Tensor):
+        tensors = (tensors,)
+    _require(isinstance(tensors, (list, tuple)) and len(tensors) > 0, "tensors must be a tensor or a non-empty list or tuple of tensors")
+    for i, t in enumerate(tensors):
+        _require(isinstance(t, torch.Tensor) and t.dtype in _GRAD_DT and t.is_contiguous(),
+                 "tensors[%d] must be a contiguous float32 or bfloat16 tensor", i)
+    if out is not None:
+        _require(isinstance(out, torch.Tensor), "out must be a tensor")
+        _want(out, "sumsq", torch.float64, (1,), "out ")
+    _require(out is not None or not accumulate, "accumulate=True needs out=")
+    return tensors, out
+
+
+def _sumsq_run(tensors, out, accumulate: bool, sync: bool) -> torch.Tensor:
+    count = len(tensors)
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float64, device=tensors[0].device)
+    ptrs = (ctypes.c_void_p * count)(*[t.data_ptr() for t in tensors])
+    numel = (ctypes.c_int64 * count)(*[t.numel() for t in tensors])
+    dts = (ctypes.c_int * count)(*[_GRAD_DT[t.dtype] for t in tensors])
+
+    def call(L, stream):
+        ws_ptr, ws_bytes = _scratch("grad_sumsq", out.device, int(L.dga_grad_sumsq_workspace_bytes(count, numel)))
+        return L.dga_grad_sumsq(ptrs, numel, dts, count, out.data_ptr(), 1 if accumulate else 0, ws_ptr, ws_bytes, stream)
+    _launch("grad_sumsq", (out,) + tuple(tensors), call, sync)
+    return out
+
+
+def grad_sumsq(tensors, out: Optional[torch.Tensor] = None, accumulate: bool = False, sync: bool = False) -> torch.Tensor:
+    """The sum of squares of a list of gradient tensors as a float64 [1] device tensor (dga_grad_sumsq): tensors is a tensor or a non-empty
+    list or tuple of contiguous float32 or bfloat16 device tensors of any shape (numel == 0 included; the dtypes may be mixed; float16 is
+    refused, as by the optimizer), all on one device.  sumsq[0] = sum_i sum_e x_i[e]^2 with every product and every sum in float64: the
+    squares are exact and can neither overflow nor underflow, subnormals are kept, and  |sumsq - exact| <= (n + 1) 2^-53 exact  for n
+    elements.  A NaN or an infinity anywhere makes sumsq non-finite and nothing else can, so isfinite(sumsq) is the overflow check of a
+    loss-scaled step.  The order of the additions is fixed by the list of (numel, dtype) alone, without floating-point atomics: two runs
+    give the same bits, wherever the tensors lie.  out= takes the caller's float64 [1]; accumulate=True (with out=) adds out[0] last,
+    fl64(out[0] + sum), so that several calls build one sum.  Nothing is read back, the scratch is the module's: capturable."""
+    tensors, out = _sumsq_args(tensors, out, accumulate)
+    return _sumsq_run(tensors, out, accumulate, sync)
+
+
+def _clip_args(step_scalars, max_norm, pre_scale, eps):
+    """grad_clip_scalars' checks behind sumsq's -> max_norm, pre_scale and eps as floats."""
+    _require(isinstance(step_scalars, torch.Tensor), "step_scalars must be a tensor")
+    _want(step_scalars, "step_scalars", torch.float32, (4,))
+    mx, ps, e = float(max_norm), float(pre_scale), float(eps)
+    _require(mx >= 0.0, "max_norm must be >= 0 (it may be inf)")
+    _require(0.0 < ps < float("inf"), "pre_scale must be finite and > 0")
+    _require(0.0 <= e < float("inf"), "eps must be finite and >= 0")
+    return mx, ps, e
+
+
+_CLIP_SPECS = (("norm", torch.float32, (1,)), ("coef", torch.float32, (1,)), ("skip", torch.int32, (1,)))
+
+
+def _clip_run(sumsq, step_scalars, mx, ps, e, outs, sync):
+    norm, coef, skip = outs
+    _launch("grad_clip_scalars", (sumsq, step_scalars, norm, coef, skip), lambda L, stream: L.dga_grad_clip_scalars(
+        sumsq.data_ptr(), mx, ps, e, step_scalars.data_ptr(), norm.data_ptr(), coef.data_ptr(), skip.data_ptr(), stream), sync)
+    return norm, coef, skip
+
+
+def grad_clip_scalars(sumsq: torch.Tensor, step_scalars: torch.Tensor, max_norm: float, pre_scale: float = 1.0, eps: float = 1e-6, out=None,
+                      sync: bool = False):
+    """From the sum of squares to what the optimizer reads (dga_grad_clip_scalars): sumsq a float64 [1] device tensor (grad_sumsq's, possibly
+    all-reduced across ranks in between), step_scalars the optimizer's float32 [4], of which only element 3 is written -> the named tuple
+    (norm, coef, skip).  One lane on the device, float64, rounded once to float32 on store:
+      finite = isfinite(sumsq[0])
+      normd  = pre_scale sqrt(sumsq[0])                      the norm of the unscaled gradients; pre_scale = 1 / loss_scale
+      coefd  = min(1, max_norm / (normd + eps))              torch.nn.utils.clip_grad_norm_'s; max_norm = inf never clips; 0 / 0 gives 1
+      norm[0] = f32(normd), non-finite as it comes;  coef[0] = finite ? f32(coefd) : 0;  step_scalars[3] = finite ? f32(pre_scale coefd) : 0
+      skip[0] = finite ? 0 : 1                               int32, overwritten at every call
+    norm and coef are float32 [1] device tensors (parameters that stay with torch's optimizer multiply their gradients by coef), skip is
+    the int32 [1] that adamw_per_block_cast_to_fp8_transposed(..., skip=) reads.  max_norm >= 0 (it may be inf), pre_scale finite and > 0,
+    eps finite and >= 0: launch arguments, C doubles.  out=(norm, coef, skip) takes the caller's tensors.  Nothing is read back: capturable."""
+    _require(isinstance(sumsq, torch.Tensor), "sumsq must be a tensor")
+    _want(sumsq, "sumsq", torch.float64, (1,))
+    mx, ps, e = _clip_args(step_scalars, max_norm, pre_scale, eps)
+    outs = _outputs(out, _CLIP_SPECS, sumsq.device, "out must be (norm, coef, skip)")
+    return GradClip(*_clip_run(sumsq, step_scalars, mx, ps, e, outs, sync))
+
+
+def clip_grad_norm_step_scalars(tensors, step_scalars: torch.Tensor, max_norm: float, pre_scale: float = 1.0, eps: float = 1e-6, out=None):
+    """grad_sumsq(tensors) then grad_clip_scalars(sumsq, step_scalars, max_norm, pre_scale, eps): the global gradient norm, the clip
+    coefficient into step_scalars[3] and the skip flag, with nothing decided on the host -> the named tuple (norm, coef, skip, sumsq).
+    out=(norm, coef, skip, sumsq) takes the caller's tensors.  Every argument is checked before the first launch.  Capturable: a captured
+    graph runs weight gradient -> this -> adamw_per_block_cast_to_fp8_transposed(..., skip=skip) -> the next GEMMs."""
+    _require(out is None or (isinstance(out, (tuple, list)) and len(out) == 4), "out must be (norm, coef, skip, sumsq)")
+    tensors, sumsq = _sumsq_args(tensors, None if out is None else out[3], False)
+    mx, ps, e = _clip_args(step_scalars, max_norm, pre_scale, eps)
+    outs = _outputs(None if out is None else tuple(out[:3]), _CLIP_SPECS, tensors[0].device, "out must be (norm, coef, skip, sumsq)")
+    sumsq = _sumsq_run(tensors, sumsq, False, False)
+    return GradClipNorm(*_clip_run(sumsq, step_scalars, mx, ps, e, outs, False), sumsq)
 
 
 def route_tokens(expert_ids: torch.Tensor, groups: int):

@@ -3,6 +3,8 @@
 //   dga_adamw_cast_to_fp8_128x128_transposed   w, m, v (in place), grad, step_scalars {lr, bc1, bc2s, grad_scale} on the device
 //                                              -> (qt, sft), optionally (q_row, sf_row): dga_cast_to_fp8_128x128_transposed of the w it
 //                                                 leaves behind, byte for byte
+//   dga_adamw_cast_to_fp8_128x128_transposed_skip   the same with a device flag (dga_grad_clip_scalars writes it): where skip[0] != 0 nothing
+//                                              is stored to w, m and v, whatever grad holds, and the codes are those of the unchanged w
 // 16 bytes in and 12 out per element for the update, 1 (2) out for the codes: 30 with fp32 moments and both layouts, 22 with bf16 moments;
 // a separate optimizer and quantiser move 34.  Per element, every operation in fp32 and rounded on its own (this unit's text is compiled
 // without contraction, the pragma below; division and square root are the correctly rounded ones, subnormals are kept):
@@ -58,9 +60,10 @@ __global__ void __launch_bounds__(256) adamw_cast_128x128_transposed_kernel(floa
                                                                             const float *step_scalars, float beta1, float beta2, float eps,
                                                                             float weight_decay, uint8_t *qt, float *sft, uint8_t *q_row,
                                                                             float *sf_row, int64_t n, int64_t k, uint32_t nb_n,
-                                                                            uint32_t kb_n, uint32_t vec, bool ue8m0)
+                                                                            uint32_t kb_n, uint32_t vec, bool ue8m0, const int32_t *skip)
 {
     const int t = threadIdx.x;
+    const bool step = !skip || skip[0] == 0;   // (uniform) a skipped step stores nothing to w, m and v: the codes are those of w as it is
     const BlockTileAt at = block_tile_at(blockIdx.x, t, n, k, nb_n, kb_n);
     const int64_t c0 = at.c0, r0 = at.r0, g0 = at.g0;
     const float lr = step_scalars[0], bc1 = step_scalars[1];
@@ -96,19 +99,23 @@ __global__ void __launch_bounds__(256) adamw_cast_128x128_transposed_kernel(floa
             Elem<TM>::unpack8(rm, mm);
             Elem<TM>::unpack8(rv, vv);
             Elem<TG>::unpack8(rg, gg);
-            adamw8(s, x[p], mm, vv, gg);
-            Store8<float>::run(w, at_e, x[p], true);
-            Store8<TM>::run(m, at_e, mm, true);
-            Store8<TM>::run(v, at_e, vv, true);
+            if (step) {
+                adamw8(s, x[p], mm, vv, gg);
+                Store8<float>::run(w, at_e, x[p], true);
+                Store8<TM>::run(m, at_e, mm, true);
+                Store8<TM>::run(v, at_e, vv, true);
+            }
         } else {
             load8_bounded<float>(w, at_e, x[p], vec_w, c0, k);
             load8_bounded<TM>(m, at_e, mm, vec_m, c0, k);
             load8_bounded<TM>(v, at_e, vv, vec_v, c0, k);
             load8_bounded<TG>(grad, at_e, gg, vec_g, c0, k);
-            adamw8(s, x[p], mm, vv, gg);
-            store8_bounded<float>(w, at_e, x[p], vec_w, c0, k);
-            store8_bounded<TM>(m, at_e, mm, vec_m, c0, k);
-            store8_bounded<TM>(v, at_e, vv, vec_v, c0, k);
+            if (step) {
+                adamw8(s, x[p], mm, vv, gg);
+                store8_bounded<float>(w, at_e, x[p], vec_w, c0, k);
+                store8_bounded<TM>(m, at_e, mm, vec_m, c0, k);
+                store8_bounded<TM>(v, at_e, vv, vec_v, c0, k);
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[p][j] = c0 + j < k ? x[p][j] : 0.f;   // (eps = 0 makes 0 / 0 of the zeros beyond k)
         }
@@ -119,10 +126,10 @@ __global__ void __launch_bounds__(256) adamw_cast_128x128_transposed_kernel(floa
 
 }  // namespace dga
 
-extern "C" int dga_adamw_cast_to_fp8_128x128_transposed(void *w, void *m, void *v, int moment_dtype, const void *grad, int grad_dtype,
-                                                        const float *step_scalars, float beta1, float beta2, float eps, float weight_decay,
-                                                        int64_t groups, int64_t n, int64_t k, void *qt, float *sft, void *q_row,
-                                                        float *sf_row, int flags, void *stream)
+extern "C" int dga_adamw_cast_to_fp8_128x128_transposed_skip(void *w, void *m, void *v, int moment_dtype, const void *grad, int grad_dtype,
+                                                             const float *step_scalars, float beta1, float beta2, float eps,
+                                                             float weight_decay, int64_t groups, int64_t n, int64_t k, void *qt, float *sft,
+                                                             void *q_row, float *sf_row, int flags, const int32_t *skip, void *stream)
 {
     using namespace dga;
     // run_cast's order: flags, shape, nothing to do, pointers, dtypes, the ranges and the grid
@@ -148,7 +155,7 @@ extern "C" int dga_adamw_cast_to_fp8_128x128_transposed(void *w, void *m, void *
         hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(groups * nb_n * kb_n)), dim3(256), 0, static_cast<hipStream_t>(stream),
                            static_cast<float *>(w), m, v, grad, step_scalars, beta1, beta2, eps, weight_decay, static_cast<uint8_t *>(qt), sft,
                            static_cast<uint8_t *>(q_row), sf_row, n, k, static_cast<uint32_t>(nb_n), static_cast<uint32_t>(kb_n), vec,
-                           (flags & DGA_CAST_UE8M0) != 0);
+                           (flags & DGA_CAST_UE8M0) != 0, skip);
     };
     const auto with_types = [&](auto tg, auto tm) {
         using TG = decltype(tg);
@@ -161,4 +168,13 @@ extern "C" int dga_adamw_cast_to_fp8_128x128_transposed(void *w, void *m, void *
     else if (moment_dtype == DGA_DT_FP32) with_types(Bf16Tag{}, float{});
     else with_types(Bf16Tag{}, Bf16Tag{});
     return record_hip(hipGetLastError());
+}
+
+extern "C" int dga_adamw_cast_to_fp8_128x128_transposed(void *w, void *m, void *v, int moment_dtype, const void *grad, int grad_dtype,
+                                                        const float *step_scalars, float beta1, float beta2, float eps, float weight_decay,
+                                                        int64_t groups, int64_t n, int64_t k, void *qt, float *sft, void *q_row,
+                                                        float *sf_row, int flags, void *stream)
+{
+    return dga_adamw_cast_to_fp8_128x128_transposed_skip(w, m, v, moment_dtype, grad, grad_dtype, step_scalars, beta1, beta2, eps, weight_decay,
+                                                         groups, n, k, qt, sft, q_row, sf_row, flags, nullptr, stream);
 }

@@ -586,6 +586,50 @@ int dga_adamw_cast_to_fp8_128x128_transposed(void *w, void *m, void *v, int mome
                                              int64_t groups, int64_t n, int64_t k, void *qt, float *sft, void *q_row, float *sf_row,
                                              int flags, void *stream);
 
+/* The same step behind a device flag: skip (int32 [1] on the device, NULL = no flag; dga_grad_clip_scalars writes one) is read by the
+ * kernel, one uniform branch.  Where skip[0] != 0 nothing is stored to w, m and v -- their bits after the call are their bits before,
+ * whatever grad holds, NaN and infinities included -- and the codes are formed from the unchanged w: (qt, sft) and (q_row, sf_row) are
+ * dga_cast_to_fp8_128x128_transposed(w) byte for byte, every element of every output written, so the GEMMs behind it in a captured graph
+ * read valid operands.  Where skip[0] == 0, and with skip == NULL, every bit of every result is the entry's above, which forwards here
+ * with NULL.  The step number stays the caller's: it reads skip back when convenient and does not advance step after a skipped one. */
+int dga_adamw_cast_to_fp8_128x128_transposed_skip(void *w, void *m, void *v, int moment_dtype, const void *grad, int grad_dtype,
+                                                  const float *step_scalars, float beta1, float beta2, float eps, float weight_decay,
+                                                  int64_t groups, int64_t n, int64_t k, void *qt, float *sft, void *q_row, float *sf_row,
+                                                  int flags, const int32_t *skip, void *stream);
+
+/* The global gradient norm on the device (csrc/dga_grad_norm.hip): sumsq[0] = sum_i sum_e x_i[e]^2 over `count` contiguous tensors of
+ * numel[i] elements (0 allowed) and dtypes[i] = DGA_DT_FP32 or DGA_DT_BF16 (they may be mixed; fp16 is refused, as by the optimizer),
+ * all on one device.  accumulate != 0: sumsq[0] = fl(sumsq[0] + sum), added last, so that several calls build one sum.  Every product and
+ * every sum is float64: the inputs convert exactly and their squares are exact (48 significant bits) and can neither overflow nor
+ * underflow; subnormals are kept; the only roundings are the additions':  |sumsq - exact| <= (n + 1) 2^-53 exact  for n elements.  A NaN
+ * or an infinity anywhere makes sumsq non-finite and nothing else can: isfinite(sumsq) is the overflow check of a loss-scaled step.
+ * The order of the additions is fixed by the list of (numel, dtype) alone -- not by the pointers, their alignment, the device or the
+ * stream -- without floating-point atomics: two runs give the same bits.  Stage 1: one workgroup per chunk of DGA_GRAD_SUMSQ_CHUNK
+ * consecutive elements of one tensor (a chunk never spans two), each lane its fixed elements in ascending order, the lanes by a fixed
+ * tree, one float64 partial per chunk into the workspace; the tensor table is a kernel argument, 64 list entries per launch, longer
+ * lists take more stage-1 launches into disjoint partial ranges.  Stage 2: one workgroup adds the partials in a fixed order and writes
+ * sumsq.  A pointer short of 16 bytes takes bounded loads for that tensor alone: the same bits.  dga_grad_sumsq_workspace_bytes: 8 bytes
+ * per chunk (0 for a list the entry refuses or an empty one).  Nothing is allocated or read back (capturable).  Checks in this order,
+ * every code before the first launch: DGA_E_SHAPE: a negative count or numel;  DGA_E_NULL: sumsq, the three arrays with count > 0, a
+ * tensor with numel > 0, the workspace when there is a chunk;  DGA_E_DTYPE;  DGA_E_RANGE: more chunks than a 31-bit grid holds, a
+ * workspace that is too small or not 8-byte aligned.  count == 0, or all tensors empty, still writes sumsq = accumulate ? sumsq : 0. */
+#define DGA_GRAD_SUMSQ_CHUNK 16384
+int64_t dga_grad_sumsq_workspace_bytes(int count, const int64_t *numel);
+int dga_grad_sumsq(const void *const *tensors, const int64_t *numel, const int *dtypes, int count, double *sumsq, int accumulate,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+
+/* From the sum of squares (possibly all-reduced across ranks in between) to what the optimizer reads.  One lane, float64, one rounding
+ * to fp32 on store:
+ *   finite = isfinite(sumsq[0])
+ *   normd  = pre_scale * sqrt(sumsq[0])               the norm of the unscaled gradients; pre_scale = 1 / loss_scale
+ *   q      = max_norm / (normd + eps);  coefd = q < 1 ? q : 1     torch.nn.utils.clip_grad_norm_'s; +inf never clips; 0 / 0 gives 1
+ *   norm[0] = f32(normd) (non-finite as it comes);  coef[0] = finite ? f32(coefd) : 0;  step_scalars[3] = finite ? f32(pre_scale coefd) : 0
+ *   skip[0] = finite ? 0 : 1                          int32, overwritten at every call
+ * step_scalars is the optimizer's fp32 [4]; elements 0 .. 2 are not touched.  DGA_E_NULL: any pointer;  DGA_E_RANGE: max_norm negative or
+ * NaN, pre_scale not a finite number > 0, eps negative, NaN or infinite.  One launch, nothing read back (capturable). */
+int dga_grad_clip_scalars(const double *sumsq, double max_norm, double pre_scale, double eps, float *step_scalars, float *norm,
+                          float *coef, int32_t *skip, void *stream);
+
 /* ---- the framework's 28-int Config (deep_gemm_ascend/framework/csrc/jit/get_best_config.hpp) ---- */
 
 /* struct Config in declaration order (get_best_config.hpp:12-31), 28 uint32. */
