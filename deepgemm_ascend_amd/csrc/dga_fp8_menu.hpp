@@ -3,6 +3,7 @@
 // (dga_launch_menu_{a,b,c}.hip -- split so that `make -j` compiles the menu in parallel).  This is the AOT replacement
 // of the reference's per-shape cmake-subprocess JIT (/root/reference/deep_gemm_ascend/framework/csrc/jit/compiler.hpp:26-93).
 #pragma once
+#include "dga_fp8_plan.hpp"
 #include "dga_internal.hpp"
 #include "gemm_fp8_kernel.hpp"
 
@@ -115,20 +116,16 @@ int launch_ue8m0_w4(const GemmParams &p, hipStream_t stream);
 int launch_bf16u(int bm, int bn, const GemmParams &p, hipStream_t stream);
 
 // one-launch Stream-K build of the 256 x 256 continuous kernel (gemm_fp8_streamk_kernel.hpp; dga_launch_menu_k.hip): dense rasters of
-// full tiles, fp32 partial tiles through the caller's workspace.  DGA_E_TILING: not a problem it takes
+// full tiles, fp32 partial tiles through the caller's workspace (streamk_workspace_bytes, dga_fp8_plan.hpp).  DGA_E_TILING: not a problem it takes
 int launch_streamk(const GemmParams &p, void *ws, size_t ws_bytes, bool ue8m0, hipStream_t stream);
-size_t streamk_workspace_bytes();
 // ... and of the bf16-exact policy's persistent 128 x 256 kernel (gemm_fp8_bf16x_streamk_kernel.hpp; dga_launch_menu_m.hip): any dense
 // raster with a partial last round.  DGA_E_TILING: not a launch it takes (nothing to cut, no workspace, co-residency not guaranteed)
 int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, Out out = Out::Bf16);   // no Out::F32Rows form
-size_t bx_streamk_workspace_bytes();
 // workgroups a launch on this stream can count on being resident together, one per CU; 0 when a CU mask narrows the queue
 int coresident_workgroups(hipStream_t stream);
 // one-launch split-K for decode rows under the bf16-exact policy (gemm_fp8_bf16x_dsk_kernel.hpp; dga_launch_menu_n.hip): dense problems of
-// at most as many 64 x 128 tiles as CUs; `splits` = the tiling's splitkFactor.  DGA_E_TILING: not a launch it takes
+// at most as many 64 x 128 tiles as CUs; `splits` = the tiling's splitkFactor (bx_dsk_splits, bx_dsk_workspace_bytes: dga_fp8_plan.hpp).  DGA_E_TILING: not a launch it takes
 int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, Out out = Out::Bf16);   // no Out::F32Rows form
-int bx_dsk_splits(int64_t tiles, int kb, int want, int cus);
-size_t bx_dsk_workspace_bytes(int64_t tiles, int splits);
 
 // persistent continuous-pipeline build of the 256x256 tile (gemm_fp8_cont_persistent_kernel.hpp, dispatchPolicyTag 6): dense
 // rasters of full tiles only -- launch_cont_persistent returns DGA_E_TILING for anything else

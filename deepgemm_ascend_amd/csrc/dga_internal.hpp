@@ -75,4 +75,11 @@ int pad_rows_strided(const void *src0, int64_t stride0, void *dst0, int64_t rows
                      int64_t rows1, int64_t src_row_bytes, int64_t dst_row_bytes, hipStream_t stream);
 // dense 256x256 tilings: turn a small last partial wave into a K-split tail (dga_tiling.cpp)
 void apply_tail_split(dga_tiling_t &t, uint32_t cus);
+// the wave grid and LDS bytes of a tiling that names a tile, a stage count and a schedule only (a cache row, the predictor's pick)
+namespace tiling {
+void complete_from_menu(dga_tiling_t &t);
+// the compiled menu's first build of a tile (stages 0: of any stage count; loaders: one with loader waves); nullptr: none
+struct MenuEntry;
+const MenuEntry *find_build(int bm, int bn, int stages = 0, bool loaders = false);
+}
 }  // namespace dga

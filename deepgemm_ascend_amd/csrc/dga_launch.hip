@@ -161,11 +161,7 @@ static int check_tiling(const dga_tiling_t &t)
 {
     if (t.dispatchPolicyTag & ~(DGA_POLICY_UE8M0_SCALES | 7)) return DGA_E_TILING;      // bits nobody defined
     const int tag = t.dispatchPolicyTag & 7;
-    switch (t.kernelSerial) {
-        case DGA_KERNEL_COMMON: case DGA_KERNEL_SMALL: case DGA_KERNEL_PADDING_COMMON: case DGA_KERNEL_STREAMK:
-        case DGA_KERNEL_STREAMK_TAIL: case DGA_KERNEL_SPLITK_WORKGROUP: case DGA_KERNEL_STREAMK_ONE_LAUNCH: break;
-        default: return DGA_E_TILING;
-    }
+    if (!known_kernel_serial(t.kernelSerial)) return DGA_E_TILING;
     if (t.k1 != 0 && t.k1 != 128) return DGA_E_TILING;                                  // one scale block per k step
     if (t.splitkFactor > 1024) return DGA_E_RANGE;
     if (t.reserved0) return DGA_E_TILING;
@@ -528,19 +524,18 @@ static int run_bf16x(const Fp8Call &c, const dga_tiling_t &t, const Bf16xVariant
     // last partial round -- at most half of the CUs' worth of tiles -- is covered by 64 x 128 tiles (four per parent tile, two
     // workgroups to a CU) in a second launch.  Same arithmetic in the same k order: the bytes are those of one launch.
     if (t.kernelSerial == DGA_KERNEL_STREAMK_TAIL && dense && vx->bm == 128 && vx->bn == 256) {
-        const int tiles = p.tiles_m * p.tiles_n, cus = static_cast<int>(device_cus());
-        const int tail = tiles % cus, main_tiles = tiles - tail;
+        const PartialRound pr = partial_round(p.tiles_m * p.tiles_n, device_cus(), 2);
         const Bf16xVariant *vq = find_bf16x_variant(64, 128);
-        if (tail > 0 && tail * 2 <= cus && main_tiles > 0 && vq && vq->bm == 64 && vq->bn == 128) {
+        if (pr && vq && vq->bm == 64 && vq->bn == 128) {
             GemmParams pm = p;
-            pm.launch_tiles = main_tiles;
+            pm.launch_tiles = static_cast<int>(pr.main_tiles);
             rc = launch_bf16x_persistent(pm, c.kind, c.stream);    // (DGA_E_TILING: a launch it does not take -- one k block)
             if (rc == DGA_E_TILING) rc = vx->launch[form](pm, c.stream);
             if (rc != DGA_OK) return rc;
             GemmParams pt = p;  // tiles_m / tiles_n / raster_group stay those of the parent raster
-            pt.tail_begin = main_tiles;
+            pt.tail_begin = static_cast<int>(pr.main_tiles);
             pt.tail_sub = 2;
-            pt.launch_tiles = tail * 4;
+            pt.launch_tiles = static_cast<int>(pr.tail * 4);
             return vq->launch[form](pt, c.stream);
         }
     }
@@ -556,7 +551,7 @@ static int run_bf16x(const Fp8Call &c, const dga_tiling_t &t, const Bf16xVariant
     // runs them, the last partial round cut along K with fp32 partial tiles through the workspace.  What it does not take (no partial
     // round, no workspace, a CU mask) runs the builds below.
     if (t.kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH && vx->bm == 128 && vx->bn == 256 && dense && c.kind != Out::F32Rows) {
-        const size_t need = bx_streamk_workspace_bytes();
+        const size_t need = bx_streamk_workspace_bytes(device_cus());
         if (uint8_t *sk_ws = carve(need)) {
             rc = launch_bf16x_streamk(p, sk_ws, need, c.stream, c.kind);
             if (rc != DGA_E_TILING) return rc;
@@ -633,7 +628,7 @@ static int run_fast(const Fp8Call &c, const dga_tiling_t &t, const Variant *v, b
     // ---- Stream-K proper (kernelSerial 7): one launch, the raster's k blocks cut evenly over the CUs, fp32 partial tiles through the
     //      workspace (gemm_fp8_streamk_kernel.hpp).  What it does not take (ragged shapes, no workspace) runs the tile kernel below.
     if (t.kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH && !c.clock_stamps && dense && v->bm == 256 && v->bn == 256) {
-        const size_t need = streamk_workspace_bytes();
+        const size_t need = streamk_workspace_bytes(device_cus());
         if (uint8_t *sk_ws = carve(need)) {
             rc = launch_streamk(p, sk_ws, need, ue8m0, stream);
             if (rc != DGA_E_TILING) return rc;
@@ -646,21 +641,20 @@ static int run_fast(const Fp8Call &c, const dga_tiling_t &t, const Variant *v, b
     //      wave quantisation) without partial sums: every output still comes from one accumulation in k order, the
     //      bytes are those of a single launch.
     if (t.kernelSerial == DGA_KERNEL_STREAMK_TAIL && c.groups == 1 && !c.masked_m && !c.m_indices && v->bm == 256 && v->bn == 256) {
-        const int tiles = p.tiles_m * p.tiles_n, cus = static_cast<int>(device_cus());
-        const int tail = tiles % cus, main_tiles = tiles - tail;
+        const PartialRound pr = partial_round(p.tiles_m * p.tiles_n, device_cus(), 2);
         const Variant *vq = find_variant(128, 128, 0, 0, 3);
         // (up to half of the CUs' worth of parent tiles: two quarter tiles per CU.  A tail longer than a quarter of the RASTER used to
         //  fault -- the kernel read a quarter-tile index beyond the parent tile count as a group index; fixed there, tested in
         //  tests/test_gemm_gpu.py)
-        if (tail > 0 && tail * 2 <= cus && main_tiles > 0 && vq) {
+        if (pr && vq) {
             GemmParams pm = p;
-            pm.launch_tiles = main_tiles;
+            pm.launch_tiles = static_cast<int>(pr.main_tiles);
             rc = launch_main(pm);
             if (rc != DGA_OK) return rc;
             GemmParams pt = p;  // tiles_m / tiles_n / raster_group stay those of the parent raster
-            pt.tail_begin = main_tiles;
+            pt.tail_begin = static_cast<int>(pr.main_tiles);
             pt.tail_sub = 2;
-            pt.launch_tiles = tail * 4;
+            pt.launch_tiles = static_cast<int>(pr.tail * 4);
             // (the quarter tiles give a CU at most two workgroups: the 4 + 4 loader-wave build of the tile, -1..-2 % on the whole call:
             //  1024 x 18432 x 7168 139.8 -> 136.9 us, 4608 x 4096 x 7168 139.2 -> 136.2; same arithmetic, same bytes)
             if (ue8m0) {

@@ -7,8 +7,6 @@
 #include "gemm_fp8_streamk_kernel.hpp"
 namespace dga {
 
-size_t streamk_workspace_bytes() { return static_cast<size_t>(device_cus()) * (256 * 256 * 4 + 8) + 256; }
-
 template <int MATH>
 static int launch_streamk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
@@ -16,7 +14,7 @@ static int launch_streamk_one(const GemmParams &p, const StreamKArgs &sk, unsign
     return launch_kernel<gemm_fp8_blockscaled_nt_streamk_kernel<Cfg, MATH>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p, sk);
 }
 
-// ws: the caller's workspace, at least streamk_workspace_bytes().  DGA_E_TILING: not a problem this kernel takes (the caller then
+// ws: the caller's workspace, at least streamk_workspace_bytes(CUs).  DGA_E_TILING: not a problem this kernel takes (the caller then
 // runs the tiling's tile kernel).  ue8m0: the hardware-scale form (power-of-two block scales).
 int launch_streamk(const GemmParams &p, void *ws, size_t ws_bytes, bool ue8m0, hipStream_t stream)
 {
@@ -27,7 +25,7 @@ int launch_streamk(const GemmParams &p, void *ws, size_t ws_bytes, bool ue8m0, h
     const int64_t grid = coresident_workgroups(stream);
     if (grid <= 0) return DGA_E_TILING;
     // (a workspace that is missing, short or misaligned: the tile kernel too -- the documented fall-back, not an error)
-    if (!ws || ws_bytes < static_cast<size_t>(grid) * (256 * 256 * 4) + static_cast<size_t>(grid) * 8) return DGA_E_TILING;
+    if (!ws || ws_bytes < streamk_workspace_bytes(static_cast<uint32_t>(grid))) return DGA_E_TILING;
     if (reinterpret_cast<uintptr_t>(ws) & 15) return DGA_E_TILING;
     StreamKArgs sk;
     sk.partials = static_cast<float *>(ws);

@@ -33,8 +33,6 @@ int coresident_workgroups(hipStream_t stream)
     return cus;
 }
 
-size_t bx_streamk_workspace_bytes() { return static_cast<size_t>(device_cus()) * (128 * 256 * 4 + 8) + 256; }
-
 template <bool KTAIL, int OUT = 0>
 static int launch_bx_streamk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
@@ -42,7 +40,7 @@ static int launch_bx_streamk_one(const GemmParams &p, const StreamKArgs &sk, uns
     return launch_kernel<gemm_fp8_bf16x_streamk_kernel<KTAIL, OUT>>(grid, Cfg::NT, Cfg::LDS_BYTES, stream, p, sk);
 }
 
-// ws: the caller's workspace, at least bx_streamk_workspace_bytes().  DGA_E_TILING: not a launch this kernel takes (no partial round to
+// ws: the caller's workspace, at least bx_streamk_workspace_bytes(CUs).  DGA_E_TILING: not a launch this kernel takes (no partial round to
 // cut, a layout it does not have, co-residency not guaranteed, no or too small a workspace): the caller runs the tiling's tile kernel.
 int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStream_t stream, Out out)
 {
@@ -55,7 +53,7 @@ int launch_bf16x_streamk(const GemmParams &p, void *ws, size_t ws_bytes, hipStre
     if (tiles <= 0 || tiles > 0x3FFFFFFF) return DGA_E_TILING;
     const BxStreamKPlan pl = bx_streamk_plan(static_cast<int>(tiles), grid, p.kb_n);
     if (pl.form == 0) return DGA_E_TILING;     // nothing to cut: the persistent kernel
-    if (!ws || ws_bytes < static_cast<size_t>(grid) * (128 * 256 * 4 + 8) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DGA_E_TILING;
+    if (!ws || ws_bytes < bx_streamk_workspace_bytes(grid) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DGA_E_TILING;
     StreamKArgs sk;
     sk.partials = static_cast<float *>(ws);
     sk.flags = reinterpret_cast<unsigned long long *>(sk.partials + static_cast<size_t>(grid) * (128 * 256));

@@ -9,24 +9,6 @@ namespace dga {
 
 static constexpr int kDskExtraHalfBlocks = 2;
 
-// the splits a launch of `tiles` 64 x 128 tiles over kb k blocks runs with, given the tiling's splitkFactor: every workgroup resident
-// at once (`cus`), every k slice at least two blocks, at most DskCfg::MAX_S workgroups per tile
-int bx_dsk_splits(int64_t tiles, int kb, int want, int cus)
-{
-    if (tiles <= 0 || tiles > cus) return 0;
-    int s = want > 0 ? want : 1;
-    if (s > DskCfg::MAX_S) s = DskCfg::MAX_S;
-    if (s > cus / tiles) s = static_cast<int>(cus / tiles);
-    if (s > kb / 4) s = kb / 4;
-    return s;      // 0: the problem is too short along K (fewer than four k blocks)
-}
-
-size_t bx_dsk_workspace_bytes(int64_t tiles, int splits)
-{
-    if (splits <= 1) return 0;
-    return static_cast<size_t>(tiles) * (splits - 1) * (DskCfg::SLOT_FLOATS * 4 + 8) + 256;
-}
-
 template <bool KTAIL, bool IMG = true, int OUT = 0>
 static int launch_bx_dsk_one(const GemmParams &p, const StreamKArgs &sk, unsigned grid, hipStream_t stream)
 {
@@ -34,7 +16,7 @@ static int launch_bx_dsk_one(const GemmParams &p, const StreamKArgs &sk, unsigne
     return launch_kernel<gemm_fp8_bf16x_dsk_kernel<KTAIL, IMG, OUT>>(grid, DskCfg::NT, kLds, stream, p, sk);
 }
 
-// splits: the tiling's splitkFactor (clamped by bx_dsk_splits).  ws: the caller's workspace, bx_dsk_workspace_bytes() at least where the
+// splits: the tiling's splitkFactor (clamped by bx_dsk_splits, dga_fp8_plan.hpp).  ws: the caller's workspace, bx_dsk_workspace_bytes() at least where the
 // launch splits across workgroups.  DGA_E_TILING: not a launch this kernel takes (a layout it does not have, more tiles than CUs, fewer
 // than four k blocks, co-residency not guaranteed, no or too small a workspace): the caller runs the tiling's tile kernel.
 int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes, hipStream_t stream, Out out)
@@ -53,7 +35,7 @@ int launch_bf16x_dsk(const GemmParams &p, int splits, void *ws, size_t ws_bytes,
     StreamKArgs sk{};
     if (s > 1) {
         const size_t slots = static_cast<size_t>(tiles) * (s - 1);
-        if (!ws || ws_bytes < slots * (DskCfg::SLOT_FLOATS * 4 + 8) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DGA_E_TILING;
+        if (!ws || ws_bytes < bx_dsk_workspace_bytes(tiles, s) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DGA_E_TILING;
         sk.partials = static_cast<float *>(ws);
         sk.flags = reinterpret_cast<unsigned long long *>(sk.partials + slots * DskCfg::SLOT_FLOATS);
         // a flag is raised when it holds this launch's epoch -- 64 mixed bits no earlier launch used and stale workspace bytes will not

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "dga_fp8_plan.hpp"
 #include "dga_hip.h"
 #include "dga_internal.hpp"
 
@@ -108,19 +109,13 @@ static std::shared_ptr<const Model> model()
 
 static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
-// LDS bytes of one stage (dga_device_common.hpp GemmCfg with 256 DMA threads; the 8-wave tile gives the same figure)
-static inline uint32_t stage_bytes(uint32_t m1, uint32_t n1)
-{
-    return std::max(m1, 32u) * 128 + n1 * 128 + ((m1 + 8 + 255) / 256) * 256 * 4;
-}
-
 // One candidate -> the 16 inputs.  Must match harness/train_predictor.py feature_row() exactly.
 static void feature_row(uint32_t m, uint32_t n, uint32_t k, const Cand &c, float *f)
 {
     const uint32_t tm = cdiv(m, c.m1), tn = cdiv(n, c.n1);
     const uint64_t tiles = static_cast<uint64_t>(tm) * tn * c.splitk;
     const uint32_t waves = (c.m1 == 256 && c.n1 == 256) ? 8 : 4;
-    const uint32_t lds = stage_bytes(c.m1, c.n1) * (c.stages == 3 ? 3 : 2);
+    const uint32_t lds = dga::fp8_stage_bytes(c.m1, c.n1) * (c.stages == 3 ? 3 : 2);
     const uint32_t wg_per_cu = std::max(1u, std::min(160u * 1024u / lds, 2048u / (waves * 64)));
     const uint64_t rounds = (tiles + 256ull * wg_per_cu - 1) / (256ull * wg_per_cu);
     const uint32_t kb = cdiv(k, 128), kbps = cdiv(kb, c.splitk);
@@ -159,16 +154,6 @@ static float forward(const Model &mo, const float *f)
     return std::exp(h[0]);  // the model is trained on log(microseconds)
 }
 
-static bool has_variant(int bm, int bn)
-{
-    for (int i = 0; i < variant_count(); ++i) {
-        int vm, vn, wm, wn, lds;
-        variant_info(i, &vm, &vn, &wm, &wn, &lds);
-        if (vm == bm && vn == bn) return true;
-    }
-    return false;
-}
-
 // the list harness/sweep.py candidates() times (tiles x stages x split-K x schedule, one raster per candidate)
 static std::vector<Cand> candidates(uint32_t m, uint32_t n, uint32_t k)
 {
@@ -177,7 +162,7 @@ static std::vector<Cand> candidates(uint32_t m, uint32_t n, uint32_t k)
     const uint32_t kb = cdiv(k, 128);
     for (const auto &t : tiles) {
         const uint32_t bm = t[0], bn = t[1];
-        if (!has_variant(bm, bn)) continue;
+        if (!dga::tiling::find_build(bm, bn)) continue;
         if (bm >= 2 * std::max(m, 16u) && bm > 16) continue;  // a tile twice the problem is pointless
         const uint64_t blocks = static_cast<uint64_t>(cdiv(m, bm)) * cdiv(n, bn);
         const bool three = bm <= 128;   // every tile below 256 rows has a 3-stage build
@@ -203,7 +188,7 @@ static uint8_t raster_for(uint32_t m, uint32_t n, const Cand &c)
     // as select_mi355x: a near-square patch of the tiles an XCD runs at the same time
     const uint32_t tiles_m = cdiv(m, c.m1);
     const uint32_t waves = (c.m1 == 256 && c.n1 == 256) ? 8 : 4;
-    const uint32_t lds = stage_bytes(c.m1, c.n1) * (c.stages == 3 ? 3 : 2);
+    const uint32_t lds = dga::fp8_stage_bytes(c.m1, c.n1) * (c.stages == 3 ? 3 : 2);
     const uint32_t wg_per_cu = std::max(1u, std::min(160u * 1024u / lds, 2048u / (waves * 64)));
     const uint64_t per_xcd = std::max<uint64_t>(1, (static_cast<uint64_t>(tiles_m) * cdiv(n, c.n1) * c.splitk) / 8);
     const uint32_t conc = static_cast<uint32_t>(std::min<uint64_t>(per_xcd, 32ull * wg_per_cu));
@@ -413,7 +398,7 @@ int dga_select_kernel_with_predictor_ex(const dga_problem_t *problem, dga_tiling
         const uint32_t kb = cdiv(problem->k, 128), per = cdiv(kb, pick->splitk);
         out->splitkFactor = static_cast<uint16_t>(cdiv(kb, per));
     }
-    const uint64_t blocks = static_cast<uint64_t>(cdiv(problem->m, pick->m1)) * cdiv(problem->n, pick->n1);
+    const uint64_t blocks = dga::raster_tiles(1, problem->m, problem->n, pick->m1, pick->n1);
     out->kernelSerial = out->splitkFactor > 1 ? DGA_KERNEL_STREAMK
                         : (blocks <= dga::device_cus() && problem->k <= 128) ? DGA_KERNEL_SMALL : DGA_KERNEL_COMMON;
     out->blockDim = static_cast<uint32_t>(blocks) * out->splitkFactor;
@@ -421,15 +406,7 @@ int dga_select_kernel_with_predictor_ex(const dga_problem_t *problem, dga_tiling
     // the build the sweep timed for this (tile, stage count): the menu's first entry with that tile AND that stage count
     // (what a tiling that names no wave grid resolves to in the launcher); the tile's first entry only if none matches
     out->wavesM = out->wavesN = 0;
-    for (int pass = 0; pass < 2 && !out->wavesM; ++pass)
-        for (int i = 0; i < dga::variant_count(); ++i) {
-            int vm, vn, wm, wn, lds;
-            dga::variant_info(i, &vm, &vn, &wm, &wn, &lds);
-            if (vm != pick->m1 || vn != pick->n1 || (pass == 0 && dga::variant_stages(i) != pick->stages)) continue;
-            out->wavesM = static_cast<uint8_t>(wm); out->wavesN = static_cast<uint8_t>(wn);
-            out->ldsBytes = static_cast<uint32_t>(lds);
-            break;
-        }
+    dga::tiling::complete_from_menu(*out);
     dga::prefer_loader_waves(*out);
     if (predicted_us) *predicted_us = best;
     dga::apply_tail_split(*out, dga::device_cus());  // the model picks the tile; a small last wave of 256x256 tiles is still cut along K

@@ -32,6 +32,7 @@
 #include <tuple>
 #include <vector>
 
+#include "dga_fp8_plan.hpp"
 #include "dga_hip.h"
 #include "dga_internal.hpp"
 
@@ -255,17 +256,29 @@ void select_reference(dga_tiling_t &t, const dga_platform_t &pf)
 // ---- MI355X mode -------------------------------------------------------------------------
 // Cost of running the problem with workgroup tile (bm, bn): rounds of the chip x time of one
 // tile, where one tile is bound by the slower of its MFMA work and its operand streaming.
-struct MenuEntry { int bm, bn, wm, wn, lds; };
+struct MenuEntry { int bm, bn, wm, wn, lds, stages; bool loaders; };
 
-static std::vector<MenuEntry> menu()
+// the compiled menu (dga_launch.hip kVariants), in its preference order
+static const std::vector<MenuEntry> &menu()
 {
-    std::vector<MenuEntry> v;
-    for (int i = 0; i < variant_count(); ++i) {
-        MenuEntry e{};
-        variant_info(i, &e.bm, &e.bn, &e.wm, &e.wn, &e.lds);
-        v.push_back(e);
-    }
+    static const std::vector<MenuEntry> v = [] {
+        std::vector<MenuEntry> m(variant_count());
+        for (int i = 0; i < variant_count(); ++i) {
+            variant_info(i, &m[i].bm, &m[i].bn, &m[i].wm, &m[i].wn, &m[i].lds);
+            m[i].stages = variant_stages(i);
+            m[i].loaders = variant_has_loader_waves(i);
+        }
+        return m;
+    }();
     return v;
+}
+
+// the menu's first build of a tile; stages 0: of any stage count; loaders: a build with loader waves (dispatchPolicyTag 4)
+const MenuEntry *find_build(int bm, int bn, int stages, bool loaders)
+{
+    for (const MenuEntry &e : menu())
+        if (e.bm == bm && e.bn == bn && (!stages || e.stages == stages) && (!loaders || e.loaders)) return &e;
+    return nullptr;
 }
 
 // MFMA issue efficiency of a wave tile: each k block costs (TM*TN) MFMAs of 32 cycles and
@@ -284,24 +297,16 @@ static double tile_cycles_per_kblock(const MenuEntry &e)
 
 }  // namespace tiling
 
-// Tail in quarter tiles (kernelSerial 5): more than one wave of 256x256 tiles with a small remainder -- the remainder would
-// cost a whole extra round at 1/8..1/4 occupancy; covered by 128x128 tiles (second launch) it occupies four times the
-// CUs for about half a round.  Applied to a dense tiling whatever chose the tile (heuristic or predictor).
 // LDS bytes of the compiled build a tiling resolves to: exact (tile, stages, wave grid) match, else the menu's first
 // build of that tile and stage count, else of that tile
 static uint32_t menu_lds_bytes(const dga_tiling_t &t)
 {
     const int stages = t.stages == 3 ? 3 : 2;
-    for (int pass = 0; pass < 3; ++pass)
-        for (int i = 0; i < variant_count(); ++i) {
-            int bm, bn, wm, wn, lds;
-            variant_info(i, &bm, &bn, &wm, &wn, &lds);
-            if (bm != t.m1 || bn != t.n1) continue;
-            if (pass < 2 && variant_stages(i) != stages) continue;
-            if (pass == 0 && t.wavesM && (wm != t.wavesM || wn != t.wavesN)) continue;
-            return static_cast<uint32_t>(lds);
-        }
-    return t.ldsBytes;
+    for (const tiling::MenuEntry &e : tiling::menu())
+        if (e.bm == t.m1 && e.bn == t.n1 && e.stages == stages && (!t.wavesM || (e.wm == t.wavesM && e.wn == t.wavesN))) return e.lds;
+    const tiling::MenuEntry *e = tiling::find_build(t.m1, t.n1, stages);
+    if (!e) e = tiling::find_build(t.m1, t.n1);
+    return e ? static_cast<uint32_t>(e->lds) : t.ldsBytes;
 }
 
 // Loader waves (dispatchPolicyTag 4): every 4-wave, 3-stage tile has a build with four extra waves that carry the whole
@@ -324,20 +329,15 @@ void prefer_loader_waves(dga_tiling_t &t, bool upgrade_plain)
     //  is the same kernel within 0.1 % under split-K)
     if (upgrade_plain && t.dispatchPolicyTag == DGA_POLICY_PLAIN && t.stages == 3 &&
         !(t.splitkFactor > 1 && t.m1 == 128 && t.n1 == 256)) {
-        for (int i = 0; i < variant_count(); ++i) {
-            int bm, bn, wm, wn, lds;
-            variant_info(i, &bm, &bn, &wm, &wn, &lds);
-            if (bm != t.m1 || bn != t.n1 || variant_stages(i) != 3 || !variant_has_loader_waves(i)) continue;
-            t.wavesM = static_cast<uint8_t>(wm); t.wavesN = static_cast<uint8_t>(wn);
-            t.ldsBytes = static_cast<uint32_t>(lds);
+        if (const tiling::MenuEntry *e = tiling::find_build(t.m1, t.n1, 3, true)) {
+            t.wavesM = static_cast<uint8_t>(e->wm); t.wavesN = static_cast<uint8_t>(e->wn);
+            t.ldsBytes = static_cast<uint32_t>(e->lds);
             t.dispatchPolicyTag = DGA_POLICY_LOADER_WAVES;
-            break;
         }
     }
     if (t.dispatchPolicyTag == DGA_POLICY_LOADER_WAVES && t.splitkFactor <= 1 && t.kernelSerial != DGA_KERNEL_STREAMK_TAIL &&
         t.m1 && t.n1 && !(t.contiguous && t.m1 > DGA_CONTIGUOUS_M_ALIGNMENT)) {
-        const uint64_t groups = t.contiguous ? 1 : std::max<uint32_t>(1, t.groups);
-        const uint64_t tiles = groups * ((t.m + t.m1 - 1) / t.m1) * ((t.n + t.n1 - 1) / t.n1);
+        const uint64_t tiles = raster_tiles(t.contiguous ? 1 : std::max<uint32_t>(1, t.groups), t.m, t.n, t.m1, t.n1);
         // the weight stream of the grouped layouts runs the persistent build whatever its tile count: that kernel moves the
         // weights and the outputs with the non-temporal policy (dga_launch.hip), worth more than the tile boundaries
         const bool weight_stream = t.contiguous ? (t.groups > 1 && static_cast<uint64_t>(t.m) <= static_cast<uint64_t>(t.groups) * DGA_CONTIGUOUS_M_ALIGNMENT)
@@ -365,15 +365,16 @@ void prefer_loader_waves(dga_tiling_t &t, bool upgrade_plain)
     }
 }
 
+// Tail in quarter tiles (kernelSerial 5): more than one wave of 256x256 tiles with a small remainder -- the remainder would
+// cost a whole extra round at 1/8..1/4 occupancy; covered by 128x128 tiles (second launch) it occupies four times the
+// CUs for about half a round.  Applied to a dense tiling whatever chose the tile (heuristic or predictor).
 void apply_tail_split(dga_tiling_t &t, uint32_t cus)
 {
     if (t.splitkFactor > 1 || t.m1 != 256 || t.n1 != 256 || t.groups > 1 || t.contiguous || !cus) return;
-    const uint64_t blocks = static_cast<uint64_t>((t.m + 255) / 256) * ((t.n + 255) / 256);
-    if (blocks <= cus) return;
-    const uint32_t tail = static_cast<uint32_t>(blocks % cus);
-    if (tail == 0 || tail * 4 > cus) return;
+    const PartialRound pr = partial_round(raster_tiles(1, t.m, t.n, 256, 256), cus, 4);
+    if (!pr) return;
     t.kernelSerial = DGA_KERNEL_STREAMK_TAIL;
-    t.blockDim = static_cast<uint32_t>(blocks - tail) + tail * 4;
+    t.blockDim = static_cast<uint32_t>(pr.launch_tiles());
 }
 
 namespace tiling {
@@ -394,35 +395,31 @@ struct DenseTileCost { int bm, bn; double us_per_kblock; };
 struct DenseCostModel {
     const DenseTileCost *tiles; int n_tiles;
     double share_exponent, launch_us, prologue_us, combine_us, slab_bytes_per_us, hbm_bytes_per_us, workgroup_bytes_per_us;
+    // the tile whose last partial round runs in quarter tiles (partial_round, dga_fp8_plan.hpp: a tail on at most 1 / tail_share_den
+    // of the CUs), and what that round then costs, in rounds: with the tail on at most a quarter of the CUs, and beyond
+    int tail_bm, tail_bn, tail_share_den;
+    double tail_round_quarter, tail_round_half;
+    double tall32_us_per_kblock;   // > 0: the 32-row build on a problem of more than 256 rows (warm operands) has its own figure
 };
 static const DenseTileCost kDenseTileCost[] = {{256, 256, 1.547}, {128, 256, 0.933}, {256, 128, 1.153}, {128, 128, 0.579},
                                                {64, 256, 0.650},  {64, 128, 0.367},  {32, 256, 0.449},  {32, 128, 0.256},
                                                {16, 256, 0.394},  {16, 128, 0.213}};
-static const DenseCostModel kFastModel = {kDenseTileCost, 10, 0.8845, 2.66, 1.31, 3.53, 5.09e6, 8.0e6, 48.6e3};
+// (a small last wave of 256 x 256 tiles is cut along K, apply_tail_split: half a round)
+static const DenseCostModel kFastModel = {kDenseTileCost, 10, 0.8845, 2.66, 1.31, 3.53, 5.09e6, 8.0e6, 48.6e3, 256, 256, 4, 0.5, 0.5, 0.0};
 // the bf16-exact policy's menu (dga_launch_menu_e.hip: three stages, no loader waves), fitted the same way on its own
 // device-timed sweep (scripts/bx_sweep.py, 214 + 120 shapes): held-out pick / best 1.019 geomean, max 1.28 (the hand-set model
 // of this policy's first version, fitted to 19 shapes timed through Python: 1.069, max 1.47)
 // (refitted after the MFMA results moved to VGPRs -- the Makefile's -amdgpu-mfma-vgpr-form note: the 128x128 / 64x256 / 64x128 / 32x128
 //  builds lost a v_accvgpr_read per MFMA and 14-19 % of their time on mid-M shapes, profiles/r03_vgpr_form.txt)
 static const DenseTileCost kBf16xTileCost[] = {{128, 256, 1.583}, {128, 128, 0.966}, {64, 256, 1.075}, {64, 128, 0.677}, {32, 128, 0.605}};
-static constexpr double kBf16x32RowTallUs = 0.442;   // the 32-row build on a problem of more than 256 rows (warm operands): its own figure
-static const DenseCostModel kBf16xModel = {kBf16xTileCost, 5, 0.529, 1.57, 3.02, 2.98, 5.10e6, 5.35e6, 39.9e3};
+// (the 128 x 256 tile's last partial round in 64 x 128 quarter tiles -- dga_launch.hip, kernelSerial 5: a quarter tile alone on a CU takes
+//  0.6 of a parent tile's time, two to a CU 0.85; scripts/bx_tail_ab.py, profiles/r05_bx_tail_ab.txt)
+static const DenseCostModel kBf16xModel = {kBf16xTileCost, 5, 0.529, 1.57, 3.02, 2.98, 5.10e6, 5.35e6, 39.9e3, 128, 256, 2, 0.62, 0.85, 0.442};
 static constexpr uint32_t kDenseSplits[] = {1, 2, 3, 4, 5, 6, 8, 16};   // what the sweeps cover
 // fp32 split-K slabs a tiling may ask for: the caller keeps one grow-only workspace per stream (api._scratch), so this bounds
 // the scratch a serving process pins per stream through tiling choices alone (+ the odd-K padding copies of its operands)
 static constexpr uint64_t kMaxSlabBytes = 256ull << 20;
-static bool tile_has_three_stages(int bm, int bn)
-{
-    for (int i = 0; i < variant_count(); ++i) {
-        int vm, vn, wm, wn, lds;
-        variant_info(i, &vm, &vn, &wm, &wn, &lds);
-        if (vm == bm && vn == bn && variant_stages(i) == 3) return true;
-    }
-    return false;
-}
-
-// one LDS stage of a tile (dga_device_common.hpp GemmCfg with 256 DMA threads)
-static uint32_t dense_stage_bytes(uint32_t bm, uint32_t bn) { return std::max(bm, 32u) * 128 + bn * 128 + ((bm + 8 + 255) / 256) * 1024; }
+static bool tile_has_three_stages(int bm, int bn) { return find_build(bm, bn, 3) != nullptr; }
 
 static double dense_cost_us(const DenseCostModel &mo, uint32_t m, uint32_t n, uint32_t k, const DenseTileCost &c, uint32_t splitk,
                             uint32_t stages, uint32_t cus, uint32_t lds_per_cu, uint32_t *splitk_eff)
@@ -430,18 +427,11 @@ static double dense_cost_us(const DenseCostModel &mo, uint32_t m, uint32_t n, ui
     const uint32_t kb = ceil_div(std::max(k, 1u), 128), per = ceil_div(kb, splitk), s = ceil_div(kb, per);
     *splitk_eff = s;
     const uint64_t tiles_m = ceil_div(m, c.bm), tiles = tiles_m * ceil_div(n, c.bn), items = tiles * s;
-    const uint64_t wpc = std::max<uint64_t>(1, std::min<uint64_t>(lds_per_cu / (stages * dense_stage_bytes(c.bm, c.bn)), 4));
+    const uint64_t wpc = std::max<uint64_t>(1, std::min<uint64_t>(lds_per_cu / (stages * fp8_stage_bytes(c.bm, c.bn)), 4));
     double rounds = std::ceil(static_cast<double>(items) / static_cast<double>(cus * wpc));
-    if (&mo == &kFastModel && c.bm == 256 && c.bn == 256 && s == 1 && tiles > cus) {   // a small last wave is cut along K (apply_tail_split)
-        const uint64_t tail = tiles % cus;
-        if (tail > 0 && tail * 4 <= cus) rounds = static_cast<double>(tiles / cus) + 0.5;
-    }
-    if (&mo == &kBf16xModel && c.bm == 128 && c.bn == 256 && s == 1 && tiles > cus) {
-        // the bf16-exact tile's last partial round in 64 x 128 quarter tiles (dga_launch.hip, kernelSerial 5): a quarter tile alone on a CU
-        // takes 0.6 of a parent tile's time, two to a CU 0.85 (scripts/bx_tail_ab.py, profiles/r05_bx_tail_ab.txt)
-        const uint64_t tail = tiles % cus;
-        if (tail > 0 && tail * 2 <= cus) rounds = static_cast<double>(tiles / cus) + (tail * 4 <= cus ? 0.62 : 0.85);
-    }
+    if (c.bm == mo.tail_bm && c.bn == mo.tail_bn && s == 1)
+        if (const PartialRound pr = partial_round(tiles, cus, mo.tail_share_den))
+            rounds = static_cast<double>(tiles / cus) + (pr.tail * 4 <= cus ? mo.tail_round_quarter : mo.tail_round_half);
     const double share = static_cast<double>(std::min<uint64_t>(wpc, (items + cus - 1) / cus));
     double t = mo.launch_us + rounds * (per * c.us_per_kblock * std::pow(share, mo.share_exponent) + mo.prologue_us);
     const double bytes = static_cast<double>(m) * k + static_cast<double>(n) * k * (m <= 256 ? static_cast<double>(tiles_m) : 1.0) +
@@ -452,27 +442,77 @@ static double dense_cost_us(const DenseCostModel &mo, uint32_t m, uint32_t n, ui
     return t;
 }
 
-void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, uint32_t expected_m,
-                   bool contiguous = false)
+// The (tile, split-K) of a dense problem by a fitted model: every tile of the model that `skip` lets through x kDenseSplits, with at
+// least four k blocks per split and slabs of at most kMaxSlabBytes; ties go to the tile with fewer idle rows.  splitk == 0: no candidate.
+struct DensePick { int bm = 0, bn = 0; uint32_t splitk = 0; double us = 1e300; };
+template <class StagesOf, class Skip>
+static DensePick dense_pick(const DenseCostModel &mo, uint32_t m, uint32_t n, uint32_t k, uint32_t cus, uint32_t lds_per_cu,
+                            StagesOf stages_of, Skip skip)
+{
+    const uint32_t kb = ceil_div(std::max(k, 1u), 128);
+    DensePick best;
+    for (int i = 0; i < mo.n_tiles; ++i) {
+        DenseTileCost c = mo.tiles[i];
+        if (skip(c.bm, c.bn)) continue;
+        if (c.bm == 32 && m > 256 && mo.tall32_us_per_kblock > 0) c.us_per_kblock = mo.tall32_us_per_kblock;
+        for (uint32_t sk : kDenseSplits) {
+            if (sk > 1 && (kb < 4 * sk || static_cast<uint64_t>(sk) * m * n * 4 > kMaxSlabBytes)) continue;
+            uint32_t s_eff = 1;
+            double us = dense_cost_us(mo, m, n, k, c, sk, stages_of(c.bm, c.bn), cus, lds_per_cu, &s_eff);
+            us *= 1.0 + 1e-3 * (c.bm > static_cast<int>(m) ? (c.bm - static_cast<int>(m)) / 16.0 : 0.0);
+            if (us < best.us) { best.bm = c.bm; best.bn = c.bn; best.splitk = s_eff; best.us = us; }
+        }
+    }
+    return best;
+}
+
+// "Double the split while the grid still fits": while twice the workgroups fit `slots`, a slice keeps min_kb k blocks and the slabs stay
+// within kMaxSlabBytes
+static uint32_t grow_split(uint32_t s, uint64_t tiles, uint64_t slots, uint32_t kb, uint32_t min_kb, uint32_t m, uint32_t n)
+{
+    while (tiles * s * 2 <= slots && kb / (2 * s) >= min_kb && static_cast<uint64_t>(2 * s) * m * n * 4 <= kMaxSlabBytes) s *= 2;
+    return s;
+}
+
+// raster: walk `swizzleOffset` tile-rows together so that the tiles an XCD runs AT THE SAME TIME (`conc`: its CUs x workgroups per CU,
+// consecutive in the raster) are a near-square patch sharing A and B panels in its L2.  (Sizing the patch by the XCD's whole share of
+// the grid instead gave 8 / 16 where the sweep finds 4: 8192^3 472 -> 440 us.)
+// (a patch of gm x (conc / gm) tiles fetches gm * BM + (conc / gm) * BN operand rows into the XCD's L2: the minimum is at
+//  gm^2 = conc * BN / BM -- square in ROWS, not in tiles.  128 x 256 tiles, one per CU: gm 4 -> 8 takes 29 MB off the 170 MB
+//  configs[2] moves per launch at the same time, profiles/r05_raster_traffic.txt; 8 XCDs x (1024 + 1024) rows x K is the floor)
+static uint32_t raster_group(uint32_t conc, uint32_t bm, uint32_t bn, uint32_t tiles_m)
+{
+    uint32_t gm = 1;
+    while (static_cast<uint64_t>(gm * 2) * (gm * 2) * bm <= static_cast<uint64_t>(conc) * bn && gm * 2 <= tiles_m) gm *= 2;
+    return gm;
+}
+
+// the selectors' environment switches, each read once per process
+struct Switches {
+    bool no_fill_bump = env_int("DGA_NO_FILL_BUMP", 0) != 0;   // the model's own split on decode rows (A/B)
+    bool no_wsk_pick = env_int("DGA_NO_WSK_PICK", 0) != 0;     // the tile kernels instead of the workgroup split-K (A/B scripts)
+    bool no_dsk_pick = env_int("DGA_NO_DSK_PICK", 0) != 0;     // ... instead of the bf16-exact one-launch decode split-K
+};
+static const Switches &env() { static const Switches s; return s; }
+
+// ---- the fast selector's rules, in the order select_mi355x applies them -----------------------------------------------------------
+// (accumulators: JudgeSpace's L0C test on VGPRs)
+static bool fits(const MenuEntry &e, const dga_platform_t &pf) { return static_cast<uint64_t>(e.lds) <= pf.l1Size && 4ull * e.bm * e.bn <= pf.l0CSize; }
+
+// The tile of a grouped layout by rounds of the chip x cycles of one tile (tile_cycles_per_kblock), over the first build of every tile
+// size (later entries of a size are alternative builds -- waves / stages -- named by fast_name_build).  A dense problem never gets
+// here: whenever a tile of the menu fits, so does 16 x 128, which the fitted model always prices.
+static bool fast_cycle_pick(const dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, bool contiguous, MenuEntry &pick)
 {
     // Grouped masked-M: the tile height covers m_max (the rows allocated per group), not expected_m.  masked_m[g] may
     // exceed the hint, and every extra tile row of a group streams that group's whole B again, while rows beyond
     // masked_m cost nothing but skipped waves: at G = 256 x (128, 7168, 2048) with 0..32 rows per group the 128-row tile
     // streams 5.7 TB/s where a 16-row tile (the hint's choice) reaches 2.8 (scripts/grouped_decode_perf.py).
-    (void)expected_m;
-    const uint32_t m_eff = t.m;
     const uint32_t kb = ceil_div(std::max(t.k, 1u), 128);
     double best = 1e300;
-    MenuEntry pick{};
     bool found = false;
-    std::vector<MenuEntry> seen;
     for (const MenuEntry &e : menu()) {
-        bool dup = false;
-        for (const MenuEntry &q : seen) dup |= (q.bm == e.bm && q.bn == e.bn);
-        if (dup) continue;  // later entries of a tile size are alternative builds (waves / stages), chosen below
-        seen.push_back(e);
-        if (static_cast<uint64_t>(e.lds) > pf.l1Size) continue;
-        if (4ull * e.bm * e.bn > pf.l0CSize) continue;  // accumulators: JudgeSpace's L0C test on VGPRs
+        if (&e != find_build(e.bm, e.bn) || !fits(e, pf)) continue;
         // contiguous-grouped layout: a tile must not straddle two group segments (aligned to 128 rows)
         // Long groups (>= 512 rows on average) take the 256x256 tile all the same: it runs a second pass on the tiles
         // that straddle two groups (about every second group boundary) and still wins by 15-25 % (scripts/contig_ab.py).
@@ -480,7 +520,7 @@ void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, u
             // (... where its raster fills the CUs' rounds: 4 groups x 1024 rows x (2048, 4096) is 128 such tiles -- half the CUs --
             //  and takes 49 us against the 128 x 256 tile's 38; x (5120, 5120), 320 tiles = 1.25 rounds, 129 against 112;
             //  scripts/grouped_selector_regret.py)
-            const uint64_t tiles256 = static_cast<uint64_t>(ceil_div(t.m, 256)) * ceil_div(t.n, 256);
+            const uint64_t tiles256 = raster_tiles(1, t.m, t.n, 256, 256);
             const double fill256 = static_cast<double>(tiles256) / (std::ceil(static_cast<double>(tiles256) / pf.coreNum) * pf.coreNum);
             const bool tall = t.m / std::max(1u, t.groups) >= 512 && t.n >= 256 && fill256 >= 0.8;
             if (tall ? !(e.bm == 2 * DGA_CONTIGUOUS_M_ALIGNMENT && e.bn == 256)
@@ -489,45 +529,26 @@ void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, u
         }
         // M fits one tile row (decode / grouped shapes): B is the whole stream, so never cut M (every extra tile row
         // re-reads B) -- take the smallest tile height that covers M and let N tiles and split-K supply parallelism
-        if (m_eff <= 128 && e.bm != static_cast<int>(std::max(16u, round_up(m_eff, m_eff <= 16 ? 16 : m_eff <= 32 ? 32 : m_eff <= 64 ? 64 : 128))))
+        if (t.m <= 128 && e.bm != static_cast<int>(std::max(16u, round_up(t.m, t.m <= 16 ? 16 : t.m <= 32 ? 32 : t.m <= 64 ? 64 : 128))))
             continue;
         const uint32_t wg_per_cu = std::max<uint64_t>(1, std::min<uint64_t>(pf.l1Size / e.lds, 2048 / (e.wm * e.wn * 64)));
-        const uint64_t tiles = static_cast<uint64_t>(groups) * ceil_div(m_eff, e.bm) * ceil_div(t.n, e.bn);
+        const uint64_t n_tiles = raster_tiles(groups, t.m, t.n, e.bm, e.bn);
         const uint64_t slots = static_cast<uint64_t>(pf.coreNum) * wg_per_cu;
-        double rounds = std::ceil(static_cast<double>(tiles) / slots);
-        // 256x256: a small last partial wave is cut along K (apply_tail_split) and costs a fraction of a round
-        if (groups == 1 && !contiguous && e.bm == 256 && e.bn == 256 && tiles > pf.coreNum) {
-            const uint64_t tail = tiles % pf.coreNum;
-            if (tail > 0 && tail * 4 <= pf.coreNum) rounds = static_cast<double>(tiles / pf.coreNum) + 0.5;
-        }
+        const double rounds = std::ceil(static_cast<double>(n_tiles) / slots);
         // co-resident workgroups share the CU's MFMA pipes
-        const double share = std::min<double>(wg_per_cu, std::ceil(static_cast<double>(tiles) / pf.coreNum));
+        const double share = std::min<double>(wg_per_cu, std::ceil(static_cast<double>(n_tiles) / pf.coreNum));
         double cost = rounds * share * kb * tile_cycles_per_kblock(e);
         // wasted rows of a partially filled tile are paid in full
-        cost *= 1.0 + 1e-3 * (e.bm > m_eff ? (e.bm - m_eff) / 16.0 : 0.0);
+        cost *= 1.0 + 1e-3 * (e.bm > t.m ? (e.bm - t.m) / 16.0 : 0.0);
         if (cost < best) { best = cost; pick = e; found = true; }
     }
-    uint32_t dense_splitk = 0;   // > 0: (tile, split-K) chosen together by the fitted cost model
-    if (groups == 1 && !contiguous) {
-        double best_us = 1e300;
-        for (const MenuEntry &e : seen) {
-            if (static_cast<uint64_t>(e.lds) > pf.l1Size || 4ull * e.bm * e.bn > pf.l0CSize) continue;
-            const DenseTileCost *c = nullptr;
-            for (const DenseTileCost &q : kDenseTileCost)
-                if (q.bm == e.bm && q.bn == e.bn) c = &q;
-            if (!c) continue;
-            if (c->bn == 256 && c->bm <= 32 && t.m > 256) continue;   // never the best of a tall problem (1 shape of 381), and their warm builds differ
-            for (uint32_t sk : kDenseSplits) {
-                if (sk > 1 && (kb < 4 * sk || static_cast<uint64_t>(sk) * t.m * t.n * 4 > kMaxSlabBytes)) continue;  // >= 4 k blocks per split, slabs <= 256 MiB
-                uint32_t s_eff = 1;
-                double us = dense_cost_us(kFastModel, t.m, t.n, t.k, *c, sk, tile_has_three_stages(c->bm, c->bn) ? 3 : 2, pf.coreNum,
-                                          static_cast<uint32_t>(pf.l1Size), &s_eff);
-                us *= 1.0 + 1e-3 * (e.bm > static_cast<int>(t.m) ? (e.bm - static_cast<int>(t.m)) / 16.0 : 0.0);   // ties: the tile with fewer idle rows
-                if (us < best_us) { best_us = us; pick = e; dense_splitk = s_eff; found = true; }
-            }
-        }
-    }
-    if (!found) { t.m1 = t.n1 = 0; return; }
+    return found;
+}
+
+// The build of the picked tile: stage count, wave grid, schedule.
+static void fast_name_build(dga_tiling_t &t, MenuEntry &pick, uint32_t groups, bool contiguous)
+{
+    const bool dense = groups == 1 && !contiguous;
     t.m1 = static_cast<uint16_t>(pick.bm); t.n1 = static_cast<uint16_t>(pick.bn); t.k1 = 128;
     t.wavesM = static_cast<uint8_t>(pick.wm); t.wavesN = static_cast<uint8_t>(pick.wn);
     t.stages = 2;
@@ -542,18 +563,17 @@ void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, u
         t.stages = 3;
     // dense: the same sweep has the three-stage build (with its loader waves where it has them) ahead on every tile, cold by
     // 13-32 % and warm by 3-26 % (except the 256-wide short tiles on warm operands, which tall problems do not get)
-    if (dense_splitk && tile_has_three_stages(pick.bm, pick.bn)) t.stages = 3;
+    if (dense && tile_has_three_stages(pick.bm, pick.bn)) t.stages = 3;
     // The masked grouped stream on short tiles (at most 64 rows a group), off the tuned table: the three-stage build -- with its
     // loader waves in the persistent form where the tile has them (16 / 64 x 128: prefer_loader_waves below) -- instead of the
-    // two-stage plain loop this function used to leave them with: 64 groups x 16 rows x (3072, 8192) 291 -> 260 us, x (1536, 4096)
+    // two-stage plain loop: 64 groups x 16 rows x (3072, 8192) 291 -> 260 us, x (1536, 4096)
     // 99 -> 85, 16 x 64 x (1536, 4096) 29 -> 20-22 (every legal build timed on 12 unseen grouped problems:
     // scripts/grouped_selector_regret.py -> profiles/r04_grouped_selector_regret.txt).  A 16-row group takes the 128-wide tile (the
     // one with loader waves: 272 against the 256-wide tile's 300-315 us at 64 x 16 x (5120, 5120)); the 32-row tiles have no such
     // build and are level at two and three stages: left alone.
     if (groups > 1 && !contiguous && pick.bm <= 64 && pick.bm != 32) {
-        if (pick.bm == 16 && pick.bn == 256)
-            for (const MenuEntry &e : seen)
-                if (e.bm == 16 && e.bn == 128) { pick = e; t.n1 = 128; t.wavesM = static_cast<uint8_t>(e.wm); t.wavesN = static_cast<uint8_t>(e.wn); t.ldsBytes = e.lds; }
+        const MenuEntry *narrow = (pick.bm == 16 && pick.bn == 256) ? find_build(16, 128) : nullptr;
+        if (narrow) { pick = *narrow; t.n1 = 128; t.wavesM = static_cast<uint8_t>(pick.wm); t.wavesN = static_cast<uint8_t>(pick.wn); t.ldsBytes = pick.lds; }
         if (tile_has_three_stages(pick.bm, pick.bn)) t.stages = 3;
     }
     // 128x256 with three stages has two builds: 4 waves (2x2) and 8 waves (2x4, two per SIMD).  The masked grouped
@@ -564,15 +584,21 @@ void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, u
     if (pick.bm == 128 && pick.bn == 256 && t.stages == 3 && !weight_stream) { t.wavesM = 2; t.wavesN = 4; }
     // ... and on the weight stream the 4-wave build takes four extra loader waves (dispatchPolicyTag 4): the refill leaves
     // the computing waves' instruction streams, -2 % time on 256 x (128, 7168, 2048) (profiles/r02_grouped_ablation.txt)
-    // (the weight stream keeps 2x2 computing waves; prefer_loader_waves() below adds the loader waves to every 3-stage pick)
-    const uint32_t tiles_m = ceil_div(t.m, t.m1), tiles_n = ceil_div(t.n, t.n1);
-    const uint64_t blocks = static_cast<uint64_t>(groups) * tiles_m * tiles_n;
+    // (the weight stream keeps 2x2 computing waves; prefer_loader_waves() adds the loader waves to every 3-stage pick)
+}
+
+// The launch form of the named build: Small / Common, split-K (splitk: the fitted model's factor on a dense problem, else 1), the
+// quarter-tile tail.
+static void fast_name_schedule(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, bool contiguous, uint32_t splitk)
+{
+    const bool dense = groups == 1 && !contiguous;
+    const uint32_t kb = ceil_div(std::max(t.k, 1u), 128);
+    const uint64_t blocks = raster_tiles(groups, t.m, t.n, t.m1, t.n1);
     t.blockDim = static_cast<uint32_t>(blocks) * ((contiguous && t.m1 > DGA_CONTIGUOUS_M_ALIGNMENT) ? 2 : 1);
     t.paddingTagA = t.paddingTagB = t.paddingTagC = DGA_PADDING_NONE;
     // variant menu in the reference's order: Small (one tile per core, single K step) -> Stream-K -> Common.
-    // Stream-K handler (select_kernel.cpp:303-331, CDNA4 reading): when the tiles fill less than half of the CUs and K
-    // is long, K is cut so that every CU streams a share of the operands; the fp32 partial tiles are combined by a
-    // second kernel.  Worth it only while the partial slabs stay small next to the operand stream.
+    // Stream-K handler (select_kernel.cpp:303-331, CDNA4 reading): K is cut so that every CU streams a share of the operands; the
+    // fp32 partial tiles are combined by a second kernel.
     t.kernelSerial = (blocks <= pf.coreNum && t.k <= t.k1) ? DGA_KERNEL_SMALL : DGA_KERNEL_COMMON;
     // Decode rows whose raster fills at most half of the CUs with the split the model chose: the model's form misses the 100-128
     // tile range (N ~ 12-16 K at 128 columns a tile), where it sees no reason to split and a split of 2 is 15-20 % faster cold
@@ -580,40 +606,22 @@ void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, u
     // still fits the CUs once and a slice keeps >= 16 k blocks -- on 30 unseen (N, K) x 3 row counts it changes 12 picks, all
     // for the better (0.75-0.89 of the time, profiles/r04_sweep_decode3/fill_bump_ab.txt); with 8 k blocks a slice (K = 2048) the
     // same doubling costs 2-10 %.  $DGA_NO_FILL_BUMP = 1: the model's own split (A/B).
-    static const bool no_bump = [] { const char *e = std::getenv("DGA_NO_FILL_BUMP"); return e && std::atoi(e) != 0; }();
-    if (!no_bump && dense_splitk >= 1 && groups == 1 && !contiguous && t.m <= 128) {
-        while (blocks * dense_splitk * 2 <= pf.coreNum && kb / (2 * dense_splitk) >= 16 &&
-               static_cast<uint64_t>(2 * dense_splitk) * t.m * t.n * 4 <= kMaxSlabBytes)
-            dense_splitk *= 2;
-    }
-    if (dense_splitk > 1) {
-        t.splitkFactor = static_cast<uint16_t>(dense_splitk);
+    if (!env().no_fill_bump && dense && t.m <= 128) splitk = grow_split(splitk, blocks, pf.coreNum, kb, 16, t.m, t.n);
+    if (splitk > 1) {
+        t.splitkFactor = static_cast<uint16_t>(splitk);
         t.kernelSerial = DGA_KERNEL_STREAMK;
         t.blockDim = static_cast<uint32_t>(blocks) * t.splitkFactor;
-    } else if (!dense_splitk && groups == 1 && !contiguous && blocks * 4 <= pf.coreNum * 3 && kb >= 8) {
-        uint32_t s = std::min<uint32_t>({pf.coreNum * 2 / static_cast<uint32_t>(blocks), kb / 4, 32u});
-        const uint64_t operand_bytes = static_cast<uint64_t>(t.m + t.n) * t.k;
-        while (s > 1 && static_cast<uint64_t>(s) * t.m * t.n * 8 * 2 > operand_bytes) --s;  // slab write + read <= half the operand read
-        if (s > 1) {
-            const uint32_t per = ceil_div(kb, s);
-            t.splitkFactor = static_cast<uint16_t>(ceil_div(kb, per));
-            t.kernelSerial = DGA_KERNEL_STREAMK;
-            t.blockDim = static_cast<uint32_t>(blocks) * t.splitkFactor;
-        }
     }
-    if (groups == 1 && !contiguous) apply_tail_split(t, pf.coreNum);
-    // raster: walk `swizzleOffset` tile-rows together so that the tiles an XCD runs AT THE SAME TIME (its CUs x
-    // workgroups per CU, consecutive in the raster) are a near-square patch sharing A and B panels in its L2.  (Sizing
-    // the patch by the XCD's whole share of the grid instead gave 8 / 16 where the sweep finds 4: 8192^3 472 -> 440 us.)
+    if (dense) apply_tail_split(t, pf.coreNum);
+}
+
+static void fast_raster(dga_tiling_t &t, const dga_platform_t &pf, const MenuEntry &pick, bool contiguous)
+{
     const uint32_t lds_pick = static_cast<uint32_t>(pick.lds) / 2 * t.stages;
     const uint32_t wpc = std::max<uint32_t>(1, std::min<uint32_t>(pf.l1Size / std::max(1u, lds_pick), 2048 / (pick.wm * pick.wn * 64)));
     const uint32_t per_xcd = std::max<uint32_t>(1, static_cast<uint32_t>(static_cast<uint64_t>(t.blockDim) / std::max(1u, pf.xcdNum)));
     const uint32_t conc = std::min<uint32_t>(per_xcd, pf.coreNum / std::max(1u, pf.xcdNum) * wpc);
-    // (a patch of gm x (conc / gm) tiles fetches gm * BM + (conc / gm) * BN operand rows into the XCD's L2: the minimum is at
-    //  gm^2 = conc * BN / BM -- square in ROWS, not in tiles.  128 x 256 tiles, one per CU: gm 4 -> 8 takes 29 MB off the 170 MB
-    //  configs[2] moves per launch at the same time, profiles/r05_raster_traffic.txt; 8 XCDs x (1024 + 1024) rows x K is the floor)
-    uint32_t gm = 1;
-    while (static_cast<uint64_t>(gm * 2) * (gm * 2) * t.m1 <= static_cast<uint64_t>(conc) * t.n1 && gm * 2 <= tiles_m) gm *= 2;
+    uint32_t gm = raster_group(conc, t.m1, t.n1, ceil_div(t.m, t.m1));
     // contiguous-grouped layout: tile rows of different groups share no B panel, so a band should not be taller than a
     // group (one 128-row block per group: walk along N, the group's tiles then share its A panel and stream its B once:
     // 933 -> 826 us at 256 groups x 128 rows; scripts/contig_stream.py)
@@ -622,40 +630,70 @@ void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, u
         while (gm > 1 && gm > rows_per_group) gm /= 2;
     }
     t.swizzleOffset = static_cast<uint8_t>(std::min<uint32_t>(gm, 255));
+}
+
+// Decode rows (M <= 16) on a weight matrix of up to 10240 rows with 2048 <= K <= 18432: the one-launch workgroup split-K on
+// per-wave LDS-DMA rings (kernelSerial 6, stages 3 names that build; csrc/gemm_fp8_wsk_kernel.hpp).  Cold, it was the fastest
+// kernel on 64 of the 68 such shapes of the decode grids, by 3-34 % (profiles/r04_sweep_wskd/table.txt): no combine launch, no
+// slab.  Wider matrices need three or more passes per workgroup (each re-streams the A rows), shorter K leaves the eight waves
+// a k block or two each, more rows double the A share of every stage: the tile kernels keep those.
+// $DGA_NO_WSK_PICK = 1 keeps the tile kernels (A/B scripts).
+// (wider matrices, up to 32768 rows with K >= 4096, take its continuous-ring build: 3-7 % ahead on 16384 / 18432 x 7168 and
+//  28672 x 4096, profiles/r04_sweep_wskd/table_wide.txt)
+// (round 4's fourth decode grid, eight more (N, K) of common models: ahead too at K = 18944 -- 148 k blocks, 3584 x 18944 0.85-0.90
+//  of the best tile plan up to 8 rows -- and on 37888 x 3584 (0.89-0.95); level on 53248 x 16384; behind once a slice is very
+//  long on a narrow matrix, 5120 x 27648 1.03-1.34: profiles/r04_sweep_decode4/)
+static void fast_decode_workgroup_split(dga_tiling_t &t, const dga_platform_t &pf)
+{
+    const uint32_t kb = ceil_div(std::max(t.k, 1u), 128);
+    if (env().no_wsk_pick || t.m > 16 || (t.k % 16) != 0 || kb < 16 || kb > 160 || !(t.n <= 10240 || (t.n <= 65536 && kb >= 24))) return;
+    t.kernelSerial = DGA_KERNEL_SPLITK_WORKGROUP;
+    t.m1 = 16; t.n1 = 128; t.k1 = 128;
+    t.splitkFactor = 1; t.stages = 3; t.wavesM = 1; t.wavesN = 4; t.dispatchPolicyTag = DGA_POLICY_PLAIN; t.swizzleOffset = 1;
+    t.blockDim = std::min<uint32_t>(ceil_div(t.n, 16), pf.coreNum);
+    t.ldsBytes = menu_lds_bytes(t);   // (of the 16 x 128 tile a shape the kernel does not take falls back to: what a cache file gives back)
+}
+
+// Very deep K on a raster of at most 64 tiles of 256 x 256 (a quarter of the CUs): Stream-K in ONE launch (kernelSerial 7,
+// gemm_fp8_streamk_kernel.hpp) -- every tile cut into 4..16 k ranges, partials added in k order inside the launch -- instead of the
+// split-K pair with its fp32 slabs and combine launch: 256 x 4096 x 32768 69.6 -> 54.7 us, 512 x 7168 x 32768 153.9 -> 141.8,
+// 768 x 4096 x 32768 108.6 -> 105.5, 1024 x 4096 x 32768 131.1 -> 125.4; at K = 16384 / 18432 it is between -8 and +8 % and keeps
+// the pair (profiles/r05_streamk_class_sweep.txt).  The reference's rule for its Stream-K: select_kernel.cpp:303-331 (k > 3072
+// and a raster that leaves cores idle).
+static void fast_deep_k_streamk(dga_tiling_t &t, const dga_platform_t &pf)
+{
+    if (t.k < 32768 || (t.k % 128) != 0 || (t.m % 256) != 0 || (t.n % 256) != 0 || static_cast<uint64_t>(t.m / 256) * (t.n / 256) > 64) return;
+    t.m1 = 256; t.n1 = 256; t.k1 = 128; t.wavesM = 4; t.wavesN = 2; t.stages = 2; t.splitkFactor = 1;
+    t.dispatchPolicyTag = DGA_POLICY_CONTINUOUS; t.kernelSerial = DGA_KERNEL_STREAMK_ONE_LAUNCH;
+    t.blockDim = pf.coreNum; t.swizzleOffset = 1;
+    t.ldsBytes = menu_lds_bytes(t);
+}
+
+// groups: of the masked grouped layout (the contiguous layout has one A / out matrix: 1)
+void select_mi355x(dga_tiling_t &t, const dga_platform_t &pf, uint32_t groups, bool contiguous = false)
+{
+    const bool dense = groups == 1 && !contiguous;
+    MenuEntry pick{};
+    uint32_t splitk = 1;
+    bool found = false;
+    if (dense) {   // (tile, split-K) chosen together by the fitted cost model
+        // (the 256-wide short tiles: never the best of a tall problem -- 1 shape of 381 -- and their warm builds differ)
+        auto skip = [&](int bm, int bn) { return !find_build(bm, bn) || !fits(*find_build(bm, bn), pf) || (bn == 256 && bm <= 32 && t.m > 256); };
+        const DensePick dp = dense_pick(kFastModel, t.m, t.n, t.k, pf.coreNum, static_cast<uint32_t>(pf.l1Size),
+                                        [](int bm, int bn) { return tile_has_three_stages(bm, bn) ? 3u : 2u; }, skip);
+        if (dp.splitk) { pick = *find_build(dp.bm, dp.bn); splitk = dp.splitk; found = true; }
+    } else {
+        found = fast_cycle_pick(t, pf, groups, contiguous, pick);
+    }
+    if (!found) { t.m1 = t.n1 = 0; return; }
+    fast_name_build(t, pick, groups, contiguous);
+    fast_name_schedule(t, pf, groups, contiguous, splitk);
+    fast_raster(t, pf, pick, contiguous);
     t.ldsBytes = menu_lds_bytes(t);   // of the build that will run (stage count and wave grid are settled by now)
     prefer_loader_waves(t);
-    // Decode rows (M <= 16) on a weight matrix of up to 10240 rows with 2048 <= K <= 18432: the one-launch workgroup split-K on
-    // per-wave LDS-DMA rings (kernelSerial 6, stages 3 names that build; csrc/gemm_fp8_wsk_kernel.hpp).  Cold, it was the fastest
-    // kernel on 64 of the 68 such shapes of the decode grids, by 3-34 % (profiles/r04_sweep_wskd/table.txt): no combine launch, no
-    // slab.  Wider matrices need three or more passes per workgroup (each re-streams the A rows), shorter K leaves the eight waves
-    // a k block or two each, more rows double the A share of every stage: the tile kernels keep those.
-    // $DGA_NO_WSK_PICK = 1 keeps the tile kernels (A/B scripts).
-    static const bool no_wsk = [] { const char *e = std::getenv("DGA_NO_WSK_PICK"); return e && std::atoi(e) != 0; }();
-    // (wider matrices, up to 32768 rows with K >= 4096, take its continuous-ring build: 3-7 % ahead on 16384 / 18432 x 7168 and
-    //  28672 x 4096, profiles/r04_sweep_wskd/table_wide.txt)
-    // (round 4's fourth decode grid, eight more (N, K) of common models: ahead too at K = 18944 -- 148 k blocks, 3584 x 18944 0.85-0.90
-    //  of the best tile plan up to 8 rows -- and on 37888 x 3584 (0.89-0.95); level on 53248 x 16384; behind once a slice is very
-    //  long on a narrow matrix, 5120 x 27648 1.03-1.34: profiles/r04_sweep_decode4/)
-    if (!no_wsk && groups == 1 && !contiguous && t.m <= 16 && (t.k % 16) == 0 && kb >= 16 && kb <= 160 &&
-        (t.n <= 10240 || (t.n <= 65536 && kb >= 24))) {
-        t.kernelSerial = DGA_KERNEL_SPLITK_WORKGROUP;
-        t.m1 = 16; t.n1 = 128; t.k1 = 128;
-        t.splitkFactor = 1; t.stages = 3; t.wavesM = 1; t.wavesN = 4; t.dispatchPolicyTag = DGA_POLICY_PLAIN; t.swizzleOffset = 1;
-        t.blockDim = std::min<uint32_t>(ceil_div(t.n, 16), pf.coreNum);
-        t.ldsBytes = menu_lds_bytes(t);   // (of the 16 x 128 tile a shape the kernel does not take falls back to: what a cache file gives back)
-    }
-    // Very deep K on a raster of at most 64 tiles of 256 x 256 (a quarter of the CUs): Stream-K in ONE launch (kernelSerial 7,
-    // gemm_fp8_streamk_kernel.hpp) -- every tile cut into 4..16 k ranges, partials added in k order inside the launch -- instead of the
-    // split-K pair with its fp32 slabs and combine launch: 256 x 4096 x 32768 69.6 -> 54.7 us, 512 x 7168 x 32768 153.9 -> 141.8,
-    // 768 x 4096 x 32768 108.6 -> 105.5, 1024 x 4096 x 32768 131.1 -> 125.4; at K = 16384 / 18432 it is between -8 and +8 % and keeps
-    // the pair (profiles/r05_streamk_class_sweep.txt).  The reference's rule for its Stream-K: select_kernel.cpp:303-331 (k > 3072
-    // and a raster that leaves cores idle).
-    if (groups == 1 && !contiguous && t.k >= 32768 && (t.k % 128) == 0 && (t.m % 256) == 0 && (t.n % 256) == 0 &&
-        static_cast<uint64_t>(t.m / 256) * (t.n / 256) <= 64) {
-        t.m1 = 256; t.n1 = 256; t.k1 = 128; t.wavesM = 4; t.wavesN = 2; t.stages = 2; t.splitkFactor = 1;
-        t.dispatchPolicyTag = DGA_POLICY_CONTINUOUS; t.kernelSerial = DGA_KERNEL_STREAMK_ONE_LAUNCH;
-        t.blockDim = pf.coreNum; t.swizzleOffset = 1;
-        t.ldsBytes = menu_lds_bytes(t);
+    if (dense) {
+        fast_decode_workgroup_split(t, pf);
+        fast_deep_k_streamk(t, pf);
     }
 }
 
@@ -788,7 +826,7 @@ public:
         t.build = static_cast<uint8_t>(e.build);
         if (e.raster) t.swizzleOffset = static_cast<uint8_t>(e.raster);
         if (bucketed && t.m1 && t.n1)   // the neighbour's grid is not this problem's
-            t.blockDim = ((t.m + t.m1 - 1) / t.m1) * ((t.n + t.n1 - 1) / t.n1) * std::max<uint32_t>(1, t.splitkFactor);
+            t.blockDim = static_cast<uint32_t>(raster_tiles(1, t.m, t.n, t.m1, t.n1) * std::max<uint32_t>(1, t.splitkFactor));
         *swept = e.stages != 0;
         *timed_policy = e.has_policy;
         return true;
@@ -905,32 +943,38 @@ void complete_from_menu(dga_tiling_t &t)
 {
     if (!t.stages) t.stages = 2;
     // a row that asks for loader waves (dispatchPolicyTag 4) names the build that has them, whatever wave grid it carries
+    const int stages = t.stages == 3 ? 3 : 2;
     if (t.dispatchPolicyTag == DGA_POLICY_LOADER_WAVES || t.dispatchPolicyTag == DGA_POLICY_PERSISTENT) {
-        for (int i = 0; i < variant_count(); ++i) {
-            int bm, bn, wm, wn, lds;
-            variant_info(i, &bm, &bn, &wm, &wn, &lds);
-            if (bm != t.m1 || bn != t.n1 || variant_stages(i) != (t.stages == 3 ? 3 : 2) || !variant_has_loader_waves(i)) continue;
-            t.wavesM = static_cast<uint8_t>(wm); t.wavesN = static_cast<uint8_t>(wn);
-            t.ldsBytes = static_cast<uint32_t>(lds);
+        if (const MenuEntry *e = find_build(t.m1, t.n1, stages, true)) {
+            t.wavesM = static_cast<uint8_t>(e->wm); t.wavesN = static_cast<uint8_t>(e->wn);
+            t.ldsBytes = static_cast<uint32_t>(e->lds);
             return;
         }
         t.dispatchPolicyTag = DGA_POLICY_PLAIN;   // no such build for this tile: the plain loop
     }
     // first build of that tile size with that stage count (the launcher's own preference order), else any build of it
-    for (int pass = 0; pass < 2; ++pass)
-        for (int i = 0; i < variant_count(); ++i) {
-            int bm, bn, wm, wn, lds;
-            variant_info(i, &bm, &bn, &wm, &wn, &lds);
-            if (bm != t.m1 || bn != t.n1 || (pass == 0 && variant_stages(i) != (t.stages == 3 ? 3 : 2))) continue;
-            if (!t.wavesM) { t.wavesM = static_cast<uint8_t>(wm); t.wavesN = static_cast<uint8_t>(wn); }
-            t.ldsBytes = menu_lds_bytes(t);
-            return;
-        }
+    const MenuEntry *e = find_build(t.m1, t.n1, stages);
+    if (!e) e = find_build(t.m1, t.n1);
+    if (!e) return;
+    if (!t.wavesM) { t.wavesM = static_cast<uint8_t>(e->wm); t.wavesN = static_cast<uint8_t>(e->wn); }
+    t.ldsBytes = menu_lds_bytes(t);
+}
+
+// A reference-format file (or one written by hand) may name what this library's menu does not hold: the reference's own
+// fixture row `512,512,512,128,256,256,0,...` carries k1 = 256, its kernel type 3 (PaddingStreamK) has no build here.  The
+// kernels step one 128-wide scale block at a time whatever k1 says, so a cached row is normalised onto the menu -- as its
+// CDNA4-only fields are re-derived by the caller -- instead of coming back as a tiling that dga_tiling_check refuses
+// (csv_test.cpp:33-35 rows; tests/test_tiling.py, tests/test_tiling_check.py).
+static void normalise_cache_row(dga_tiling_t &t)
+{
+    if (t.k1 != 0 && t.k1 != 128) t.k1 = 128;
+    if (!known_kernel_serial(t.kernelSerial)) t.kernelSerial = DGA_KERNEL_COMMON;
 }
 
 }  // namespace tiling
 }  // namespace dga
 
+using namespace dga;
 using namespace dga::tiling;
 
 extern "C" {
@@ -1003,8 +1047,7 @@ int dga_select_kernel(const dga_problem_t *problem, const dga_platform_t *platfo
         if (problem->k == 0) return DGA_E_SHAPE;   // the reference's padding simulator divides by K (select_kernel.cpp:147-180)
         select_reference(*out, pf);
     } else {
-        if (out->contiguous) select_mi355x(*out, pf, 1, 0, true);  // one A/out matrix; groups counts the B matrices
-        else select_mi355x(*out, pf, out->groups, problem->expected_m);
+        select_mi355x(*out, pf, out->contiguous ? 1 : out->groups, out->contiguous != 0);  // contiguous: one A/out matrix; groups counts the B matrices
         if (!out->m1) return DGA_E_TILING;
     }
     return DGA_OK;
@@ -1016,24 +1059,12 @@ int dga_tiling(const dga_problem_t *problem, dga_tiling_t *out)
     init_params(*problem, *out);
     bool swept = false, timed_policy = false;
     if (Cache::instance().get(*out, &swept, &timed_policy)) {
-        // A reference-format file (or one written by hand) may name what this library's menu does not hold: the reference's own
-        // fixture row `512,512,512,128,256,256,0,...` carries k1 = 256, its kernel type 3 (PaddingStreamK) has no build here.  The
-        // kernels step one 128-wide scale block at a time whatever k1 says, so a cached row is normalised onto the menu -- as its
-        // CDNA4-only fields are re-derived below -- instead of coming back as a tiling that dga_tiling_check refuses
-        // (csv_test.cpp:33-35 rows; tests/test_tiling.py, tests/test_tiling_check.py).
-        if (out->k1 != 0 && out->k1 != 128) out->k1 = 128;
-        switch (out->kernelSerial) {
-            case DGA_KERNEL_COMMON: case DGA_KERNEL_SMALL: case DGA_KERNEL_PADDING_COMMON: case DGA_KERNEL_STREAMK:
-            case DGA_KERNEL_STREAMK_TAIL: case DGA_KERNEL_SPLITK_WORKGROUP: case DGA_KERNEL_STREAMK_ONE_LAUNCH: break;
-            default: out->kernelSerial = DGA_KERNEL_COMMON;
-        }
+        normalise_cache_row(*out);
         // (the power-of-two-scales flag is the caller's promise about its scales -- a fast_ue8m0 process default or policy adds it to
         //  the tiling -- never a row's: a call on general scales must not run the E8M0-operand builds)
         out->dispatchPolicyTag &= static_cast<uint8_t>(~DGA_POLICY_UE8M0_SCALES);
         if (out->contiguous)   // a bucketed key: the workgroup count follows this call's row count
-            out->blockDim = static_cast<uint32_t>(static_cast<uint64_t>((out->m + out->m1 - 1) / std::max<uint32_t>(1, out->m1)) *
-                                                  ((out->n + out->n1 - 1) / std::max<uint32_t>(1, out->n1)) *
-                                                  (out->m1 > DGA_CONTIGUOUS_M_ALIGNMENT ? 2 : 1));
+            out->blockDim = static_cast<uint32_t>(raster_tiles(1, out->m, out->n, out->m1, out->n1) * (out->m1 > DGA_CONTIGUOUS_M_ALIGNMENT ? 2 : 1));
         if (swept) {  // a swept entry is complete: the build the sweep timed (a file from before the policy column existed, or a
                       // reference-format one, is upgraded to the loader waves where the tile has such a build)
             complete_from_menu(*out);
@@ -1061,112 +1092,107 @@ int dga_tiling(const dga_problem_t *problem, dga_tiling_t *out)
     return DGA_OK;
 }
 
-// Tiling of the bf16-exact policy (dispatchPolicyTag 7).  Its menu (dga_launch_menu_e.hip) and its costs are not the fast
-// path's: one 8-wave build (128x256) and four 4-wave builds whose single wave per SIMD issues conversions and promotions at
-// about 0.6-0.75 of the rate, and a split-K combine that costs a launch.  The fast path's tuned tile mapped onto that menu
-// was 10-40 % off on mid-M shapes (512..1024 x 4096 x 7168 took the 4-wave 128x128 build; profiles/r03_bx_tile_sweep.txt), so
-// dense problems get their own pick from a small cost model fitted to that sweep: rounds x (per-workgroup time) + combine.
-// Grouped layouts keep the fast tiling's tile (its height is dictated by the layout).
-int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out)
+}  // extern "C"
+
+// ---- the bf16-exact selector's rules, in the order dga_tiling_bf16_exact applies them; a bool rule completes the answer (true) or declines
+
+// Every field a rule of this policy decides, written in one place: its builds are named by tile and `build`, with three stages and no
+// wave grid.  block_dim 0: the plain raster x split-K.
+static void set_bx_answer(dga_tiling_t &t, int bm, int bn, uint8_t serial, uint8_t build, uint32_t splitk, uint32_t raster, uint32_t block_dim = 0)
 {
-    if (!problem || !out) return DGA_E_NULL;
-    {   // The cache first, as the reference's op does on every call (select_kernel.cpp:371-378, cache.cpp:69-100): a row the sweep timed
-        // under THIS policy (dispatchPolicyTag 7 in tuned/mi355x.csv or in the caller's $DGA_CACHE_FILE_PATH; harness/sweep.py --arith
-        // bf16_exact) is what a default call runs, before any cost model
-        init_params(*problem, *out);
-        bool swept = false, timed_policy = false;
-        if (out->m && out->n && Cache::instance().get(*out, &swept, &timed_policy, /*bf16_exact_class*/ true) && out->m1 && out->n1) {
-            if (out->k1 != 0 && out->k1 != 128) out->k1 = 128;
-            if (!out->stages) out->stages = 3;
-            if (!out->splitkFactor) out->splitkFactor = 1;
-            out->wavesM = out->wavesN = 0;      // (this policy's builds are named by tile and `build`)
-            if (!out->blockDim) out->blockDim = std::max<uint32_t>(1, out->groups) * ((out->m + out->m1 - 1) / out->m1) * ((out->n + out->n1 - 1) / out->n1) * out->splitkFactor;
-            // The row's class is this policy, its tag is not the arithmetic: the power-of-two-scales flag is the caller's promise about
-            // its scales, added where the process default makes it (run_fp8 under bf16_exact_ue8m0, api._with_policy), never a row's.
-            out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
-            // A row the menu does not hold (a hand-written file: the decode build off its 64 x 128 tile, the tail pair off 128 x 256, a
-            // stage count or build no kernel has) is no answer: the rules below pick instead of the launch refusing the call.
-            if (dga_tiling_check(out) == DGA_OK) return DGA_OK;
-        }
+    t.m1 = static_cast<uint16_t>(bm); t.n1 = static_cast<uint16_t>(bn);
+    t.stages = 3; t.wavesM = t.wavesN = 0;
+    t.splitkFactor = static_cast<uint16_t>(splitk); t.kernelSerial = serial; t.build = build;
+    t.swizzleOffset = static_cast<uint8_t>(raster);
+    t.blockDim = block_dim ? block_dim : static_cast<uint32_t>(raster_tiles(t.contiguous ? 1 : std::max<uint32_t>(1, t.groups), t.m, t.n, bm, bn) * splitk);
+}
+
+// The cache first, as the reference's op does on every call (select_kernel.cpp:371-378, cache.cpp:69-100): a row the sweep timed
+// under THIS policy (dispatchPolicyTag 7 in tuned/mi355x.csv or in the caller's $DGA_CACHE_FILE_PATH; harness/sweep.py --arith
+// bf16_exact) is what a default call runs, before any cost model
+static bool bx_cache_row(const dga_problem_t &problem, dga_tiling_t &t)
+{
+    init_params(problem, t);
+    bool swept = false, timed_policy = false;
+    if (!t.m || !t.n || !Cache::instance().get(t, &swept, &timed_policy, /*bf16_exact_class*/ true) || !t.m1 || !t.n1) return false;
+    // A row the menu does not hold (a hand-written file: a kernel type without a build, the decode build off its 64 x 128 tile, the tail
+    // pair off 128 x 256, a stage count or build no kernel has) is no answer: the rules pick instead of the launch refusing the call.
+    if (!known_kernel_serial(t.kernelSerial)) return false;
+    normalise_cache_row(t);
+    if (!t.stages) t.stages = 3;
+    if (!t.splitkFactor) t.splitkFactor = 1;
+    t.wavesM = t.wavesN = 0;      // (this policy's builds are named by tile and `build`)
+    if (!t.blockDim) t.blockDim = static_cast<uint32_t>(raster_tiles(std::max<uint32_t>(1, t.groups), t.m, t.n, t.m1, t.n1) * t.splitkFactor);
+    // The row's class is this policy, its tag is not the arithmetic: the power-of-two-scales flag is the caller's promise about
+    // its scales, added where the process default makes it (run_fp8 under bf16_exact_ue8m0, api._with_policy), never a row's.
+    t.dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+    return dga_tiling_check(&t) == DGA_OK;
+}
+
+// Masked grouped layout, experts of more than 64 rows allocated: the layout's own kernel on the 128 x 256 tile (gemm_fp8_bf16x_grouped_kernel.hpp:
+// rows that do not exist are not multiplied, at 16-row granularity, and two k blocks of the weight stream are in flight) whatever
+// the hint says -- 256 x (128, 7168, 2048): random masks 865-900 -> 761-796 us, 0..16 rows 674 (617 with the hint's 32 x 128 tiles)
+// -> 522, 0..64 rows 735 -> 600, full mask level (profiles/r06_grouped_masks.txt).
+static bool bx_masked_grouped_kernel(dga_tiling_t &t)
+{
+    if (t.m <= 64 || t.k < 256 || (t.k % 16) != 0) return false;
+    set_bx_answer(t, 128, 256, DGA_KERNEL_COMMON, DGA_BUILD_BX_GROUPED, 1, 1);
+    return true;
+}
+
+// Masked grouped layout on the tile kernels (K < 256): this policy's loop multiplies every row of its tile (no per-m-tile skipping as in the
+// fast kernels), so the tile height follows the caller's hint where it says the experts are nearly empty -- rows present 0..16: 832 -> 597 us on
+// 256 x (128, 7168, 2048) with 32 x 128 tiles, 0..32: 886 -> 628, 0..64: 938 -> 734 with 64 x 256 (scripts/grouped_decode_bf16x.py,
+// profiles/r04_grouped_decode_bf16x.txt).  A hint that is too low costs time only (every further tile row of an expert streams its
+// weights again), never rows: the raster still covers m_max.
+static bool bx_masked_hint_tiles(dga_tiling_t &t, uint32_t expected_m)
+{
+    if (expected_m == 0 || expected_m > 64 || t.m <= 64 || t.k < 128 || (t.k % 16) != 0) return false;
+    const bool low = expected_m <= 32;
+    set_bx_answer(t, low ? 32 : 64, low ? 128 : 256, DGA_KERNEL_COMMON, DGA_BUILD_DEFAULT, 1, t.swizzleOffset);
+    return true;
+}
+
+// Grouped layouts (and degenerate problems) keep the fast tiling's tile: its height is dictated by the layout -- but not its wave
+// layout: 2 x 2 waves would name this policy's 4-wave IMAGE build (dga_launch.hip), 4-10 % behind the in-register build on the grouped
+// stream and without its row skipping.
+// (K % 16 != 0 on a dense problem takes the cost model like any other K: the padding pass in front of the kernel is the same for every
+//  tile -- 8 x 7168 x 18433 75.6 -> 63.2 us on the workgroup split-K, the prefill-sized odd shapes unchanged)
+static bool bx_keep_fast_tile(const dga_problem_t &problem, dga_tiling_t &t)
+{
+    if (!(std::max<uint32_t>(1, t.groups) > 1 || t.contiguous || !t.m || !t.n || t.k < 128)) return false;
+    t.wavesM = t.wavesN = 0;
+    // (a fast-class cache row whose schedule this policy's menu lacks -- written by hand -- gives way to the selector's own tile)
+    if (t.m1 && dga_tiling_check(&t) != DGA_OK && dga_select_kernel_with_predictor(&problem, &t, nullptr, nullptr) == DGA_OK) {
+        t.dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+        t.build = DGA_BUILD_DEFAULT;
+        t.wavesM = t.wavesN = 0;
     }
-    int rc = dga_tiling(problem, out);
-    if (rc != DGA_OK) return rc;
-    out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
-    // The fast tiling's build name is not this policy's (a fast sweep row of the register workgroup split-K carries build 1, or the
-    // legacy `stages` 1); the branches below that name a build set it themselves.
-    out->build = DGA_BUILD_DEFAULT;
-    // Masked grouped layout: this policy's loop multiplies every row of its tile (no per-m-tile skipping as in the fast kernels), so the
-    // tile height follows the caller's hint where it says the experts are nearly empty -- rows present 0..16: 832 -> 597 us on
-    // 256 x (128, 7168, 2048) with 32 x 128 tiles, 0..32: 886 -> 628, 0..64: 938 -> 734 with 64 x 256 (scripts/grouped_decode_bf16x.py,
-    // profiles/r04_grouped_decode_bf16x.txt).  A hint that is too low costs time only (every further tile row of an expert streams its
-    // weights again), never rows: the raster still covers m_max.
-    // Masked grouped layout, experts of more than 64 rows allocated: the layout's own kernel on the 128 x 256 tile (gemm_fp8_bf16x_grouped_kernel.hpp:
-    // rows that do not exist are not multiplied, at 16-row granularity, and two k blocks of the weight stream are in flight) whatever
-    // the hint says -- 256 x (128, 7168, 2048): random masks 865-900 -> 761-796 us, 0..16 rows 674 (617 with the hint's 32 x 128 tiles)
-    // -> 522, 0..64 rows 735 -> 600, full mask level (profiles/r06_grouped_masks.txt).
-    if (std::max<uint32_t>(1, out->groups) > 1 && !out->contiguous && out->m > 64 && out->k >= 256 && (out->k % 16) == 0) {
-        out->m1 = 128; out->n1 = 256;
-        out->stages = 3; out->wavesM = 0; out->wavesN = 0; out->splitkFactor = 1; out->kernelSerial = DGA_KERNEL_COMMON;
-        out->build = DGA_BUILD_BX_GROUPED;
-        out->swizzleOffset = 1;
-        out->blockDim = out->groups * ((out->m + out->m1 - 1) / out->m1) * ((out->n + out->n1 - 1) / out->n1);
-        return DGA_OK;
-    }
-    if (std::max<uint32_t>(1, out->groups) > 1 && !out->contiguous && problem->expected_m > 0 && problem->expected_m <= 64 && out->m > 64 &&
-        out->k >= 128 && (out->k % 16) == 0) {
-        out->m1 = problem->expected_m <= 32 ? 32 : 64;
-        out->n1 = problem->expected_m <= 32 ? 128 : 256;
-        out->stages = 3; out->wavesM = 0; out->wavesN = 0; out->splitkFactor = 1; out->kernelSerial = DGA_KERNEL_COMMON;
-        out->blockDim = out->groups * ((out->m + out->m1 - 1) / out->m1) * ((out->n + out->n1 - 1) / out->n1);
-        return DGA_OK;
-    }
-    if (std::max<uint32_t>(1, out->groups) > 1 || out->contiguous || !out->m || !out->n || out->k < 128) {
-        // (K % 16 != 0 takes the cost model below like any other K: the padding pass in front of the kernel is the same for every tile --
-        //  8 x 7168 x 18433 75.6 -> 63.2 us on the workgroup split-K, the prefill-sized odd shapes unchanged)
-        // grouped layouts keep the fast tiling's tile -- but not its wave layout: 2 x 2 waves would name this policy's 4-wave IMAGE build
-        // (dga_launch.hip), 4-10 % behind the in-register build on the grouped stream and without its row skipping
-        out->wavesM = out->wavesN = 0;
-        // (a fast-class cache row whose schedule this policy's menu lacks -- written by hand -- gives way to the selector's own tile)
-        if (out->m1 && dga_tiling_check(out) != DGA_OK && dga_select_kernel_with_predictor(problem, out, nullptr, nullptr) == DGA_OK) {
-            out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
-            out->build = DGA_BUILD_DEFAULT;
-            out->wavesM = out->wavesN = 0;
-        }
-        return DGA_OK;
-    }
-    using namespace dga::tiling;
-    const uint32_t cus = dga::device_cus(), kb = (out->k + 127) / 128;
-    double best = 1e300;
-    int bm = out->m1, bn = out->n1;
-    uint32_t sk = 1;
-    for (int i = 0; i < kBf16xModel.n_tiles; ++i) {
-        DenseTileCost c = kBf16xModel.tiles[i];
-        if (c.bm == 32 && out->m > 256) c.us_per_kblock = kBf16x32RowTallUs;
-        for (uint32_t s : kDenseSplits) {
-            if (s > 1 && (kb < 4 * s || static_cast<uint64_t>(s) * out->m * out->n * 4 > kMaxSlabBytes)) continue;
-            uint32_t s_eff = 1;
-            double us = dense_cost_us(kBf16xModel, out->m, out->n, out->k, c, s, 3, cus, 160 * 1024, &s_eff);
-            us *= 1.0 + 1e-3 * (c.bm > static_cast<int>(out->m) ? (c.bm - static_cast<int>(out->m)) / 16.0 : 0.0);
-            if (us < best) { best = us; bm = c.bm; bn = c.bn; sk = s_eff; }
-        }
-    }
+    return true;
+}
+
+// Dense problems: (tile, split-K) by this policy's own fitted model (kBf16xModel).
+static void bx_dense_pick(dga_tiling_t &t, uint32_t cus, uint32_t kb)
+{
+    const DensePick dp = dense_pick(kBf16xModel, t.m, t.n, t.k, cus, 160 * 1024, [](int, int) { return 3u; }, [](int, int) { return false; });
+    uint32_t sk = dp.splitk;
     // Short-M rows on the tiles of which two workgroups share a CU (64x128, 32x128: 75 / 63 KB of LDS): the fitted model stops splitting
     // once every CU has a workgroup, but these rows are streams and the second workgroup per CU is more bytes in flight -- cold,
     // 64 x 7168 x 18432 48.2 -> 40.1 us and 64 x 7168 x 16384 43.9 -> 36.3 with 8 splits instead of 4, 128 x 4096 x 7168 23.9 -> 22.5
     // (scripts/bf16x_decode_sweep.py).  Double the split while the grid stays within two workgroups per CU and a split keeps >= 4 k blocks.
-    if (out->m <= 128 && bn == 128 && bm <= 64 && kb >= 16) {   // (K < 2048: 64 x 24576 x 1536 is best unsplit)
-        const uint64_t tiles0 = static_cast<uint64_t>((out->m + bm - 1) / bm) * ((out->n + bn - 1) / bn);
-        while (tiles0 * sk * 2 <= 2ull * cus && kb / (2 * sk) >= 4 && static_cast<uint64_t>(2 * sk) * out->m * out->n * 4 <= kMaxSlabBytes) sk *= 2;
-    }
-    out->m1 = static_cast<uint16_t>(bm); out->n1 = static_cast<uint16_t>(bn);
-    out->splitkFactor = static_cast<uint16_t>(sk);
-    out->kernelSerial = sk > 1 ? DGA_KERNEL_STREAMK : DGA_KERNEL_COMMON;
-    out->stages = 3; out->wavesM = 0; out->wavesN = 0;
-    const uint64_t tiles = static_cast<uint64_t>((out->m + bm - 1) / bm) * ((out->n + bn - 1) / bn);
-    out->blockDim = static_cast<uint32_t>(tiles * sk);
+    if (t.m <= 128 && dp.bn == 128 && dp.bm <= 64 && kb >= 16)   // (K < 2048: 64 x 24576 x 1536 is best unsplit)
+        sk = grow_split(sk, raster_tiles(1, t.m, t.n, dp.bm, dp.bn), 2ull * cus, kb, 4, t.m, t.n);
+    set_bx_answer(t, dp.bm, dp.bn, sk > 1 ? DGA_KERNEL_STREAMK : DGA_KERNEL_COMMON, DGA_BUILD_DEFAULT, sk, t.swizzleOffset);
+}
+
+// The unsplit 128 x 256 tile with a partial last round: Stream-K in one launch, or the quarter-tile tail the cost model counted.
+static void bx_partial_round(dga_tiling_t &t, uint32_t cus, uint32_t kb)
+{
+    if (t.m1 != 128 || t.n1 != 256 || t.splitkFactor != 1) return;
+    const uint64_t tiles = raster_tiles(1, t.m, t.n, 128, 256), rem = tiles % cus;
     // (tails per spare workgroup of the cut's second form, as gemm_fp8_bf16x_streamk_kernel.hpp bx_streamk_plan computes it)
-    const uint64_t rem = tiles % cus, spare_t = (rem * 2 > cus) ? (rem + (cus - rem) - 1) / (cus - rem) : 1;
-    if (bm == 128 && bn == 256 && sk == 1 && tiles >= 2 * static_cast<uint64_t>(cus) && rem > 0 && kb >= 48 && spare_t <= 4) {
+    const uint64_t spare_t = (rem * 2 > cus) ? (rem + (cus - rem) - 1) / (cus - rem) : 1;
+    if (tiles >= 2 * static_cast<uint64_t>(cus) && rem > 0 && kb >= 48 && spare_t <= 4) {
         // Rasters of at least two rounds with a partial last one: Stream-K in one launch (kernelSerial 7, gemm_fp8_bf16x_streamk_kernel.hpp)
         // -- the whole rounds as the persistent kernel runs them, the last round cut along K.  3511 x 6151 x 8191 (2.73 rounds) 380 ->
         // 368 us, 1024 x 18432 x 7168 (2.25 rounds) 233 (the launch pair below) -> 227; below two rounds the cut does not pay: at 1.125
@@ -1176,70 +1202,93 @@ int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out)
         // 4096 / 5120 the cut LOSES 10 / 8 / 3 % (4096 x 7168 x 2048, 6016 x 4096 x 4096, 5120^3: profiles/r06_bx_regret.txt) -- from
         // K = 6144 on, and with at most four tails per spare workgroup.  The reference's rule: more blocks than cores with a remainder
         // below 0.8 of the cores and k > 3072 (op_host/op_tiling/select_kernel.cpp:303-331).
-        out->kernelSerial = DGA_KERNEL_STREAMK_ONE_LAUNCH;
-        out->blockDim = cus;
-    } else
-    if (bm == 128 && bn == 256 && sk == 1 && tiles > cus && tiles % cus > 0 && (tiles % cus) * 2 <= cus) {
-        // the cost above counted the last partial round in quarter tiles: name that launch pair (1024 x 18432 x 7168, 2.25 rounds:
+        t.kernelSerial = DGA_KERNEL_STREAMK_ONE_LAUNCH;
+        t.blockDim = cus;
+    } else if (const PartialRound pr = partial_round(tiles, cus, kBf16xModel.tail_share_den)) {
+        // the cost model counted the last partial round in quarter tiles: name that launch pair (1024 x 18432 x 7168, 2.25 rounds:
         // 276 -> 241 us; 2304 x 4096 x 7168, 1.125 rounds, 168 on 128 x 128 tiles -> 139; same bytes as the single launch)
-        out->kernelSerial = DGA_KERNEL_STREAMK_TAIL;
-        out->blockDim = static_cast<uint32_t>(tiles - tiles % cus + 4 * (tiles % cus));
+        t.kernelSerial = DGA_KERNEL_STREAMK_TAIL;
+        t.blockDim = static_cast<uint32_t>(pr.launch_tiles());
     }
-    {   // raster group: the XCD's concurrent patch square in operand ROWS (see select_mi355x); 4096^3 on 128 x 256 tiles:
-        // 202 -> 169 MB of fabric traffic per launch at the same time (profiles/r05_raster_traffic.txt)
-        const uint32_t tiles_m = (out->m + bm - 1) / bm;
-        const uint32_t wpc = (bm * bn <= 64 * 128) ? 2 : 1;
-        const uint32_t conc = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(1, tiles / 8), static_cast<uint64_t>(cus / 8) * wpc));
-        uint32_t gm = 1;
-        while (static_cast<uint64_t>(gm * 2) * (gm * 2) * bm <= static_cast<uint64_t>(conc) * bn && gm * 2 <= tiles_m) gm *= 2;
-        out->swizzleOffset = static_cast<uint8_t>(gm);
-    }
-    // 17..512 rows on a matrix that gives at most one 64 x 128 tile per CU: the one-launch split-K of that tile (kernelSerial 6 with build
-    // DGA_BUILD_BX_DECODE, gemm_fp8_bf16x_dsk_kernel.hpp: two k groups per workgroup, splitkFactor workgroups per tile meeting in the
-    // workspace, no combine launch), S = min(8, CUs / tiles, k blocks / 4), 6 where that is 8.  Timed as decode rows are (SURVEY 8(d):
-    // operand sets rotated past the Infinity Cache) against EVERY other candidate of this policy's menu, 61 shapes
-    // (scripts/r06_bx_regret.py, profiles/r06_decode_cold_table.txt): 0.76-0.98 of the best other candidate inside the rule below --
-    // 128 x 4096 x 7168 21.6 -> 19.0 us, 128 x 7168 x 2048 16.5 -> 13.1, 256 x 7168 x 2048 19.6 -> 14.8, 192 x 2112 x 7168 21.0 -> 16.7,
-    // 64 x 16384 x 7168 36.8 -> 30.7, 64 x 4096 x 7168 17.3 -> 16.8 -- and behind it outside: fewer than 24 tiles (64 x 2112 x 7168 +3 %:
-    // the ~4 us hand-over between workgroups is not bought back), K below 1536, short K on few tiles (64 x 4096 x 2048 +4 %), more than
-    // 30 k blocks per k group (128 x 7168 x 18432 +4 %; 16 above 128 rows: 256 x 5120 x 5120 +7 %).  Warm (the weights in the Infinity
-    // Cache, profiles/r06_decode_grid.txt) the 49..64-row picks are level to 10 % behind the tile kernels; decode weights are not warm.
-    // 257..512 rows (timed warm, nine shapes): 0.86-1.01 of the best other candidate (320 x 2112 x 7168 22.0 -> 18.8 us, 512 x 2048 x 7168 26.4 -> 24.0).
-    static const bool no_dsk = [] { const char *e = std::getenv("DGA_NO_DSK_PICK"); return e && std::atoi(e) != 0; }();
-    // (17..32 rows: where the matrix is too tall for the per-wave split-K below -- 32 x 24576 x 1536 15.9 -> 13.0 us, 24 x 12288 x 5120
-    //  21.8 -> 20.1; on matrices of at most 8192 rows that kernel stays 7-30 % ahead)
-    //  (... and where K is long: 24 x 4096 x 18432 26.6 -> 23.4, 32 x 7168 x 18432 33.2 -> 31.5)
-    if (!no_dsk && (out->k % 16) == 0 && kb >= 12 && out->m <= 512 && (out->m >= 33 || (out->m >= 17 && (out->n > 8192 || kb >= 96)))) {
-        const uint64_t dt = static_cast<uint64_t>((out->m + 63) / 64) * ((out->n + 127) / 128);
-        if (dt >= 24 && dt <= cus && !(kb < 32 && dt < 48)) {
-            const uint32_t smax = static_cast<uint32_t>(std::min<uint64_t>(std::min<uint64_t>(8, cus / dt), kb / 4));
-            // (a grid on fewer than 3/4 of the CUs with long k groups: 64 x 18432 x 7168, 144 workgroups of 28 k blocks per group, is 5 %
-            //  behind the tile kernel's 432 workgroups, 48 x 18432 x 7168 10 %)
-            const bool thin = dt * smax * 4 < 3ull * cus && kb > 32u * smax;
-            if (smax >= 1 && !thin && kb <= (out->m > 128 ? 32u : 60u) * smax) {
-                // (eight workgroups per tile on every CU: six measured 2-4 % ahead -- 64 x 4096 x 7168 17.1 / 17.6 us, 64 x 4096 x 4096
-                //  14.0 / 14.7; on a grid that leaves CUs free eight stay ahead -- 48 x 3072 x 18432 23.1 / 25.4)
-                const uint32_t s = (smax == 8 && dt * 8 > 7ull * cus / 8) ? 6 : smax;
-                out->kernelSerial = DGA_KERNEL_SPLITK_WORKGROUP;
-                out->build = DGA_BUILD_BX_DECODE;
-                out->m1 = 64; out->n1 = 128;
-                out->splitkFactor = static_cast<uint16_t>(s); out->stages = 3; out->swizzleOffset = 1;
-                out->blockDim = static_cast<uint32_t>(dt * s);
-                return DGA_OK;
-            }
-        }
-    }
-    // Decode rows: the workgroup split-K on LDS-DMA rings runs this policy's arithmetic too (gemm_fp8_wskd_kernel<..., MATH = 1>), and
-    // since the stream pays for neither the conversions nor the bf16 matrix rate it takes the fast policy's time: cold, 20-44 % ahead
-    // of this policy's tile kernels on 103 of 120 decode shapes (profiles/r04_wskd_cold_bf16x.txt) -- up to 16 rows wherever a wave
-    // gets at least one k block and the matrix has at most 65536 rows, up to 32 rows on matrices of at most 8192.
-    static const bool no_wsk = [] { const char *e = std::getenv("DGA_NO_WSK_PICK"); return e && std::atoi(e) != 0; }();
-    if (!no_wsk && ((out->m <= 16 && kb >= 8 && out->n <= 65536) || (out->m <= 32 && kb >= 12 && out->n <= 8192))) {
-        out->kernelSerial = DGA_KERNEL_SPLITK_WORKGROUP;
-        out->m1 = out->m <= 16 ? 16 : 32; out->n1 = 128;
-        out->splitkFactor = 1; out->stages = 3; out->swizzleOffset = 1;
-        out->blockDim = std::min<uint32_t>((out->n + 15) / 16, cus);
-    }
+}
+
+// raster group: the XCD's concurrent patch square in operand ROWS (raster_group); 4096^3 on 128 x 256 tiles:
+// 202 -> 169 MB of fabric traffic per launch at the same time (profiles/r05_raster_traffic.txt)
+static void bx_raster(dga_tiling_t &t, uint32_t cus)
+{
+    const uint64_t tiles = raster_tiles(1, t.m, t.n, t.m1, t.n1);
+    const uint32_t wpc = (t.m1 * t.n1 <= 64 * 128) ? 2 : 1;
+    const uint32_t conc = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(1, tiles / 8), static_cast<uint64_t>(cus / 8) * wpc));
+    t.swizzleOffset = static_cast<uint8_t>(raster_group(conc, t.m1, t.n1, ceil_div(t.m, t.m1)));
+}
+
+// 17..512 rows on a matrix that gives at most one 64 x 128 tile per CU: the one-launch split-K of that tile (kernelSerial 6 with build
+// DGA_BUILD_BX_DECODE, gemm_fp8_bf16x_dsk_kernel.hpp: two k groups per workgroup, splitkFactor workgroups per tile meeting in the
+// workspace, no combine launch), S = min(8, CUs / tiles, k blocks / 4) (bx_dsk_splits), 6 where that is 8.  Timed as decode rows are (SURVEY 8(d):
+// operand sets rotated past the Infinity Cache) against EVERY other candidate of this policy's menu, 61 shapes
+// (scripts/r06_bx_regret.py, profiles/r06_decode_cold_table.txt): 0.76-0.98 of the best other candidate inside the rule below --
+// 128 x 4096 x 7168 21.6 -> 19.0 us, 128 x 7168 x 2048 16.5 -> 13.1, 256 x 7168 x 2048 19.6 -> 14.8, 192 x 2112 x 7168 21.0 -> 16.7,
+// 64 x 16384 x 7168 36.8 -> 30.7, 64 x 4096 x 7168 17.3 -> 16.8 -- and behind it outside: fewer than 24 tiles (64 x 2112 x 7168 +3 %:
+// the ~4 us hand-over between workgroups is not bought back), K below 1536, short K on few tiles (64 x 4096 x 2048 +4 %), more than
+// 30 k blocks per k group (128 x 7168 x 18432 +4 %; 16 above 128 rows: 256 x 5120 x 5120 +7 %).  Warm (the weights in the Infinity
+// Cache, profiles/r06_decode_grid.txt) the 49..64-row picks are level to 10 % behind the tile kernels; decode weights are not warm.
+// 257..512 rows (timed warm, nine shapes): 0.86-1.01 of the best other candidate (320 x 2112 x 7168 22.0 -> 18.8 us, 512 x 2048 x 7168 26.4 -> 24.0).
+// (17..32 rows: where the matrix is too tall for the per-wave split-K below -- 32 x 24576 x 1536 15.9 -> 13.0 us, 24 x 12288 x 5120
+//  21.8 -> 20.1; on matrices of at most 8192 rows that kernel stays 7-30 % ahead)
+//  (... and where K is long: 24 x 4096 x 18432 26.6 -> 23.4, 32 x 7168 x 18432 33.2 -> 31.5)
+static bool bx_decode_one_launch(dga_tiling_t &t, uint32_t cus, uint32_t kb)
+{
+    if (env().no_dsk_pick || (t.k % 16) != 0 || kb < 12 || t.m > 512 || !(t.m >= 33 || (t.m >= 17 && (t.n > 8192 || kb >= 96)))) return false;
+    const uint64_t dt = raster_tiles(1, t.m, t.n, DskTile::BM, DskTile::BN);
+    if (dt < 24 || dt > cus || (kb < 32 && dt < 48)) return false;
+    const uint32_t smax = static_cast<uint32_t>(bx_dsk_splits(static_cast<int64_t>(dt), static_cast<int>(kb), DskTile::MAX_S, static_cast<int>(cus)));
+    // (a grid on fewer than 3/4 of the CUs with long k groups: 64 x 18432 x 7168, 144 workgroups of 28 k blocks per group, is 5 %
+    //  behind the tile kernel's 432 workgroups, 48 x 18432 x 7168 10 %)
+    const bool thin = dt * smax * 4 < 3ull * cus && kb > 32u * smax;
+    if (smax < 1 || thin || kb > (t.m > 128 ? 32u : 60u) * smax) return false;
+    // (eight workgroups per tile on every CU: six measured 2-4 % ahead -- 64 x 4096 x 7168 17.1 / 17.6 us, 64 x 4096 x 4096
+    //  14.0 / 14.7; on a grid that leaves CUs free eight stay ahead -- 48 x 3072 x 18432 23.1 / 25.4)
+    const uint32_t s = (smax == 8 && dt * 8 > 7ull * cus / 8) ? 6 : smax;
+    set_bx_answer(t, DskTile::BM, DskTile::BN, DGA_KERNEL_SPLITK_WORKGROUP, DGA_BUILD_BX_DECODE, s, 1);
+    return true;
+}
+
+// Decode rows: the workgroup split-K on LDS-DMA rings runs this policy's arithmetic too (gemm_fp8_wskd_kernel<..., MATH = 1>), and
+// since the stream pays for neither the conversions nor the bf16 matrix rate it takes the fast policy's time: cold, 20-44 % ahead
+// of this policy's tile kernels on 103 of 120 decode shapes (profiles/r04_wskd_cold_bf16x.txt) -- up to 16 rows wherever a wave
+// gets at least one k block and the matrix has at most 65536 rows, up to 32 rows on matrices of at most 8192.
+static void bx_decode_workgroup_split(dga_tiling_t &t, uint32_t cus, uint32_t kb)
+{
+    if (env().no_wsk_pick || !((t.m <= 16 && kb >= 8 && t.n <= 65536) || (t.m <= 32 && kb >= 12 && t.n <= 8192))) return;
+    set_bx_answer(t, t.m <= 16 ? 16 : 32, 128, DGA_KERNEL_SPLITK_WORKGROUP, DGA_BUILD_DEFAULT, 1, 1, std::min<uint32_t>(ceil_div(t.n, 16), cus));
+}
+
+// Tiling of the bf16-exact policy (dispatchPolicyTag 7).  Its menu (dga_launch_menu_e.hip) and its costs are not the fast
+// path's: one 8-wave build (128x256) and four 4-wave builds whose single wave per SIMD issues conversions and promotions at
+// about 0.6-0.75 of the rate, and a split-K combine that costs a launch.  The fast path's tuned tile mapped onto that menu
+// was 10-40 % off on mid-M shapes (512..1024 x 4096 x 7168 took the 4-wave 128x128 build; profiles/r03_bx_tile_sweep.txt), so
+// dense problems get their own pick from a small cost model fitted to that sweep: rounds x (per-workgroup time) + combine.
+// The decode rules run after the dense pick and overwrite it.
+extern "C" {
+
+int dga_tiling_bf16_exact(const dga_problem_t *problem, dga_tiling_t *out)
+{
+    if (!problem || !out) return DGA_E_NULL;
+    if (bx_cache_row(*problem, *out)) return DGA_OK;
+    if (int rc = dga_tiling(problem, out)) return rc;
+    out->dispatchPolicyTag = DGA_POLICY_BF16_EXACT;
+    // The fast tiling's build name is not this policy's (a fast sweep row of the register workgroup split-K carries build 1, or the
+    // legacy `stages` 1); the rules below that name a build set it themselves.
+    out->build = DGA_BUILD_DEFAULT;
+    const bool masked = std::max<uint32_t>(1, out->groups) > 1 && !out->contiguous;
+    if (masked && (bx_masked_grouped_kernel(*out) || bx_masked_hint_tiles(*out, problem->expected_m))) return DGA_OK;
+    if (bx_keep_fast_tile(*problem, *out)) return DGA_OK;
+    const uint32_t cus = dga::device_cus(), kb = (out->k + 127) / 128;
+    bx_dense_pick(*out, cus, kb);
+    bx_partial_round(*out, cus, kb);
+    bx_raster(*out, cus);
+    if (bx_decode_one_launch(*out, cus, kb)) return DGA_OK;
+    bx_decode_workgroup_split(*out, cus, kb);
     return DGA_OK;
 }
 
@@ -1286,7 +1335,7 @@ int dga_tiling_k_grouped_wgrad(const dga_problem_t *problem, dga_tiling_t *out)
     out->k1 = 128; out->stages = 3; out->splitkFactor = 1; out->kernelSerial = DGA_KERNEL_COMMON;
     out->dispatchPolicyTag = policy == 2 ? DGA_POLICY_STRICT : DGA_POLICY_BF16_EXACT;
     const uint64_t groups = out->groups, cus = dga::device_cus();
-    auto tiles = [&](uint32_t bm, uint32_t bn) { return groups * ((out->m + bm - 1) / bm) * ((out->n + bn - 1) / bn); };
+    auto tiles = [&](uint32_t bm, uint32_t bn) { return raster_tiles(groups, out->m, out->n, bm, bn); };
     // the persistent 128 x 256 build where the raster fills the CUs and every group has a tile for each of the eight XCDs (its list
     // gives XCD x chunk x of every group: with fewer tiles per group some XCDs would idle); otherwise the tallest, then widest one-tile
     // build whose raster fills the CUs, or the smallest tile
@@ -1318,14 +1367,11 @@ size_t dga_workspace_bytes(const dga_tiling_t *tiling)
         add(groups * tiling->n * kp);
     }
     if (tiling->splitkFactor > 1) add(static_cast<size_t>(tiling->splitkFactor) * tiling->m * tiling->n * 4);
-    // Stream-K proper: one fp32 partial tile (256 x 256) per CU + the flags
-    // (one slot per CU: 256 x 256 floats on the fast path, 128 x 256 under the bf16-exact policy; + the flags)
-    if (tiling->kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH) add(static_cast<size_t>(dga::device_cus()) * (256 * 256 * 4 + 8) + 256);
-    // the decode build of the workgroup split-K: one fp32 partial tile (64 x 128) per tile and split but the first + the flags
-    if (tiling->build == DGA_BUILD_BX_DECODE && tiling->splitkFactor > 1) {
-        const size_t tiles = (static_cast<size_t>(tiling->m) + 63) / 64 * ((static_cast<size_t>(tiling->n) + 127) / 128);
-        add(tiles * (tiling->splitkFactor - 1) * (64 * 128 * 4 + 8) + 256);
-    }
+    // Stream-K proper: the fast path's slots (256 x 256 floats) bound the bf16-exact policy's (128 x 256) too
+    if (tiling->kernelSerial == DGA_KERNEL_STREAMK_ONE_LAUNCH) add(streamk_workspace_bytes(dga::device_cus()));
+    // the decode build of the workgroup split-K
+    if (tiling->build == DGA_BUILD_BX_DECODE && tiling->splitkFactor > 1)
+        add(bx_dsk_workspace_bytes(static_cast<int64_t>(raster_tiles(1, tiling->m, tiling->n, DskTile::BM, DskTile::BN)), tiling->splitkFactor));
     return bytes ? bytes + 256 : 0;
 }
 

@@ -26,20 +26,20 @@
 // fused reduce of its Stream-K kernel (op_kernel/kernel/padding_streamk_matmul_kernel.h:92-107) and the Small handler that serves
 // these shapes there (op_host/op_tiling/select_kernel.cpp:270-291).
 #pragma once
+#include "dga_fp8_plan.hpp"              // DskTile
 #include "gemm_fp8_kernel.hpp"
 #include "gemm_fp8_streamk_kernel.hpp"   // StreamKArgs
 
 namespace dga {
 
 struct DskCfg {
-    static constexpr int BM = 64, BN = 128, GT = 256, NT = 512, TN = 2;
+    static constexpr int BM = DskTile::BM, BN = DskTile::BN, GT = 256, NT = 512, TN = 2;
     static constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, SC_BYTES = GT * 4;
     static constexpr int STAGE_BYTES = A_BYTES + B_BYTES + SC_BYTES, RING_BYTES = 3 * STAGE_BYTES, LDS_BYTES = 2 * RING_BYTES;
     // the A-image build: two stages + the bf16 image of one k block's A tile (m-tile, chain step, lane: 16 bytes each) per k group
     static constexpr int IMG_BYTES = BM * 128 * 2, IMG_GROUP_BYTES = 2 * STAGE_BYTES + IMG_BYTES, IMG_LDS_BYTES = 2 * IMG_GROUP_BYTES;
     static constexpr int A_ITERS = 2, B_ITERS = 4, NL = A_ITERS + B_ITERS + 1;
-    static constexpr int SLOT_FLOATS = BM * BN;     // one workgroup's partial tile
-    static constexpr int MAX_S = 8;
+    static constexpr int SLOT_FLOATS = DskTile::SLOT_FLOATS, MAX_S = DskTile::MAX_S;
 };
 
 // IMG: the A tile of a k block is converted ONCE per k group -- wave w its m-tile w, into a bf16 image in LDS behind a second barrier --
