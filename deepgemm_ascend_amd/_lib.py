@@ -154,6 +154,8 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_silu_mul_cast_to_fp8_1x128_transposed": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                                   c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dga_silu_mul_bwd_cast_to_fp8_1x128_transposed": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                      c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dga_cast_to_fp8_128x128_transposed": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                            c_void_p]),
     "dga_adamw_cast_to_fp8_128x128_transposed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_float,

@@ -1098,7 +1098,8 @@ def silu_and_mul_backward_per_token_cast_to_fp8(x: torch.Tensor, grad_h: torch.T
     unquantised gradient in the same pass (fp32 rounded to nearest even for the 16-bit types) on the valid rows -- what
     per_token_cast_to_fp8_transposed (same mask) turns into the operand of k_grouped_wgrad_gemm_fp8_fp8_fp32_nt.  For gate >= 20 the result is the quantiser's
     on [fl32(grad_h * up) | fl32(grad_h * gate)] bit for bit; for |gate| <= 16 dup is within relative 2^-18 and dgate within
-    2^-17 |grad_h up| (s + |gate| s (1 - s)) of the real-number value."""
+    2^-17 |grad_h up| (s + |gate| s (1 - s)) of the real-number value.
+    silu_and_mul_backward_per_token_cast_to_fp8_transposed(rowwise=True) returns this (dq, dsf) and the dW1 operand from one read, without grad_x_out."""
     h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 256)
     _want(grad_h, "grad_h", None, lead + (h,))
     _require(grad_h.dtype == x.dtype, "grad_h must have x's dtype")
@@ -1185,6 +1186,37 @@ def silu_and_mul_per_token_cast_to_fp8_transposed(x: torch.Tensor, masked_m: Opt
     h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 2)
     return _cast_transposed("dga_silu_mul_cast_to_fp8_1x128_transposed", "silu_and_mul_per_token_cast_to_fp8_transposed", x, h, lead,
                             groups, rows, masked_m, m_indices, rowwise, aligned_rows, use_ue8m0, out, sync)
+
+
+def silu_and_mul_backward_per_token_cast_to_fp8_transposed(x: torch.Tensor, grad_h: torch.Tensor, masked_m: Optional[torch.Tensor] = None,
+                                                           m_indices: Optional[torch.Tensor] = None, rowwise: bool = False,
+                                                           aligned_rows: bool = False, use_ue8m0: bool = False, out=None,
+                                                           sync: bool = False):
+    """The operand of the weight gradient of an expert MLP's first GEMM, dW1[g] = dY1_g^T . x_g with dY1 = [dgate | dup] the backward of
+    silu(x[..., :H]) * x[..., H:], from (x, grad_h) in one pass (dga_silu_mul_bwd_cast_to_fp8_1x128_transposed):
+    per_token_cast_to_fp8_transposed of dY1, with dY1 kept in fp32 registers and never written.  x [..., 2H] and grad_h [..., H] are
+    silu_and_mul_backward_per_token_cast_to_fp8's inputs (one dtype of float32 / bfloat16 / float16, H % 128 == 0, its three row
+    layouts) -> qt [2H, T] float8_e4m3fn, sft [2H, ceil(T/128)] float32, T the number of rows over all groups: channels 0 .. H-1 are
+    dgate^T, H .. 2H-1 dup^T, the operand k_grouped_wgrad_gemm_fp8_fp8_fp32_nt and wgrad_gemm_fp8_fp8_fp32_nt take as it is.
+    The contract is by composition: with G the float32 grad_x_out that silu_and_mul_backward_per_token_cast_to_fp8 writes for
+    (x.float(), grad_h.float()) under the same mask,
+      (qt, sft) = per_token_cast_to_fp8_transposed(G, same mask, aligned_rows, use_ue8m0)
+    byte for byte and bit for bit, for every dtype and every input (NaN, infinities, gate <= -88.8): the gradient that is quantised was
+    never rounded to 16 bits, and its accuracy is that entry's.  The output has per_token_cast_to_fp8_transposed's meaning: a row a mask
+    excludes is not read and counts as zeros (code 0, a 128-token block without a valid token has scale 1), and EVERY element of qt and
+    sft is written.  rowwise=True also returns (dq, dsf) = silu_and_mul_backward_per_token_cast_to_fp8(x, grad_h, same mask, use_ue8m0),
+    bit for bit, from the same read on the valid rows (the rows a mask excludes are not written), and the result is
+    ((qt, sft), (dq, dsf)): the backward gets the lhs of its dgrad and the operand of dW1 in one pass.  There is no grad_x_out: a caller
+    who wants the 16-bit gradient uses silu_and_mul_backward_per_token_cast_to_fp8.  aligned_rows, out=, use_ue8m0, sync: as
+    per_token_cast_to_fp8_transposed."""
+    h, lead, groups, rows = _fused_layout(x, masked_m, m_indices, 256)
+    _want(grad_h, "grad_h", None, lead + (h,))
+    _require(grad_h.dtype == x.dtype, "grad_h must have x's dtype")
+    call = lambda fn, *outputs: fn(x.data_ptr(), grad_h.data_ptr(), _CAST_DT[x.dtype], groups, rows, h, _ptr(masked_m), _ptr(m_indices),
+                                   *outputs)
+    return _cast_transposed("dga_silu_mul_bwd_cast_to_fp8_1x128_transposed", "silu_and_mul_backward_per_token_cast_to_fp8_transposed", x,
+                            2 * h, lead, groups, rows, masked_m, m_indices, rowwise, aligned_rows, use_ue8m0, out, sync, call=call,
+                            also=(grad_h,))
 
 
 def gather_per_token_cast_to_fp8_transposed(src: torch.Tensor, index: torch.Tensor, index_div: int = 1,

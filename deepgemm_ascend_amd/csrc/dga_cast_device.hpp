@@ -1,8 +1,8 @@
 // What the fp8 quantisers share (dga_cast.hip, dga_cast_transposed.hip, dga_cast_transposed_block.hip, dga_adamw_cast.hip, dga_gather_cast_transposed.hip, dga_silu_mul_cast.hip,
-// dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip, dga_rms_norm.hip; dga_combine.hip takes the element types' loads and stores).
+// dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast.hip, dga_silu_mul_bwd_cast_transposed.hip, dga_rms_norm.hip; dga_combine.hip takes the element types' loads and stores).
 // Device: the e4m3fn conversion, the 16-lane DPP row max, the block scale and the 8-element quotient recurrence of the 1x128 / 128x128 definition
 // (oracle/: quant_1x128); the bounded 8-element loads and stores of the three types (Elem, load8_bounded, Store8, store1, store8_bounded, store_codes8); the fused kernels'
-// row locator, refined sigmoid and silu(g) * u with its fp64-rounded block amax; the transposing kernels' row masks and the gathering one's
+// row locator, refined sigmoid, silu(g) * u and its backward, each with its fp64-rounded block amax; the transposing kernels' row masks and the gathering one's
 // table reads.  Host, at the end:
 // the dtype dispatcher, the grid of 16-lane blocks and the fused entries' argument checks.  One text, so that every quantiser gives the same bytes.
 #pragma once
@@ -326,7 +326,39 @@ __device__ __forceinline__ float silu_mul_abs_rounded(float g, float u, float h3
     return one ? h32 : __builtin_fabsf(hd);
 }
 
-// ---- the transposing quantisers (dga_cast_transposed.hip, dga_silu_mul_cast_transposed.hip): 256 lanes on 128 tokens x 128 channels
+// dgate = (d u) silu'(g) and dup = d (g s), s the refined sigmoid and e = exp(-g) (sigmoid_refined: s = 0 for e = inf).  t = e s is 1 - s;
+// e = inf gives inf * 0 = NaN there, dropped by v_min_f32 in favour of the 1 that 1 - s tends to (e s <= 1 in real numbers, so the min
+// changes nothing else).  A NaN g still gives NaN: s is NaN.
+__device__ __forceinline__ void silu_mul_bwd(float g, float u, float d, float &dgate, float &dup)
+{
+    float e;
+    const float s = sigmoid_refined(g, e);
+    const float t = __builtin_fminf(e * s, 1.f);
+    const float gs = g * s;
+    dgate = (d * u) * __builtin_fmaf(gs, t, s);
+    dup = d * gs;
+}
+
+// The lane's largest |dgate| and |dup| once more, as the fp32 nearest to the real-number value (silu_mul_abs_rounded's reasons: the
+// block scale is amax / 448).  Where the fp32 factor is exactly 1 the value stays the fp32 product: the contract for gate >= 20.  An
+// element whose fp32 value is 0 never is a lane's maximum, so g > -88.8 here and exp(-g) is finite in fp64.
+__device__ __forceinline__ float dgate_abs_rounded(float g, float u, float d, float v32)
+{
+    const float e = exp_neg(g);
+    const bool one = 1.f + e == 1.f && __builtin_fmaf(g, e, 1.f) == 1.f;
+    const double gd = g, ed = exp(-gd), sd = 1.0 / (1.0 + ed);
+    const float vd = (float)((double)d * (double)u * (sd * (1.0 + gd * (ed * sd))));
+    return one ? v32 : __builtin_fabsf(vd);
+}
+__device__ __forceinline__ float dup_abs_rounded(float g, float d, float v32)
+{
+    const bool one = 1.f + exp_neg(g) == 1.f;
+    const double gd = g;
+    const float vd = (float)((double)d * (gd / (1.0 + exp(-gd))));
+    return one ? v32 : __builtin_fabsf(vd);
+}
+
+// ---- the transposing quantisers (dga_cast_transposed.hip, dga_silu_mul_cast_transposed.hip, dga_silu_mul_bwd_cast_transposed.hip): 256 lanes on 128 tokens x 128 channels
 
 // locate_row's predicate for the 8 consecutive rows r0 .. r0 + 7 of t_n > 0 (counted over all groups of mmax rows): ok[p] = the row exists
 // and the mask does not exclude it.  No branch between the 8 reads of the mask, so they go out together: a row beyond the last asks about

@@ -27,38 +27,7 @@
 
 namespace dga {
 
-// dgate = (d u) silu'(g) and dup = d (g s), s the refined sigmoid and e = exp(-g) (sigmoid_refined: s = 0 for e = inf).  t = e s is 1 - s;
-// e = inf gives inf * 0 = NaN there, dropped by v_min_f32 in favour of the 1 that 1 - s tends to (e s <= 1 in real numbers, so the min
-// changes nothing else).  A NaN g still gives NaN: s is NaN.
-__device__ __forceinline__ void silu_mul_bwd(float g, float u, float d, float &dgate, float &dup)
-{
-    float e;
-    const float s = sigmoid_refined(g, e);
-    const float t = __builtin_fminf(e * s, 1.f);
-    const float gs = g * s;
-    dgate = (d * u) * __builtin_fmaf(gs, t, s);
-    dup = d * gs;
-}
-
-// The lane's largest |dgate| and |dup| once more, as the fp32 nearest to the real-number value (silu_mul_abs_rounded's reasons: the
-// block scale is amax / 448).  Where the fp32 factor is exactly 1 the value stays the fp32 product: the contract for gate >= 20.  An
-// element whose fp32 value is 0 never is a lane's maximum, so g > -88.8 here and exp(-g) is finite in fp64.
-__device__ __forceinline__ float dgate_abs_rounded(float g, float u, float d, float v32)
-{
-    const float e = exp_neg(g);
-    const bool one = 1.f + e == 1.f && __builtin_fmaf(g, e, 1.f) == 1.f;
-    const double gd = g, ed = exp(-gd), sd = 1.0 / (1.0 + ed);
-    const float vd = (float)((double)d * (double)u * (sd * (1.0 + gd * (ed * sd))));
-    return one ? v32 : __builtin_fabsf(vd);
-}
-__device__ __forceinline__ float dup_abs_rounded(float g, float d, float v32)
-{
-    const bool one = 1.f + exp_neg(g) == 1.f;
-    const double gd = g;
-    const float vd = (float)((double)d * (gd / (1.0 + exp(-gd))));
-    return one ? v32 : __builtin_fabsf(vd);
-}
-
+// (silu_mul_bwd, dgate_abs_rounded and dup_abs_rounded live in dga_cast_device.hpp: dga_silu_mul_bwd_cast_transposed.hip shares them)
 // silu_mul_cast_1x128_kernel's geometry: 16 lanes share column block b of a row, 8 consecutive elements per lane of gate, up and grad
 // (for bf16 three 16-byte loads), and own the two output blocks b (dgate) and hb_n + b (dup) of that row: two DPP row maxima, two
 // scales, two 8-byte code stores, no LDS.  `blocks` = rows_total * hb_n 16-lane groups; a group whose row the mask excludes leaves

@@ -544,6 +544,29 @@ int dga_silu_mul_cast_to_fp8_1x128_transposed(const void *x, int x_dtype, int64_
                                               void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
                                               int flags, void *stream);
 
+/* The same quantiser on the backward of that activation -- the operand of the weight gradient of an expert MLP's first GEMM,
+ * dW1[g] = dY1_g^T . x_g with dY1 = [dgate | dup], from the tensors dga_silu_mul_bwd_cast_to_fp8_1x128 reads, in one pass and without dY1
+ * ever leaving fp32 registers:
+ *   (qt, sft) = cast_to_fp8_1x128_ex( where(valid, [dgate | dup], 0)^T ),
+ * x [groups, rows, 2h] and grad_h [groups, rows, h] contiguous of `dtype`, h % 128 == 0, T = groups * rows, qt [2h, T] e4m3fn bytes in rows
+ * ldqt bytes apart (dgate^T in the first h rows, dup^T in the last h), T <= ldqt <= round_up(T, 128), zeros from byte T to the end of each
+ * row, sft [2h, ceil(T/128)] fp32.  The contract is by composition: with G the fp32 grad_x that dga_silu_mul_bwd_cast_to_fp8_1x128 writes
+ * for the fp32 up-conversion of (x, grad_h) under the same mask, (qt, sft) are dga_cast_to_fp8_1x128_transposed's on G byte for byte and
+ * bit for bit, for every `dtype` and on every input (NaN, infinities and gate <= -88.8 included); the gradients have that entry's accuracy.
+ * The amax of a 128-token block is the plain fp32 maximum of those gradients (no NaN enters), not an fp64 re-evaluation.  masked_m,
+ * m_indices: as in dga_cast_to_fp8_1x128_transposed -- a row they exclude is not read and counts as zeros (code 0x00; a 128-token block
+ * without a valid row has scale 1), and every byte of qt and every scale of sft is written.  q_row, sf_row (both NULL or both set):
+ * (q_row [T, 2h], sf_row [T, 2h/128]) are dga_silu_mul_bwd_cast_to_fp8_1x128's (dq, dsf) on (x, grad_h) as given, bit for bit, from the
+ * same read, on the valid rows; the rows a mask excludes are not written there.  There is no grad_x: not writing it is the point.
+ * flags: DGA_CAST_UE8M0.  Checks, in dga_cast_to_fp8_1x128_transposed's order: DGA_E_RANGE: an unknown flag;  DGA_E_SHAPE: a negative
+ * size, h % 128 != 0, groups < 1, both masks, m_indices with groups != 1, ldqt outside its range, exactly one of q_row / sf_row;  T == 0
+ * or h == 0 is DGA_OK with nothing touched;  then DGA_E_NULL (x, grad_h, qt, sft), DGA_E_DTYPE, and DGA_E_RANGE for more tile halves
+ * (2 per 128 tokens x 128 channels of h) than one grid holds. */
+int dga_silu_mul_bwd_cast_to_fp8_1x128_transposed(const void *x, const void *grad_h, int dtype, int64_t groups, int64_t rows, int64_t h,
+                                                  const int32_t *masked_m, const int32_t *m_indices,
+                                                  void *qt, int64_t ldqt, float *sft, void *q_row, float *sf_row,
+                                                  int flags, void *stream);
+
 /* The 128x128 quantiser of grouped expert weights and of their transposes, in one pass -- the rhs of fprop (W) and of dgrad (W^T) from
  * the master weights, with no loop over the experts, no transposing copy and no stacking:
  *   (qt[g], sft[g]) = cast_to_fp8_128x128_ex( w[g]^T ),   byte for byte and bit for bit, for every group g,
