@@ -1795,6 +1795,48 @@ def clip_grad_norm_step_scalars(tensors, step_scalars: torch.Tensor, max_norm: f
     return GradClipNorm(*_clip_run(sumsq, step_scalars, mx, ps, e, outs, False), sumsq)
 
 
+MQA_LOGITS_HEAD_DIM, MQA_LOGITS_HEADS = 128, (32, 64)
+MQA_LOGITS_BLOCK_M, MQA_LOGITS_BLOCK_N = 64, 256   # the kernel's token run and key block (DGA_MQA_LOGITS_BLOCK_*)
+
+
+def fp8_mqa_logits(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weights: torch.Tensor, cu_seq_len_k_start: torch.Tensor,
+                   cu_seq_len_k_end: torch.Tensor, out: Optional[torch.Tensor] = None, sync: bool = False) -> torch.Tensor:
+    """The scoring kernel of the lightning indexer of DeepSeek sparse attention, upstream DeepGEMM's fp8_mqa_logits (dga_fp8_mqa_logits):
+    logits[m, n] = kscale[n] * sum_h weights[m, h] * relu(sum_d q[m, h, d] k[n, d]) for clamp(ks[m]) <= n < clamp(ke[m]), -inf elsewhere.
+    q [M, H, 128] float8_e4m3fn (or uint8 bytes) without a scale -- the caller folds it into weights, as upstream --, kv = (k [N, 128] fp8,
+    kscale float32 [N]), weights float32 [M, H], cu_seq_len_k_start / cu_seq_len_k_end int32 [M] device tensors, all contiguous;
+    H 32 or 64, any M >= 0, any N >= 1.  Returns float32 [M, N] (out= takes the caller's; it needs no pre-fill: every element is written,
+    in-range values and -inf).  The ranges are read and clamped to [0, N] on the device, so a captured graph follows new ones; ke <= ks is a
+    row of -inf.  The dot products are four chained bf16 matrix instructions on exactly converted codes with fp32 accumulation, the ReLU
+    keeps a NaN, the head sum has one order that H fixes and kscale multiplies once after it: two runs give the same bits, and
+    |logits - exact| <= (2^-22 + (H + 3) 2^-24) kscale[n] sum_h |weights| sum_d |q k| on every in-range element.  A NaN code in q poisons
+    its row, one in k its column, inside the ranges only.  A token whose range misses a block of 256 keys costs that block nothing but the
+    -inf stores, so a causal prefill costs about half the dense work.  M == 0 returns without a launch."""
+    _require(isinstance(kv, (tuple, list)) and len(kv) == 2, "kv must be (k, kscale)")
+    k, kscale = kv
+    _require(q.dim() == 3, "q must be [M, H, %d]", MQA_LOGITS_HEAD_DIM)
+    m, h, d = q.shape
+    _require(d == MQA_LOGITS_HEAD_DIM, "q must be [M, H, %d]: head dimension %d is not supported", MQA_LOGITS_HEAD_DIM, d)
+    _require(h in MQA_LOGITS_HEADS, "q must have 32 or 64 heads, got %d", h)
+    _want(_fp8_bytes(q), "q", None, (m, h, d))
+    _require(k.dim() == 2 and k.shape[0] >= 1, "k must be [N, %d] with N >= 1", d)
+    n = k.shape[0]
+    _want(_fp8_bytes(k), "k", None, (n, d))
+    _want(kscale, "kscale", torch.float32, (n,))
+    _want(weights, "weights", torch.float32, (m, h))
+    _want(cu_seq_len_k_start, "cu_seq_len_k_start", torch.int32, (m,))
+    _want(cu_seq_len_k_end, "cu_seq_len_k_end", torch.int32, (m,))
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=q.device)
+    else:
+        _want(out, "out", torch.float32, (m, n))
+    # (M == 0: the C entry returns before any launch)
+    _launch("fp8_mqa_logits", (q, k, kscale, weights, cu_seq_len_k_start, cu_seq_len_k_end, out), lambda L, stream: L.dga_fp8_mqa_logits(
+        q.data_ptr(), k.data_ptr(), kscale.data_ptr(), weights.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(),
+        m, n, h, d, out.data_ptr(), stream), sync)
+    return out
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

@@ -875,6 +875,33 @@ int dga_rms_norm_backward(const void *grad_y, const void *z, int dtype, const vo
                           int64_t workspace_bytes, void *stream);
 int64_t dga_rms_norm_backward_workspace_bytes(int64_t rows, int64_t h);
 
+/* The scoring kernel of the lightning indexer of DeepSeek sparse attention, upstream DeepGEMM's fp8_mqa_logits (csrc/dga_mqa_logits.hip):
+ *   s[m,h,n]     = sum_d q[m,h,d] k[n,d]                                          e4m3 codes, d < head_dim = 128
+ *   logits[m,n]  = kscale[n] * sum_h weights[m,h] * max(s[m,h,n], 0)               for lo[m] <= n < hi[m]
+ *                = -inf                                                            elsewhere
+ * q [m, heads, 128] and k [n, 128] contiguous e4m3fn codes (q carries no scale: the caller folds it into weights, as upstream), kscale
+ * fp32 [n], weights fp32 [m, heads], ks and ke int32 [m] on the device, logits fp32 [m, n] contiguous.  lo = min(max(ks, 0), n) and hi
+ * likewise of ke are formed on the device, so a captured graph follows new ranges; hi <= lo is a row of -inf.  Every element of logits is
+ * written on every call, by exactly one lane and without atomics: two runs give the same bits, and logits needs no pre-fill.
+ * Arithmetic (the default policy's): the codes go to bf16 exactly, s is four chained v_mfma_f32_16x16x32_bf16 over d ascending in fp32,
+ * the ReLU is s < 0 ? 0 : s on that fp32 value (a NaN stays one), each product weights * relu(s) enters an fp32 fused multiply-add chain,
+ * the head sum runs in an order heads alone fixes ("Sparse-attention indexer"), kscale multiplies once after it.  Against the exact value, on every
+ * element inside its range:
+ *   |logits - exact| <= (2^-22 + (heads + 3) 2^-24) kscale[n] sum_h |weights[m,h]| sum_d |q[m,h,d] k[n,d]|.
+ * A NaN code (0x7F, 0xFF) in q[m,h,:] makes every in-range element of row m NaN, one in k[n,:] every in-range element of column n;
+ * elements outside the ranges are -inf whatever the operands hold.  A (token, block of DGA_MQA_LOGITS_BLOCK_N keys) pair whose keys lie
+ * wholly outside the token's range is neither loaded nor multiplied.  No row of k or kscale at or beyond n and no row of q, weights, ks
+ * or ke at or beyond m is read.  One launch, nothing read back (capturable).
+ * DGA_E_SHAPE: m < 0, n < 1, head_dim != 128, heads other than 32 or 64;  m == 0 is DGA_OK with nothing launched;  then DGA_E_NULL (any
+ * pointer), DGA_E_ALIGN (q or k not 8-byte, weights not 16-byte, kscale or logits not 4-byte aligned), and DGA_E_RANGE for
+ * n > DGA_MQA_LOGITS_MAX_N or more (token run, key block) pairs than one grid holds (2^31 - 1). */
+#define DGA_MQA_LOGITS_HEAD_DIM 128
+#define DGA_MQA_LOGITS_BLOCK_N 256        /* keys of one workgroup */
+#define DGA_MQA_LOGITS_BLOCK_M 64         /* consecutive tokens one workgroup walks */
+#define DGA_MQA_LOGITS_MAX_N 0x7FFFFF00
+int dga_fp8_mqa_logits(const void *q, const void *k, const float *kscale, const float *weights, const int32_t *ks, const int32_t *ke,
+                       int64_t m, int64_t n, int heads, int head_dim, float *logits, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
