@@ -1837,6 +1837,97 @@ def fp8_mqa_logits(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weigh
     return out
 
 
+PAGED_MQA_LOGITS_BLOCK_KV, PAGED_MQA_LOGITS_BLOCK_BYTES = 64, 8448   # keys of a cache block; its bytes: 64 * 128 codes + 64 fp32 scales
+PAGED_MQA_LOGITS_CHUNK_N = 512                                       # columns of one workgroup (DGA_PAGED_MQA_LOGITS_CHUNK_N)
+
+
+def _paged_cache(kv_cache: torch.Tensor):
+    """The indexer's paged key cache, checked: uint8 [num_blocks, 64, 1, 132] or [num_blocks, 8448], the bytes of a block contiguous,
+    blocks stride(0) >= 8448 bytes apart, a multiple of 16.  Returns (num_blocks, block stride)."""
+    _require(kv_cache.dtype == torch.uint8, "kv_cache must be uint8, got %s", kv_cache.dtype)
+    _require(kv_cache.dim() in (2, 4), "kv_cache must be [num_blocks, 64, 1, 132] or [num_blocks, %d]", PAGED_MQA_LOGITS_BLOCK_BYTES)
+    if kv_cache.dim() == 4:
+        nb, bs, one, row = kv_cache.shape
+        _require(bs == PAGED_MQA_LOGITS_BLOCK_KV, "kv_cache must have blocks of 64 keys, got %d", bs)
+        _require(one == 1 and row == MQA_LOGITS_HEAD_DIM + 4, "kv_cache must be [num_blocks, 64, 1, 132]: %d x %d bytes per key", one, row)
+        inner = kv_cache.stride(1) == row and kv_cache.stride(3) == 1
+    else:
+        nb, row = kv_cache.shape
+        _require(row == PAGED_MQA_LOGITS_BLOCK_BYTES, "kv_cache must be [num_blocks, %d], got %d bytes per block", PAGED_MQA_LOGITS_BLOCK_BYTES, row)
+        inner = kv_cache.stride(1) == 1
+    _require(nb >= 1, "kv_cache must have at least one block")
+    _require(inner, "kv_cache must be contiguous inside a block")
+    stride = kv_cache.stride(0) if nb > 1 else PAGED_MQA_LOGITS_BLOCK_BYTES
+    _require(stride >= PAGED_MQA_LOGITS_BLOCK_BYTES and stride % 16 == 0,
+             "kv_cache blocks must be at least %d bytes apart and a multiple of 16, got stride(0) = %d", PAGED_MQA_LOGITS_BLOCK_BYTES, stride)
+    return nb, stride
+
+
+def fp8_paged_mqa_logits(q: torch.Tensor, kv_cache: torch.Tensor, weights: torch.Tensor, context_lens: torch.Tensor,
+                         block_tables: torch.Tensor, schedule_metadata=None, max_model_len: Optional[int] = None,
+                         clean_logits: bool = True, out: Optional[torch.Tensor] = None, sync: bool = False) -> torch.Tensor:
+    """The decode half of the lightning indexer's scoring, upstream DeepGEMM's fp8_paged_mqa_logits in its positional order
+    (dga_fp8_paged_mqa_logits): each of B sequences scores its next_n newest tokens against its whole context in a paged key cache.
+    q [B, next_n, H, 128] float8_e4m3fn (or uint8 bytes) without a scale, next_n 1 or 2, H 32 or 64; kv_cache uint8
+    [num_blocks, 64, 1, 132] or [num_blocks, 8448]: block b holds the codes of its 64 keys, key-major, in bytes 0 .. 8191 and their 64
+    float32 scales in bytes 8192 .. 8447 (upstream's fused layout; per_token_cast_to_fp8_paged writes it), stride(0) >= 8448 and a multiple
+    of 16; weights float32 [B next_n, H]; context_lens int32 [B] and block_tables int32 [B, max_blocks], device tensors read on the device;
+    max_model_len = N, the width of the result, is required.  With ctx_i = min(max(context_lens[i], 0), N, 64 max_blocks) and row
+    r = i next_n + j: logits[r, n] = kscale sum_h weights[r, h] relu(sum_d q[i, j, h, d] k[d]) for n < max(ctx_i - next_n + j + 1, 0), k the
+    key n % 64 of block block_tables[i, n // 64], and -inf from there to N.  Returns float32 [B next_n, N] (out= takes the caller's).
+    A table entry is read only for pages below ceil(ctx_i / 64); one of those outside [0, num_blocks) dereferences nothing and gives -inf
+    on its page's columns.  clean_logits=True writes every element; clean_logits=False writes the rows of sequence i only in columns
+    below 64 ceil(ctx_i / 64) and touches nothing from there on (what serving engines use: the -inf fill can cost as much as the scoring).
+    The arithmetic is fp8_mqa_logits': on the keys and scales gathered through a sequence's table the in-range elements are that
+    function's bit for bit, with its bound; no atomics, two runs give the same bits.
+    schedule_metadata is accepted for upstream call sites and never read: upstream's value is a per-SM work split for a persistent
+    scheduler, while this kernel's grid, B x ceil(N / 512), is fixed by the shapes and no workgroup assumes residency -- there is no such
+    table, and no get_paged_mqa_logits_metadata.  B == 0 returns without a launch."""
+    _require(q.dim() == 4, "q must be [B, next_n, H, %d]", MQA_LOGITS_HEAD_DIM)
+    b, nn, h, d = q.shape
+    _require(d == MQA_LOGITS_HEAD_DIM, "q must be [B, next_n, H, %d]: head dimension %d is not supported", MQA_LOGITS_HEAD_DIM, d)
+    _require(nn in (1, 2), "q must have next_n 1 or 2, got %d", nn)
+    _require(h in MQA_LOGITS_HEADS, "q must have 32 or 64 heads, got %d", h)
+    _want(_fp8_bytes(q), "q", None, (b, nn, h, d))
+    nb, stride = _paged_cache(kv_cache)
+    _want(weights, "weights", torch.float32, (b * nn, h))
+    _want(context_lens, "context_lens", torch.int32, (b,))
+    _require(block_tables.dim() == 2 and block_tables.shape[1] >= 1, "block_tables must be [B, max_blocks] with max_blocks >= 1")
+    max_blocks = block_tables.shape[1]
+    _want(block_tables, "block_tables", torch.int32, (b, max_blocks))
+    _require(max_model_len is not None, "max_model_len is required: it is the width of the result")
+    n = int(max_model_len)
+    _require(n >= 1, "max_model_len must be at least 1, got %d", n)
+    if out is None:
+        out = torch.empty((b * nn, n), dtype=torch.float32, device=q.device)
+    else:
+        _want(out, "out", torch.float32, (b * nn, n))
+    # (B == 0: the C entry returns before any launch)
+    _launch("fp8_paged_mqa_logits", (q, kv_cache, weights, context_lens, block_tables, out), lambda L, stream: L.dga_fp8_paged_mqa_logits(
+        q.data_ptr(), kv_cache.data_ptr(), weights.data_ptr(), context_lens.data_ptr(), block_tables.data_ptr(), b, nn, h, d, nb, stride,
+        max_blocks, n, 1 if clean_logits else 0, out.data_ptr(), stream), sync)
+    return out
+
+
+def per_token_cast_to_fp8_paged(x: torch.Tensor, kv_cache: torch.Tensor, slot_mapping: torch.Tensor, use_ue8m0: bool = False,
+                                sync: bool = False) -> torch.Tensor:
+    """The writer of fp8_paged_mqa_logits' key cache (dga_cast_to_fp8_1x128_paged): x [T, 128] float32 / bfloat16 / float16, kv_cache as
+    there, slot_mapping int64 [T] on the device.  For every t with 0 <= slot_mapping[t] < 64 num_blocks the 128 codes of
+    per_token_cast_to_fp8(x, use_ue8m0=...)[0][t] go to bytes 128 (slot % 64) .. of block slot // 64 and the scale [1][t, 0] to bytes
+    8192 + 4 (slot % 64) .. of that block, byte for byte.  Any other slot value (engines pad with -1) skips the token and dereferences
+    nothing; no other byte of the cache is touched.  Duplicate valid slots in one call are the caller's error.  Returns kv_cache."""
+    _require(x.dim() == 2 and x.shape[1] == MQA_LOGITS_HEAD_DIM and x.is_contiguous(), "x must be a contiguous [T, %d] tensor", MQA_LOGITS_HEAD_DIM)
+    _require(x.dtype in _CAST_DT, "x must be float32, bfloat16 or float16")
+    t = x.shape[0]
+    nb, stride = _paged_cache(kv_cache)
+    _want(slot_mapping, "slot_mapping", torch.int64, (t,))
+    # (T == 0: the C entry returns before any launch)
+    _launch("per_token_cast_to_fp8_paged", (x, kv_cache, slot_mapping), lambda L, stream: L.dga_cast_to_fp8_1x128_paged(
+        x.data_ptr(), _CAST_DT[x.dtype], t, kv_cache.data_ptr(), nb, stride, slot_mapping.data_ptr(),
+        _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+    return kv_cache
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

@@ -27,6 +27,7 @@
 
 #include "dga_hip.h"
 #include "dga_internal.hpp"
+#include "dga_mqa_device.hpp"
 
 #pragma clang fp contract(off)
 
@@ -37,22 +38,6 @@ constexpr int MQA_BN = DGA_MQA_LOGITS_BLOCK_N;   // keys of a workgroup
 constexpr int MQA_BM = DGA_MQA_LOGITS_BLOCK_M;   // tokens of a workgroup's run: one per lane of a wave (the ballot below)
 constexpr int MQA_D = DGA_MQA_LOGITS_HEAD_DIM;
 static_assert(MQA_BM == 64 && MQA_BN == 64 * (MQA_THREADS / 64) && MQA_D == 128, "the kernel's geometry");
-
-typedef int mqa_v2i __attribute__((ext_vector_type(2)));
-typedef int mqa_v4i __attribute__((ext_vector_type(4)));
-typedef float mqa_v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 mqa_v8bf __attribute__((ext_vector_type(8)));
-
-// 8 e4m3 codes (ascending d) -> 8 bf16, exact
-__device__ __forceinline__ mqa_v4i mqa_cvt8(mqa_v2i raw)
-{
-    mqa_v4i r;
-    r[0] = __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[0], 1.0f, false));
-    r[1] = __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[0], 1.0f, true));
-    r[2] = __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[1], 1.0f, false));
-    r[3] = __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(raw[1], 1.0f, true));
-    return r;
-}
 
 __device__ __forceinline__ int mqa_clamp(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }
 
@@ -151,27 +136,9 @@ __global__ void __launch_bounds__(MQA_THREADS) mqa_logits_kernel(const uint8_t *
                 mqa_v4i af[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) af[s] = mqa_cvt8(img[(ht * 4 + s) * 64 + lane]);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    mqa_v4f acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mqa_v8bf, af[s]), __builtin_bit_cast(mqa_v8bf, bf[nt][s]),
-                                                                      acc, 0, 0, 0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float s = acc[r] < 0.f ? 0.f : acc[r];          // (keeps a NaN)
-                        p[nt] = __builtin_fmaf(w[ht][r], s, p[nt]);
-                    }
-                }
+                mqa_head_tile(af, bf, w[ht], p);
             }
-            // (P_0 + P_2) + (P_1 + P_3), lane group g keeping key tile g
-            const bool up2 = (g & 2) != 0, up1 = (g & 1) != 0;
-            float k0 = up2 ? p[2] : p[0], k1 = up2 ? p[3] : p[1];
-            k0 = k0 + __shfl_xor(up2 ? p[0] : p[2], 32, 64);
-            k1 = k1 + __shfl_xor(up2 ? p[1] : p[3], 32, 64);
-            float v = up1 ? k1 : k0;
-            v = v + __shfl_xor(up1 ? k0 : k1, 16, 64);
+            const float v = mqa_exchange(p, g);
             if (my_n >= lo && my_n < hi) val = v * scale;
         }
         if (my_ok) orow[(int64_t)i * n_n] = val;

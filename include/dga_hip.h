@@ -902,6 +902,55 @@ int64_t dga_rms_norm_backward_workspace_bytes(int64_t rows, int64_t h);
 int dga_fp8_mqa_logits(const void *q, const void *k, const float *kscale, const float *weights, const int32_t *ks, const int32_t *ke,
                        int64_t m, int64_t n, int heads, int head_dim, float *logits, void *stream);
 
+/* The decode half of that scoring, upstream DeepGEMM's fp8_paged_mqa_logits (csrc/dga_paged_mqa_logits.hip): each of `batch` sequences
+ * scores its next_n (1 or 2) newest tokens against its whole context, whose keys live in a paged cache reached through a block table.
+ *   kv_cache      block b is DGA_PAGED_MQA_LOGITS_BLOCK_BYTES = 8448 bytes at b * block_stride: bytes 0 .. 8191 the e4m3 codes of its
+ *                 DGA_PAGED_MQA_LOGITS_BLOCK_KV = 64 keys, key-major (64 x 128), bytes 8192 .. 8447 their 64 fp32 scales (upstream's fused
+ *                 layout: codes first, then scales).  block_stride >= 8448 and a multiple of 16, the base 16-byte aligned, num_blocks >= 1.
+ *   q             [batch, next_n, heads, 128] contiguous e4m3fn codes, no scale;  weights fp32 [batch next_n, heads]
+ *   context_lens  int32 [batch], block_tables int32 [batch, max_blocks] (max_blocks >= 1), both on the device and read there, so a
+ *                 captured graph follows new lengths and tables
+ *   logits        fp32 [batch next_n, max_model_len] contiguous
+ *   ctx_i        = min(max(context_lens[i], 0), max_model_len, 64 max_blocks)
+ *   hi_r         = max(ctx_i - next_n + j + 1, 0)                                       row r = i next_n + j, j < next_n
+ *   key n of sequence i = key n % 64 of block block_tables[i, n / 64]
+ *   logits[r,n]  = kscale * sum_h weights[r,h] * max(sum_d q[i,j,h,d] k[d], 0)          for n < hi_r
+ *                = -inf                                                                  for hi_r <= n < max_model_len
+ * A table entry is read only for pages p < ceil(ctx_i / 64); the others may hold anything.  An entry of a needed page outside
+ * [0, num_blocks) dereferences nothing: that page's columns are -inf in the sequence's rows.  Two sequences may name the same block.
+ * clean_logits != 0: every element of logits is written on every call.  clean_logits == 0: the rows of sequence i are written only in
+ * columns n < min(64 ceil(ctx_i / 64), max_model_len) -- values below hi_r, -inf from there -- and no byte at or beyond that column is
+ * touched.  The arithmetic, the order of the head sum and the bound are dga_fp8_mqa_logits': with kg / sg the keys and scales gathered
+ * through a sequence's table, its rows are bit for bit dga_fp8_mqa_logits(q[i], kg, sg, weights[rows], ks = 0, ke = hi_r) in the columns
+ * below ctx_i.  No atomics, one writer per element, two runs give the same bits; a NaN code in a key poisons its column in every
+ * sequence whose table names the block, one in q[i, j] row r, inside the ranges only.  A workgroup owns one sequence and
+ * DGA_PAGED_MQA_LOGITS_CHUNK_N columns; the grid, batch x ceil(max_model_len / CHUNK_N), depends on the shapes alone and no workgroup
+ * waits for another, so there is no scheduling table to pass (upstream's schedule_metadata has no counterpart).  No byte outside a
+ * named block's 8448 is read, and no row of q / weights / context_lens / block_tables at or beyond batch.  One launch (capturable).
+ * DGA_E_SHAPE: batch < 0, next_n other than 1 or 2, heads other than 32 or 64, head_dim != 128, num_blocks < 1, block_stride < 8448,
+ * max_blocks < 1, max_model_len < 1;  batch == 0 is DGA_OK with nothing launched and no pointer looked at;  then DGA_E_NULL (any pointer),
+ * DGA_E_ALIGN (q not 8-byte, kv_cache or weights not 16-byte, the others not 4-byte aligned, block_stride not a multiple of 16), and
+ * DGA_E_RANGE for max_model_len > DGA_PAGED_MQA_LOGITS_MAX_N, a cache, table or output whose size leaves int64, or more workgroups than
+ * one grid holds (2^31 - 1). */
+#define DGA_PAGED_MQA_LOGITS_BLOCK_KV 64          /* keys of a block of the cache */
+#define DGA_PAGED_MQA_LOGITS_BLOCK_BYTES 8448     /* 64 * 128 codes + 64 fp32 scales */
+#define DGA_PAGED_MQA_LOGITS_CHUNK_N 512          /* columns of one workgroup */
+#define DGA_PAGED_MQA_LOGITS_MAX_N 0x7FFFFC00
+int dga_fp8_paged_mqa_logits(const void *q, const void *kv_cache, const float *weights, const int32_t *context_lens,
+                             const int32_t *block_tables, int64_t batch, int next_n, int heads, int head_dim, int64_t num_blocks,
+                             int64_t block_stride, int64_t max_blocks, int64_t max_model_len, int clean_logits, float *logits, void *stream);
+
+/* The writer of that cache (csrc/dga_cast_paged.hip): x [tokens, 128] of x_dtype (DGA_DT_FP32 / _BF16 / _FP16) contiguous, slot_mapping
+ * int64 [tokens] on the device.  Token t with 0 <= slot_mapping[t] < 64 num_blocks: its 128 codes go to bytes 128 (slot % 64) .. of block
+ * slot / 64 and its scale to bytes 8192 + 4 (slot % 64) .. of that block -- dga_cast_to_fp8_1x128_ex(x, flags)'s codes and scale of row t,
+ * byte for byte.  Any other slot value (-1 on padding) skips the token: its row is not read and nothing is dereferenced.  No other byte of the
+ * cache is touched.  Two tokens with one valid slot are the caller's error (each byte is then one writer's).  flags: DGA_CAST_UE8M0.
+ * The quantisers' order of checks: DGA_E_RANGE (flag), DGA_E_SHAPE (tokens < 0, num_blocks < 1, block_stride < 8448), tokens == 0 ->
+ * DGA_OK with nothing launched, DGA_E_NULL, DGA_E_DTYPE, DGA_E_ALIGN (x or kv_cache not 16-byte, slot_mapping not 8-byte aligned,
+ * block_stride not a multiple of 16), DGA_E_RANGE (the cache's size leaves int64, the grid).  One launch (capturable). */
+int dga_cast_to_fp8_1x128_paged(const void *x, int x_dtype, int64_t tokens, void *kv_cache, int64_t num_blocks, int64_t block_stride,
+                                const int64_t *slot_mapping, int flags, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
