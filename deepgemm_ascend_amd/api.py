@@ -1928,6 +1928,71 @@ def per_token_cast_to_fp8_paged(x: torch.Tensor, kv_cache: torch.Tensor, slot_ma
     return kv_cache
 
 
+INDEXER_TOPK_MAX_K = 2048            # DGA_INDEXER_TOPK_MAX_K
+INDEXER_TOPK_CANDIDATES = 8192       # keys of the kernel's LDS candidate buffer (DGA_INDEXER_TOPK_CANDIDATES)
+
+
+def indexer_topk(logits: torch.Tensor, k: int = 2048, row_starts: Optional[torch.Tensor] = None, row_ends: Optional[torch.Tensor] = None,
+                 context_lens: Optional[torch.Tensor] = None, next_n: int = 1, relative: bool = False,
+                 block_tables: Optional[torch.Tensor] = None, page_size: int = 64, num_blocks: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None, sync: bool = False) -> torch.Tensor:
+    """The selecting half of the lightning indexer (dga_indexer_topk): per row of fp8_mqa_logits' / fp8_paged_mqa_logits' output, the
+    indices of the k highest-scoring keys inside the row's range, ascending, as int32 [M, k].  logits float32 [M, N] with a contiguous
+    last dimension and any stride(0) >= N (a column slice logits[:, :64 max_blocks] of a wider buffer is accepted); 1 <= k <= 2048.
+    The range [lo, hi) of row m is formed on the device from exactly one of: row_starts, row_ends int32 [M] (both or neither; the tensors
+    given to fp8_mqa_logits): lo = min(max(ks, 0), N), hi = min(max(ke, 0), N);  context_lens int32 [B] with next_n 1 or 2 and
+    M = B next_n: ctx = min(max(context_lens[m // next_n], 0), N), lo = 0, hi = max(ctx - next_n + m % next_n + 1, 0)
+    (fp8_paged_mqa_logits' rule);  neither: lo = 0, hi = N.
+    The order is total and defined on the bits: key(x) = bits(x) ^ (0xFFFFFFFF if bits(x) >> 31 else 0x80000000), every NaN 0xFFFFFFFF
+    (above +inf, as torch.topk ranks it; -0 below +0); column a precedes b iff its key is greater, or equal and a < b.  With
+    c = min(hi - lo, k), out[m, :c] is the first c columns of [lo, hi) in that order, sorted ascending by column, and out[m, c:] is -1;
+    every element of out is written.  Membership is by column, never by value (an in-range -inf is a candidate); no byte of logits outside
+    [lo, hi) is read, so a buffer fp8_paged_mqa_logits(clean_logits=False) left unwritten beyond a sequence's last page is valid
+    input; a row with hi - lo <= k reads no logits.  What is written for a selected column n: n;  relative=True: n - lo (what a prefill
+    caller hands to sparse attention);  block_tables int32 [B, max_blocks] with page_size >= 1 and num_blocks (lengths form only):
+    block_tables[m // next_n, n // page_size] page_size + n % page_size, and -1 where n // page_size >= max_blocks or the entry lies
+    outside [0, num_blocks); entries of unselected columns are not read.  The result is a pure function of the in-range bits: two
+    runs give the same bytes, and a stable numpy argsort reproduces them.  One launch, capturable; M == 0 returns without one."""
+    _require(logits.dim() == 2 and logits.dtype == torch.float32, "logits must be a float32 [M, N] tensor")
+    m, n = logits.shape
+    _require(n >= 1, "logits must have at least one column")
+    _require((n == 1 or logits.stride(1) == 1) and (m <= 1 or logits.stride(0) >= n),
+             "logits must have a contiguous last dimension and stride(0) >= N")
+    _require(isinstance(k, int) and 1 <= k <= INDEXER_TOPK_MAX_K, "k must be an integer in [1, %d]", INDEXER_TOPK_MAX_K)
+    _require((row_starts is None) == (row_ends is None), "row_starts and row_ends come together or not at all")
+    _require(row_starts is None or context_lens is None, "row_starts / row_ends and context_lens exclude each other")
+    _require(not (relative and block_tables is not None), "relative and block_tables exclude each other")
+    _require(block_tables is None or context_lens is not None, "block_tables needs context_lens")
+    if row_starts is not None:
+        _want(row_starts, "row_starts", torch.int32, (m,))
+        _want(row_ends, "row_ends", torch.int32, (m,))
+    b, max_blocks, blocks = 0, 0, 0
+    if context_lens is not None:
+        _require(next_n in (1, 2), "next_n must be 1 or 2")
+        _require(m % next_n == 0, "logits must have B next_n rows, got %d with next_n = %d", m, next_n)
+        b = m // next_n
+        _want(context_lens, "context_lens", torch.int32, (b,))
+    if block_tables is not None:
+        _require(block_tables.dim() == 2 and block_tables.shape[1] >= 1, "block_tables must be [B, max_blocks] with max_blocks >= 1")
+        max_blocks = block_tables.shape[1]
+        _want(block_tables, "block_tables", torch.int32, (b, max_blocks))
+        _require(isinstance(page_size, int) and page_size >= 1, "page_size must be an integer >= 1")
+        _require(isinstance(num_blocks, int) and num_blocks >= 1, "num_blocks is required with block_tables: an integer >= 1")
+        _require(num_blocks * page_size < 1 << 31, "num_blocks page_size must be below 2^31, got %d x %d", num_blocks, page_size)
+        blocks = num_blocks
+    if out is None:
+        out = torch.empty((m, k), dtype=torch.int32, device=logits.device)
+    else:
+        _want(out, "out", torch.int32, (m, k))
+    stride = logits.stride(0) if m > 1 else n
+    # (M == 0: the C entry returns before any launch)
+    _launch("indexer_topk", (logits, row_starts, row_ends, context_lens, block_tables, out), lambda L, stream: L.dga_indexer_topk(
+        logits.data_ptr(), m, n, stride, k, _ptr(row_starts), _ptr(row_ends), _ptr(context_lens), next_n if context_lens is not None else 1,
+        1 if relative else 0, _ptr(block_tables), max_blocks, page_size if block_tables is not None else 1, blocks, out.data_ptr(), stream),
+        sync)
+    return out
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

@@ -951,6 +951,40 @@ int dga_fp8_paged_mqa_logits(const void *q, const void *kv_cache, const float *w
 int dga_cast_to_fp8_1x128_paged(const void *x, int x_dtype, int64_t tokens, void *kv_cache, int64_t num_blocks, int64_t block_stride,
                                 const int64_t *slot_mapping, int flags, void *stream);
 
+/* The selecting half of the indexer (csrc/dga_indexer_topk.hip): per row of the logits of dga_fp8_mqa_logits / dga_fp8_paged_mqa_logits,
+ * the indices of the k highest-scoring columns inside the row's range, in ascending column order.
+ *   logits        fp32 [m, n], the last dimension contiguous, rows `stride` elements apart (stride >= n: a column slice of a wider
+ *                 buffer is accepted), 4-byte aligned;  out int32 [m, k] contiguous, every element written at every call
+ *   [lo, hi) of row r, formed on the device from exactly one of
+ *     row_starts, row_ends  int32 [m] (both or neither): lo = min(max(ks[r], 0), n), hi = min(max(ke[r], 0), n); hi <= lo: an empty row
+ *     context_lens          int32 [m / next_n], next_n 1 or 2: ctx = min(max(context_lens[r / next_n], 0), n), lo = 0,
+ *                           hi = max(ctx - next_n + r % next_n + 1, 0)  (dga_fp8_paged_mqa_logits' rule)
+ *     neither               lo = 0, hi = n
+ *   key(x)        = bits(x) ^ (bits(x) >> 31 ? 0xFFFFFFFF : 0x80000000) as uint32, every NaN 0xFFFFFFFF (above +inf; -0 below +0)
+ *   order         column a precedes column b iff key is greater, or key is equal and a < b  (total)
+ *   c = min(hi - lo, k);  out[r, 0 .. c) = the first c columns of [lo, hi) in that order, sorted ascending by column, then mapped;
+ *   out[r, c .. k) = -1
+ *   mapping of a selected column col: col itself;  relative != 0: col - lo;  block_tables int32 [m / next_n, max_blocks] (lengths form
+ *   only, page_size >= 1, num_blocks page_size < 2^31): block_tables[r / next_n, col / page_size] * page_size + col % page_size, and -1 where
+ *   col / page_size >= max_blocks or the entry lies outside [0, num_blocks).  Entries of unselected columns are not read.
+ * Membership is by column, never by value: an in-range -inf is a candidate.  No byte of logits outside [lo, hi) is read -- a buffer that
+ * dga_fp8_paged_mqa_logits left unwritten beyond a sequence's last page (clean_logits == 0) is valid input -- and a row with
+ * hi - lo <= k reads no logits at all.  The result is a pure function of the in-range bits: two runs give the same bytes.
+ * One workgroup owns one row (a radix select on key in LDS, then one ordered pass that writes; no workgroup waits for another, no
+ * atomics on global memory); a bin that fits DGA_INDEXER_TOPK_CANDIDATES keys is finished inside LDS.  One launch (capturable), and a
+ * captured graph follows new ranges, lengths and tables.
+ * Checks, all before the launch: DGA_E_SHAPE (m < 0, n < 1, stride < n);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (logits,
+ * out, one of row_starts / row_ends without the other);  DGA_E_ALIGN (a pointer not 4-byte aligned);  DGA_E_RANGE (k outside
+ * [1, DGA_INDEXER_TOPK_MAX_K], n > DGA_INDEXER_TOPK_MAX_N, m >= 2^31, ranges beside lengths, relative beside block_tables, block_tables
+ * without context_lens, next_n other than 1 or 2, page_size / max_blocks / num_blocks < 1, num_blocks page_size >= 2^31, m stride or
+ * the table's size beyond int64);  DGA_E_SHAPE for m not a multiple of next_n. */
+#define DGA_INDEXER_TOPK_MAX_K 2048
+#define DGA_INDEXER_TOPK_CANDIDATES 8192          /* keys of the LDS candidate buffer */
+#define DGA_INDEXER_TOPK_MAX_N 0x7FFF0000
+int dga_indexer_topk(const float *logits, int64_t m, int64_t n, int64_t stride, int k, const int32_t *row_starts, const int32_t *row_ends,
+                     const int32_t *context_lens, int next_n, int relative, const int32_t *block_tables, int64_t max_blocks, int page_size,
+                     int64_t num_blocks, int32_t *out, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
