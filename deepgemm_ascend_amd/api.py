@@ -1993,6 +1993,69 @@ def indexer_topk(logits: torch.Tensor, k: int = 2048, row_starts: Optional[torch
     return out
 
 
+SPARSE_MLA_D_QK = 576                # DGA_SPARSE_MLA_D_QK: 512 latent + 64 rope dimensions
+SPARSE_MLA_D_V = 512                 # DGA_SPARSE_MLA_D_V
+SPARSE_MLA_MAX_HEADS = 128           # DGA_SPARSE_MLA_MAX_HEADS
+
+
+def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
+                   index_offsets: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+                   sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What the indexer selects for (dga_sparse_mla_fwd): sparse MLA attention, forward, over indexer_topk's indices, in MLA's absorbed
+    (MQA) form; the positional order is FlashMLA's flash_mla_sparse_fwd.  q bfloat16 [M, Hq, 576] contiguous, Hq a multiple of 16 in
+    [16, 128];  kv bfloat16 [S, 576] or [S, 1, 576] with a contiguous last dimension, stride(0) >= 576 and a multiple of 8, a 16-byte
+    aligned base and 1 <= S < 2^31 -- every row is key (all 576 columns) and value (its first 512); a flat view of a paged bf16 latent
+    cache is valid input and indexer_topk(block_tables=...)'s physical slots index it directly;  indices int32 [M, topk] or [M, 1, topk]
+    with a contiguous last dimension and stride(0) >= topk >= 1 (a slice idx[:, :k'] is accepted);  index_offsets int32 [M] or None: the
+    kv row of position j is indices[m, j] + index_offsets[m] (fp8_mqa_logits' row_starts beside indexer_topk(relative=True));
+    d_v must be 512.
+    Everything is read on the device.  A position is valid iff indices[m, j] >= 0 and its row lies in [0, S); an invalid one
+    (indexer_topk's -1 padding, any other negative, anything >= S) dereferences nothing and contributes nothing; duplicates count once
+    per position; no other kv row and no column >= 576 of any row is read.  Over the valid positions, with r_j the row:
+    s_j = sm_scale sum_d q[m, h, d] kv[r_j, d];  lse[m, h] = ln sum_j exp(s_j) (float32 [M, Hq], natural log: what a merge over chunks of
+    topk or over ranks needs);  out[m, h, :] = sum_j exp(s_j - lse) kv[r_j, :512] (bfloat16 [M, Hq, 512]).  A token with no valid
+    position gets out = +0 and lse = -inf.  Every element of both outputs is written.
+    Arithmetic: exact bf16 products summed in fp32 on the matrix pipe over d ascending; an online softmax over tiles of 32 positions in
+    list order; the weights rounded to bf16 (RNE) for the second product while their sum l stays unrounded fp32; one multiplication by
+    1 / l at the end.  One writer per element, no atomics: two runs give the same bytes.  Returns (out, lse), the caller's out= / lse=
+    when given.  One launch, capturable -- a replayed graph follows new indices, offsets, kv and q; M == 0 returns without one."""
+    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
+             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
+    m, heads = q.shape[0], q.shape[1]
+    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
+             SPARSE_MLA_MAX_HEADS, heads)
+    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
+    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    _require(kv.dtype == torch.bfloat16 and (kv.dim() == 2 or (kv.dim() == 3 and kv.shape[1] == 1)) and kv.shape[-1] == SPARSE_MLA_D_QK,
+             "kv must be a bfloat16 [S, %d] or [S, 1, %d] tensor", SPARSE_MLA_D_QK, SPARSE_MLA_D_QK)
+    s = kv.shape[0]
+    _require(1 <= s < 1 << 31, "kv must have between 1 and 2^31 - 1 rows, got %d", s)
+    kv_stride = kv.stride(0) if s > 1 else SPARSE_MLA_D_QK
+    _require(kv.stride(-1) == 1 and kv_stride >= SPARSE_MLA_D_QK and kv_stride % 8 == 0,
+             "kv must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 8, got %d", SPARSE_MLA_D_QK, kv_stride)
+    _require(kv.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0, "q and kv must be 16-byte aligned")
+    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
+             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
+    topk = indices.shape[-1]
+    idx_stride = indices.stride(0) if m > 1 else topk
+    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
+    if index_offsets is not None:
+        _want(index_offsets, "index_offsets", torch.int32, (m,))
+    if out is None:
+        out = torch.empty((m, heads, SPARSE_MLA_D_V), dtype=torch.bfloat16, device=q.device)
+    else:
+        _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    if lse is None:
+        lse = torch.empty((m, heads), dtype=torch.float32, device=q.device)
+    else:
+        _want(lse, "lse", torch.float32, (m, heads))
+    # (M == 0: the C entry returns before any launch)
+    _launch("sparse_mla_fwd", (q, kv, indices, index_offsets, out, lse), lambda L, stream: L.dga_sparse_mla_fwd(
+        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale),
+        _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
+    return out, lse
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

@@ -985,6 +985,37 @@ int dga_indexer_topk(const float *logits, int64_t m, int64_t n, int64_t stride, 
                      const int32_t *context_lens, int next_n, int relative, const int32_t *block_tables, int64_t max_blocks, int page_size,
                      int64_t num_blocks, int32_t *out, void *stream);
 
+/* What the indexer selects for (csrc/dga_sparse_mla.hip): sparse MLA attention, forward, in MLA's absorbed (MQA) form -- every kv row is
+ * key (all 576 columns: 512 latent + 64 rope) and value (its first 512 columns) of every head.
+ *   q             bf16 [m, heads, 576] contiguous, 16-byte aligned; heads a multiple of 16 in [16, DGA_SPARSE_MLA_MAX_HEADS]
+ *   kv            bf16 [s, 576], rows kv_stride elements apart (kv_stride >= 576 and a multiple of 8), 16-byte aligned, 1 <= s < 2^31:
+ *                 a flat view of a paged bf16 latent cache, which dga_indexer_topk's physical slots index directly
+ *   indices       int32 [m, topk], rows idx_stride elements apart (idx_stride >= topk >= 1: a column slice of a wider tensor is accepted)
+ *   index_offsets int32 [m] or NULL: the kv row of position j of token t is r = indices[t, j] + index_offsets[t]
+ *                 (dga_fp8_mqa_logits' row_starts beside dga_indexer_topk(relative))
+ *   a position is valid iff indices[t, j] >= 0 and 0 <= r < s; an invalid one (the -1 padding, any other negative, anything >= s)
+ *   dereferences nothing and contributes nothing; duplicates count once per position; no other kv row and no column >= 576 is read
+ *   over the valid positions:  s_j = sm_scale sum_d q[t, h, d] kv[r_j, d];  lse[t, h] = ln sum_j exp(s_j)  (fp32 [m, heads]);
+ *   out[t, h, :] = sum_j exp(s_j - lse) kv[r_j, :512]  (bf16 [m, heads, 512], 16-byte aligned)
+ *   a token without a valid position: out = +0, lse = -inf.  Every element of out and lse is written at every call.
+ * Arithmetic: the bf16 products exact, summed in fp32 by v_mfma_f32_16x16x32_bf16 over d ascending, times (float)(sm_scale log2 e) -- the
+ * one rounding of the scale, which is why it arrives as a double; an online softmax over tiles of
+ * DGA_SPARSE_MLA_TILE positions in list order (running maximum, and a running sum l of the unrounded fp32 weights p); p rounded to bf16
+ * (RNE) for the second product, its sums fp32 in list order; one multiplication by 1 / l at the end.  One writer per output, no
+ * atomics: two runs give the same bits.  One launch (capturable); a captured graph follows new indices, offsets, kv and q.
+ * flags: DGA_SPARSE_MLA_LINEAR_GRID takes the workgroups in grid order (the default walks consecutive tokens on one XCD); same bits.
+ * Checks, all before the launch: DGA_E_RANGE (an unknown flag);  DGA_E_SHAPE (m < 0, heads, s < 1, topk < 1, kv_stride < 576,
+ * idx_stride < topk);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (q, kv, indices, out, lse);  DGA_E_ALIGN (q, kv or out not
+ * 16-byte, indices, index_offsets or lse not 4-byte aligned, kv_stride not a multiple of 8);  DGA_E_RANGE (s >= 2^31, topk or the grid
+ * beyond int32, s kv_stride or m idx_stride beyond int64). */
+#define DGA_SPARSE_MLA_D_QK 576
+#define DGA_SPARSE_MLA_D_V 512
+#define DGA_SPARSE_MLA_MAX_HEADS 128
+#define DGA_SPARSE_MLA_TILE 32
+#define DGA_SPARSE_MLA_LINEAR_GRID 1
+int dga_sparse_mla_fwd(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int64_t s,
+                       int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, void *out, float *lse, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
