@@ -39,13 +39,14 @@ def in_range(ks, ke, n):
     return (col >= lo[:, None]) & (col < hi[:, None])
 
 
-def reference(q, k, kscale, weights, ks, ke):
+def reference(q, k, kscale, weights, ks, ke, table=TABLE):
     """(logits float64 [M, N] with -inf outside the ranges, mag float64 [M, N] = kscale[n] sum_h |weights| sum_d |q k|).  q uint8 [M, H, 128],
-    k uint8 [N, 128] codes.  A NaN code makes its row (q) or column (k) NaN inside the ranges, as the definition's arithmetic does."""
+    k uint8 [N, 128] codes.  A NaN code makes its row (q) or column (k) NaN inside the ranges, as the definition's arithmetic does.
+    (table: another decoding of the 256 codes -- what a wrong conversion would compute, for the tests of the checkers themselves.)"""
     m, h, d = q.shape
     n = k.shape[0]
     assert d == D and k.shape == (n, D) and weights.shape == (m, h) and kscale.shape == (n,)
-    qf, kf = TABLE[q].reshape(m * h, d), TABLE[k]
+    qf, kf = table[q].reshape(m * h, d), table[k]
     w = weights.astype(np.float64)
     with np.errstate(invalid="ignore"):
         s = (qf @ kf.T).reshape(m, h, n)
@@ -137,3 +138,91 @@ def exact_case(m, n, h, kind="full", seed=0):
     ks, ke = ranges(kind, m, n)
     want, _ = reference(q, k, kscale, weights, ks, ke)
     return (q, k, kscale, weights) + _frozen(ks, ke, want)
+
+
+def assert_same_values(got, want):
+    """got float32 equals the float64 reference as values: -inf exactly where it has it, no NaN, a zero of either sign is zero"""
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(np.isneginf(got), np.isneginf(want))
+    assert not np.isnan(got).any()
+    bad = np.argwhere(got.astype(np.float64) != want)
+    assert len(bad) == 0, (len(bad), bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+# ---- every e4m3 code, exactly -------------------------------------------------------------------------------------------------------
+
+FINITE = np.array([c for c in range(256) if c & 0x7F != 0x7F], dtype=np.uint8)         # the 254 codes that are no NaN
+ONE, MINUS_ONE = (int(np.flatnonzero(TABLE == v)[0]) for v in (1.0, -1.0))
+SUBNORMAL = np.array([c for c in range(256) if 1 <= c & 0x7F <= 7], dtype=np.uint8)    # 0x01 .. 0x07 and 0x81 .. 0x87
+CODES_N, CODES_M = BN + 37, 2 * D                     # the keys (two blocks, the second ragged) and tokens of the direct case
+MIRROR_M, MIRROR_N = 4 * BM + 38, 2 * D               # the tokens (five runs, the last ragged) and keys of the mirrored case
+
+
+def code_grid(rows, offset=0):
+    """uint8 [rows, 128]: FINITE[(r + 3 d + offset) % 254] -- 254 consecutive rows show every dimension every code"""
+    return FINITE[(np.arange(rows)[:, None] + 3 * np.arange(D)[None, :] + offset) % len(FINITE)]
+
+
+def unit_rows(rows):
+    """uint8 [rows, 128]: row r is zero but for the code of +1.0 (r < 128) or -1.0 at dimension r % 128"""
+    u = np.zeros((rows, D), np.uint8)
+    r = np.arange(rows)
+    u[r, r % D] = np.where(r < D, ONE, MINUS_ONE)
+    return u
+
+
+@functools.lru_cache(maxsize=None)
+def all_codes_operands(h, mirrored=False, n_keys=None):
+    """(q codes [M, h, 128], k codes [N, 128], weights [M, h], the head of every token that carries weight 1).
+    Direct: k = code_grid (every code in every dimension), token t has one nonzero weight, 1.0, on head (7 t) % h, and that head's q is
+    unit_rows' row t; the other heads hold zeros.  Mirrored: the keys are unit_rows, the weighted head of token t holds code_grid's row
+    t, and every other head holds other codes (code_grid shifted by 11 per head) under weight 0.
+    Every product but one a (token, key) pair is an exact zero or is multiplied by a zero weight, so a logit is relu(+-value(code)):
+    exact in fp32 in any order."""
+    m, n = (MIRROR_M, MIRROR_N) if mirrored else (CODES_M, CODES_N)
+    n = n if n_keys is None else n_keys
+    head = (7 * np.arange(m)) % h
+    weights = np.zeros((m, h), np.float32)
+    weights[np.arange(m), head] = 1.0
+    if mirrored:
+        shift = 11 * ((np.arange(h)[None, :] - head[:, None]) % h)                          # [m, h]: 0 on the weighted head
+        q = FINITE[(np.arange(m)[:, None, None] + 3 * np.arange(D)[None, None, :] + shift[:, :, None]) % len(FINITE)]
+        k = unit_rows(n)
+    else:
+        q = np.zeros((m, h, D), np.uint8)
+        q[np.arange(m), head] = unit_rows(m)
+        k = code_grid(n)
+    return _frozen(np.ascontiguousarray(q), k, weights, head)
+
+
+@functools.lru_cache(maxsize=None)
+def all_codes_case(h, mirrored=False):
+    """(q, k, kscale, weights, ks, ke, logits float64) of all_codes_operands under kscale = 1 and full ranges: the direct case gives
+    logits[t, n] = relu(+-value(k[n, t % 128])), the mirrored one relu(+-value(q[t, (7 t) % h, n % 128]))"""
+    q, k, weights, _ = all_codes_operands(h, mirrored)
+    m, n = q.shape[0], k.shape[0]
+    kscale = np.ones(n, np.float32)
+    ks, ke = ranges("full", m, n)
+    want, _ = reference(q, k, kscale, weights, ks, ke)
+    return (q, k) + _frozen(kscale) + (weights,) + _frozen(ks, ke, want)
+
+
+def all_codes_seen(h, mirrored=False):
+    """the codes that reach a logit as the operand opposite the unit code: k[n, t % 128] over all (t, n) of the direct case,
+    q[t, head_t, n % 128] of the mirrored one"""
+    q, k, _, head = all_codes_operands(h, mirrored)
+    if mirrored:
+        return np.unique(q[np.arange(q.shape[0]), head][:, np.arange(k.shape[0]) % D])
+    return np.unique(k[:, np.arange(q.shape[0]) % D])
+
+
+def broken_table(kind):
+    """TABLE as a wrong conversion would decode it: one subnormal code flushed to zero, or -0.5 read as +0.5"""
+    t = TABLE.copy()
+    if kind == "subnormal":
+        t[0x03] = 0.0
+    elif kind == "sign":
+        t[int(np.flatnonzero(TABLE == -0.5)[0])] = 0.5
+    else:
+        raise ValueError(kind)
+    return t

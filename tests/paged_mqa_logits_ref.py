@@ -156,3 +156,27 @@ def exact_case(h, nn, lens, n, max_blocks, share=None, seed=0):
     lens = np.asarray(lens, np.int32)
     want, _ = reference(q, buf, weights, lens, tables, n)
     return _frozen(q, buf, weights, lens, tables, want)
+
+
+@functools.lru_cache(maxsize=None)
+def all_codes_case(h, nn, mirrored=False):
+    """(q [B, nn, h, 128], buf, weights [B nn, h], context_lens [B], tables, N, logits float64 [B nn, N]): mqa_logits_ref.all_codes_operands
+    with its keys packed into pages, twice (two physical copies, in a permuted order, among blocks nobody names); the even sequences
+    share one table, the odd ones the other; every sequence has the whole width as its length, so row r = i next_n + j is token r of the
+    prefill case short of its last next_n - 1 - j keys; kscale = 1"""
+    n = M.MIRROR_N if mirrored else M.CODES_N
+    pages = (n + BLOCK_KV - 1) // BLOCK_KV
+    q, k, weights, _ = M.all_codes_operands(h, mirrored, pages * BLOCK_KV)
+    assert q.shape[0] % nn == 0
+    b = q.shape[0] // nn
+    rng = np.random.default_rng([h, nn, int(mirrored)])
+    num_blocks = 2 * pages + 3
+    where = rng.permutation(num_blocks)[:2 * pages].reshape(2, pages)         # physical block of page p of copy c
+    codes = np.full((num_blocks, BLOCK_KV, D), M.NAN_CODE, np.uint8)             # a block nobody names holds NaN codes
+    codes[where.reshape(-1)] = np.tile(k.reshape(pages, BLOCK_KV, D), (2, 1, 1))
+    buf = pack(codes, np.ones((num_blocks, BLOCK_KV), np.float32))
+    tables = where[np.arange(b) % 2].astype(np.int32)
+    lens = np.full(b, n, np.int32)
+    q = q.reshape(b, nn, h, D).copy()
+    want, _ = reference(q, buf, weights, lens, tables, n)
+    return _frozen(q, buf) + (weights,) + _frozen(lens, tables) + (n,) + _frozen(want)

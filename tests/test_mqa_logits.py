@@ -130,3 +130,61 @@ def test_the_wrapper_refuses_before_any_launch(dga):
     a = _args()
     a[1] = a[1][0]
     refused(a, "kv must be")
+
+
+@pytest.mark.parametrize("h", R.HEADS)
+@pytest.mark.parametrize("mirrored", (False, True), ids=("codes_in_k", "codes_in_q"))
+def test_the_all_codes_case_covers_every_code_exactly(mirrored, h):
+    q, k, kscale, weights, ks, ke, want = R.all_codes_case(h, mirrored)
+    m, n = (R.MIRROR_M, R.MIRROR_N) if mirrored else (R.CODES_M, R.CODES_N)
+    assert q.shape == (m, h, R.D) and k.shape == (n, R.D) and (kscale == 1).all() and R.in_range(ks, ke, n).all()
+    assert len(R.FINITE) == 254 and not np.isnan(R.TABLE[R.FINITE]).any() and np.isnan(R.TABLE[[0x7F, 0xFF]]).all()
+    assert R.TABLE[R.ONE] == 1 and R.TABLE[R.MINUS_ONE] == -1
+    assert not np.isin([0x7F, 0xFF], q).any() and not np.isin([0x7F, 0xFF], k).any()
+    # more than one token run and key block, with ragged ends, in one of the two cases each
+    assert (m > 4 * R.BM and m % R.BM and n == 2 * R.D) if mirrored else (n > R.BN and n % R.BN and m == 2 * R.D)
+    # one weight a token, 1.0, and all 254 codes inside the ranges opposite the unit codes
+    assert ((weights != 0).sum(axis=1) == 1).all() and weights.max() == 1 and len(np.unique(weights.argmax(axis=1))) == h
+    seen = R.all_codes_seen(h, mirrored)
+    assert np.array_equal(seen, R.FINITE) and np.isin(R.SUBNORMAL, seen).all() and 0x80 in seen and len(R.SUBNORMAL) == 14
+    # the expected logits: float32 values, relu of +- the code's value, the 127 magnitudes and nothing else
+    assert np.isfinite(want).all() and np.array_equal(want.astype(np.float32).astype(np.float64), want)
+    magnitudes = np.unique(np.abs(R.TABLE[R.FINITE]))
+    assert len(magnitudes) == 127 and magnitudes[1] == 2.0 ** -9 and magnitudes[-1] == 448 and np.array_equal(np.unique(want), magnitudes)
+    t, col = np.arange(m)[:, None], np.arange(n)[None, :]
+    head = weights.argmax(axis=1)
+    if mirrored:
+        value = np.where(col < R.D, 1, -1) * R.TABLE[q[np.arange(m), head]][:, np.arange(n) % R.D]
+    else:
+        value = np.where(t < R.D, 1, -1) * R.TABLE[k][:, np.arange(m) % R.D].T
+    assert np.array_equal(want, np.maximum(value, 0))
+    assert (value > 0).sum() > m * n // 3 and (value < 0).sum() > m * n // 3
+    # any order of summation gives the same float32: every product but one a logit is a zero, or meets a zero weight
+    mag = R.reference(q, k, kscale, weights, ks, ke)[1]
+    assert np.array_equal(mag, np.abs(value))
+    R.assert_same_values(want.astype(np.float32), want)
+    R.assert_same_values(np.where(want == 0, -0.0, want).astype(np.float32), want)        # a zero of either sign is zero
+
+
+@pytest.mark.parametrize("kind", ("subnormal", "sign"))
+@pytest.mark.parametrize("mirrored", (False, True), ids=("codes_in_k", "codes_in_q"))
+def test_the_value_check_rejects_a_wrong_conversion(mirrored, kind):
+    """what a kernel that flushed one subnormal code to zero, or read -0.5 as +0.5, would return"""
+    q, k, kscale, weights, ks, ke, want = R.all_codes_case(32, mirrored)
+    table = R.broken_table(kind)
+    assert (table != R.TABLE)[R.FINITE].sum() == 1
+    wrong = R.reference(q, k, kscale, weights, ks, ke, table)[0]
+    assert 0 < (wrong != want).sum() < want.size // 50
+    with pytest.raises(AssertionError):
+        R.assert_same_values(wrong.astype(np.float32), want)
+    # on the nine codes of the other exact tests neither fault shows where the code does not occur
+    eq, ek, escale, ew = R.exact_operands(5, 15, 32)
+    if kind == "subnormal":
+        r = R.ranges("full", 5, 15)
+        assert np.array_equal(R.reference(eq, ek, escale, ew, *r, table)[0], R.reference(eq, ek, escale, ew, *r)[0])
+    # and the checker's other refusals: a NaN, a -inf out of place, one float32 step
+    for bad in (np.nan, -np.inf, np.nextafter(np.float32(want[3, 3]), np.float32(1e9))):
+        got = want.astype(np.float32)
+        got[3, 3] = bad
+        with pytest.raises(AssertionError):
+            R.assert_same_values(got, want)

@@ -1,9 +1,10 @@
 """GPU: fp8_mqa_logits against tests/mqa_logits_ref.py.  BM = 64 tokens and BN = 256 keys are the kernel's token run and key block.
 Exactly summable operands must give the float64 reference as values (a zero of either sign is zero, -inf where the reference has it) at
 H = 32 and 64, on a shape of more than one run and block with ragged ends and on shapes below one tile, under every kind of range, into an
-output pre-filled with a NaN pattern; amax-quantised random operands must stay inside the derived bound on every in-range element; a NaN
-code poisons its row or column inside the ranges and nothing else; a captured graph follows rewritten operands and ranges; two calls give
-the same bits and out= matches the allocating call."""
+output pre-filled with a NaN pattern; amax-quantised random operands must stay inside the derived bound on every in-range element; every
+code that is no NaN gives its exact value from either operand; a NaN code of either sign poisons its row or column inside the ranges and
+nothing else; a captured graph follows rewritten operands and ranges; two calls give the same bits and out= matches the allocating
+call."""
 import numpy as np
 import pytest
 import torch
@@ -34,13 +35,7 @@ def _run(dga, q, k, kscale, weights, ks, ke, out=None):
     return out.cpu().numpy()
 
 
-def _same_values(got, want):
-    """got float32 equals the float64 reference as values: -inf exactly where it has it, no NaN, a zero of either sign is zero"""
-    assert got.dtype == np.float32 and got.shape == want.shape
-    assert np.array_equal(np.isneginf(got), np.isneginf(want))
-    assert not np.isnan(got).any()
-    bad = np.argwhere(got.astype(np.float64) != want)
-    assert len(bad) == 0, (len(bad), bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
+_same_values = R.assert_same_values                                  # (tests/mqa_logits_ref.py; tests/test_mqa_logits.py tests it)
 
 
 @pytest.mark.parametrize("h", R.HEADS)
@@ -96,7 +91,18 @@ def test_derived_bound_on_quantised_random_data(dga, h):
 
 
 @pytest.mark.parametrize("h", R.HEADS)
-def test_a_nan_code_poisons_its_row_and_its_column_only(dga, h):
+@pytest.mark.parametrize("mirrored", (False, True), ids=("codes_in_k", "codes_in_q"))
+def test_every_e4m3_code_gives_its_exact_value(dga, mirrored, h):
+    """All 254 codes that are no NaN -- the subnormals and -0 among them -- opposite a unit code, in every dimension: a logit is relu of
+    the code's value or of its negative, exactly, down to 2^-9"""
+    q, k, kscale, weights, ks, ke, want = R.all_codes_case(h, mirrored)
+    assert len(R.all_codes_seen(h, mirrored)) == 254 and len(np.unique(want)) == 127
+    _same_values(_run(dga, q, k, kscale, weights, ks, ke), want)
+
+
+# (the first two ids are those the test had before the negative NaN byte joined it)
+@pytest.mark.parametrize("h,code", [(32, 0x7F), (64, 0x7F), (32, 0xFF), (64, 0xFF)], ids=("32", "64", "32-0xff", "64-0xff"))
+def test_a_nan_code_poisons_its_row_and_its_column_only(dga, h, code):
     m, n = BIG
     q, k, kscale, weights, ks, ke, _ = R.exact_case(m, n, h, "windows")
     clean = _run(dga, q, k, kscale, weights, ks, ke)
@@ -104,7 +110,8 @@ def test_a_nan_code_poisons_its_row_and_its_column_only(dga, h):
     row = int(np.flatnonzero(inside.sum(axis=1) > 40)[3])
     col = int(np.flatnonzero(inside.sum(axis=0) > 2)[-1])
     q2, k2 = q.copy(), k.copy()
-    q2[row, h - 3, 77], k2[col, 5] = R.NAN_CODE, R.NAN_CODE
+    assert code & 0x7F == R.NAN_CODE
+    q2[row, h - 3, 77], k2[col, 5] = code, code
     got = _run(dga, q2, k2, kscale, weights, ks, ke)
     poisoned = np.zeros_like(inside)
     poisoned[row], poisoned[:, col] = True, True

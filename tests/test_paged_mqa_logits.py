@@ -229,3 +229,39 @@ def test_the_writer_wrapper_refuses_before_any_launch(dga):
     refused("got stride\\(0\\) = 8456", kv=torch.zeros((5, 8456), dtype=torch.uint8)[:, :8448])
     refused("slot_mapping must be contiguous int64 \\[4\\]", slots=torch.zeros(4, dtype=torch.int32))
     refused("slot_mapping must be contiguous int64 \\[4\\]", slots=torch.zeros(5, dtype=torch.int64))
+
+
+@pytest.mark.parametrize("nn", (1, 2))
+@pytest.mark.parametrize("mirrored", (False, True), ids=("codes_in_k", "codes_in_q"))
+def test_the_all_codes_case_keeps_every_code_inside_the_row_ends(mirrored, nn):
+    h = 32
+    q, buf, weights, lens, tables, n, want = R.all_codes_case(h, nn, mirrored)
+    fq, fk, fw, head = M.all_codes_operands(h, mirrored)
+    b = q.shape[0]
+    assert np.array_equal(q.reshape(b * nn, h, R.D), fq) and np.array_equal(weights, fw) and (lens == n).all() and n == fk.shape[0]
+    # two tables, shared by the even and by the odd sequences, over disjoint blocks that hold the same keys; the rest holds NaN codes
+    assert np.array_equal(tables[::2], np.tile(tables[0], (len(tables[::2]), 1))) and np.array_equal(tables[1::2], np.tile(tables[1], (b // 2, 1)))
+    assert len(set(tables[0]) | set(tables[1])) == 2 * tables.shape[1] and tables.shape[1] == (n + 63) // 64
+    for row in tables[:2]:
+        kg, sg, ok = R.gather(buf, row, n)
+        assert ok.all() and np.array_equal(kg, fk) and (sg == 1).all()
+    codes, _ = R.unpack(buf)
+    spare = np.setdiff1d(np.arange(buf.shape[0]), tables[:2].reshape(-1))
+    assert len(spare) == 3 and (codes[spare] == M.NAN_CODE).all()
+    # the prefill case's values on the columns below each row's end, -inf behind it
+    flat = M.all_codes_case(h, mirrored)[6]
+    inside = np.arange(n)[None, :] < R.row_ends(lens, nn, n, tables.shape[1])[:, None]
+    assert inside.sum() == b * nn * n - b * (nn - 1) and np.array_equal(want[inside], flat[inside]) and np.isneginf(want[~inside]).all()
+    assert np.array_equal(want[inside].astype(np.float32).astype(np.float64), want[inside])
+    assert np.array_equal(np.unique(want[inside]), np.unique(np.abs(M.TABLE[M.FINITE])))
+    # every code still meets a unit code inside a row's range
+    t, col = np.nonzero(inside)
+    seen = fq[t, head[t], col % R.D] if mirrored else fk[col, t % R.D]
+    assert np.array_equal(np.unique(seen), M.FINITE)
+    # a wrong conversion is rejected here as well
+    fq, fk, fscale, fw, ks, ke, _ = M.all_codes_case(h, mirrored)
+    for kind in ("subnormal", "sign"):                                  # one subnormal code flushed to zero; -0.5 read as +0.5
+        wrong = np.where(inside, M.reference(fq, fk, fscale, fw, ks, ke, M.broken_table(kind))[0], -np.inf)
+        assert 0 < (wrong != want).sum() < want.size // 50
+        with pytest.raises(AssertionError):
+            M.assert_same_values(wrong.astype(np.float32), want)

@@ -4,9 +4,10 @@ sequences share their first block, and the unused table entries hold -1 and 0x7F
 reference as values at H = 32 and 64 and next_n = 1 and 2 -- lengths 0, 1, a page, a page and one, a chunk and one and the whole ragged
 width; one column; a table shorter than the width -- lengths are clamped and an out-of-range entry costs its page only; amax-quantised
 random operands are bit for bit fp8_mqa_logits on the gathered operands and inside its bound; clean_logits=False leaves what it must not
-touch; a padded cache changes nothing; a NaN code poisons its column in every sequence that names the block, or its row; a captured graph
-follows rewritten operands, lengths, tables and cache bytes; the writer stores the quantiser's bytes at their slots and nothing else; and
-one captured graph that writes the new keys and then scores them matches fp8_mqa_logits on the contiguous history."""
+touch; a padded cache changes nothing; every code that is no NaN gives its exact value from either operand, and fp8_mqa_logits' bits; a
+NaN code of either sign poisons its column in every sequence that names the block, or its row; a captured graph follows rewritten
+operands, lengths, tables and cache bytes; the writer stores the quantiser's bytes at their slots and nothing else; and one captured
+graph that writes the new keys and then scores them matches fp8_mqa_logits on the contiguous history."""
 import numpy as np
 import pytest
 import torch
@@ -142,6 +143,29 @@ def test_bit_for_bit_fp8_mqa_logits_on_the_gathered_operands(dga, h, nn):
     assert (err <= bar).all(), (int((err > bar).sum()), float((err / bar).max()))
 
 
+@pytest.mark.parametrize("nn", (1, 2))
+@pytest.mark.parametrize("h", M.HEADS)
+@pytest.mark.parametrize("mirrored", (False, True), ids=("codes_in_k", "codes_in_q"))
+def test_every_e4m3_code_gives_its_exact_value_and_fp8_mqa_logits_bits(dga, mirrored, h, nn):
+    """mqa_logits_ref.all_codes_operands behind two tables that the even and the odd sequences share: the exact value of every code that
+    is no NaN from either operand, and the bits of fp8_mqa_logits on the gathered operands"""
+    q, buf, weights, lens, tables, n, want = R.all_codes_case(h, nn, mirrored)
+    b = q.shape[0]
+    assert len(np.unique(tables, axis=0)) == 2 and np.array_equal(tables[0], tables[2]) and len(np.unique(want[~np.isneginf(want)])) == 127
+    hi = R.row_ends(lens, nn, n, tables.shape[1])
+    assert np.array_equal(~np.isneginf(want), np.arange(n)[None, :] < hi[:, None]) and hi.min() == n - nn + 1
+    got = _run(dga, q, buf, weights, lens, tables, n)
+    _same_values(got, want)
+    # both tables gather the same keys, so one prefill call holds every row
+    kg, sg, ok = R.gather(buf, tables[0], n)
+    kg1, sg1, ok1 = R.gather(buf, tables[1], n)
+    assert ok.all() and ok1.all() and np.array_equal(kg, kg1) and np.array_equal(sg, sg1) and not np.array_equal(tables[0], tables[1])
+    ke = _dev(hi.astype(np.int32))
+    flat = dga.fp8_mqa_logits(_dev(q).view(b * nn, h, R.D).view(torch.float8_e4m3fn), (_dev(kg).view(torch.float8_e4m3fn), _dev(sg)),
+                              _dev(weights), torch.zeros_like(ke), ke, sync=True)
+    assert np.array_equal(_bits(got), _bits(flat.cpu().numpy()))
+
+
 @pytest.mark.parametrize("h", M.HEADS)
 def test_clean_logits_false_touches_nothing_beyond_the_last_page(dga, h):
     nn = 2
@@ -170,8 +194,9 @@ def test_a_padded_cache_gives_the_same_bits(dga, clean):
     assert np.array_equal(_bits(dense), _bits(flat.cpu().numpy()))
 
 
-@pytest.mark.parametrize("h", M.HEADS)
-def test_a_nan_code_poisons_its_column_in_both_sequences_and_its_row_only(dga, h):
+# (the first two ids are those the test had before the cache took the negative NaN byte too)
+@pytest.mark.parametrize("h,code", [(32, 0x7F), (64, 0x7F), (32, 0xFF), (64, 0xFF)], ids=("32", "64", "32-0xff", "64-0xff"))
+def test_a_nan_code_poisons_its_column_in_both_sequences_and_its_row_only(dga, h, code):
     nn = 2
     lens, n, max_blocks, share = _big()
     q, buf, weights, lens_a, tables, want = R.exact_case(h, nn, lens, n, max_blocks, share)
@@ -179,8 +204,9 @@ def test_a_nan_code_poisons_its_column_in_both_sequences_and_its_row_only(dga, h
     inside = ~np.isneginf(want)
     q2, buf2 = q.copy(), buf.copy()
     shared, key = int(tables[3, 0]), 5
-    buf2[shared, key * R.D + 9] = M.NAN_CODE                           # key 5 of the block sequences 3 and 4 both name as page 0
-    q2[4, 1, h - 3, 77] = 0xFF                                          # row 9
+    assert code & 0x7F == M.NAN_CODE
+    buf2[shared, key * R.D + 9] = code                                  # key 5 of the block sequences 3 and 4 both name as page 0
+    q2[4, 1, h - 3, 77] = code ^ 0x80                                   # row 9: the NaN byte of the other sign
     got = _run(dga, q2, buf2, weights, lens_a, tables, n)
     poisoned = np.zeros_like(inside)
     poisoned[6:10, key], poisoned[9] = True, True

@@ -127,3 +127,69 @@ def test_every_refusal_comes_from_the_wrapper(dga):
         with pytest.raises(dga.DGAError) as e:
             call()
         assert "HIP device" in str(e.value)
+
+
+@pytest.mark.parametrize("h", R.ALL_HEADS)
+def test_winners_case_tells_every_head_apart(h):
+    """what the GPU test of the same case relies on"""
+    q, kv, idx, scale, win = R.winners_case(h)
+    assert q.shape == (R.WIN_M, h, R.D_QK) and idx.shape == (R.WIN_M, R.WIN_TOPK) and win.shape == (R.WIN_M, h) and scale == 2.0 ** -3
+    assert np.array_equal(R.bf16_round(q), q) and np.array_equal(R.bf16_round(kv), kv)          # bf16 holds the operands
+    rows, valid = R.rows_of(idx, R.WIN_S)
+    assert (valid.sum(axis=1) == R.WIN_TOPK - R.WIN_INVALID).all() and (idx[~valid] == -1).all() and not valid[:, -3:].any()
+    for t, sc in enumerate(R.scores(q, kv, idx, scale)):
+        top = np.sort(sc, axis=1)
+        assert (top[:, -1] == 512).all() and (top[:, -1] - top[:, -2] >= 256).all()              # the top score, the margin
+        assert set(np.unique(sc)) <= {-512.0, 0.0, 512.0}
+        assert np.array_equal(rows[t][valid[t]][sc.argmax(axis=1)], win[t])                       # the winner is the row it says
+        assert len(set(win[t])) == h                                                              # distinct within the token
+        where = np.flatnonzero(np.isin(rows[t], win[t]) & valid[t])
+        assert len(where) == h and len(set(where // R.TILE)) == R.WIN_TOPK // R.TILE >= 3          # once each, in every tile
+    assert len({tuple(w) for w in win}) == R.WIN_M                                               # a fresh map per token
+    assert len(np.unique(R.winner_bits(kv, win).reshape(-1, R.D_V), axis=0)) == len(np.unique(win))   # distinct rows, distinct bits
+    # the float64 reference is the winner's row, and its lse is 512
+    ref = R.reference(q, kv, idx, scale)
+    assert np.array_equal(ref["out"].astype(np.float32), kv[win][:, :, :R.D_V]) and np.array_equal(ref["lse"], np.full((R.WIN_M, h), 512.0))
+    assert R.heads_off_their_winner(R.winner_bits(kv, win), kv, win) == []
+
+
+def test_the_winner_check_rejects_two_swapped_heads():
+    for h in (16, 80):
+        q, kv, idx, scale, win = R.winners_case(h)
+        bits = R.winner_bits(kv, win)
+        bad = bits.copy()
+        bad[1, [3, h - 2]] = bits[1, [h - 2, 3]]                        # two heads of one token swapped: a head in the wrong lane or wave
+        assert R.heads_off_their_winner(bad, kv, win) == [(1, 3), (1, h - 2)]
+        bad = bits.copy()
+        bad[2, 5, 511] ^= 0x8000                                        # one sign bit (the -0 the float64 out would round to)
+        assert R.heads_off_their_winner(bad, kv, win) == [(2, 5)]
+
+
+def test_the_peaked_cases_keep_every_weight_in_fp32s_normal_range():
+    for h in R.PEAK_HEADS:
+        q, kv, idx = R.random_case(h)
+        flat = R.score_spread(q, kv, idx, R.SCALE4)
+        for sign in (1, -1):
+            spread = R.score_spread(q, kv, idx, sign * R.PEAK * R.SCALE4)
+            assert np.isclose(spread, R.PEAK * flat) and 20 < spread < R.SPREAD_MAX, (h, sign, spread)
+        for order in ("ascending", "descending"):                      # the order changes the list, not the set
+            assert R.score_spread(q, kv, R.ordered(q, kv, idx, order), R.PEAK * R.SCALE4) == R.score_spread(q, kv, idx, R.PEAK * R.SCALE4)
+    # every head count's list has the counts the GPU test asserts
+    for h in R.ALL_HEADS:
+        _, _, idx = R.random_case(h)
+        assert R.rows_of(idx, R.S4)[1].sum(axis=1).tolist() == [318, 298, 318, 318, 318]
+    q, kv, idx = R.long_case(16)
+    rows, valid = R.rows_of(idx, kv.shape[0])
+    assert idx.shape == (2, 2048) and valid.all() and all(len(set(r)) == 2048 for r in rows) and R.score_spread(q, kv, idx, R.SCALE4) < R.SPREAD_MAX
+
+
+def test_the_int32_extremes_name_the_rows_they_should():
+    s = 40
+    idx, off, want = R.extremes_case(s)
+    assert idx.dtype == np.int32 and off.dtype == np.int32 and off.tolist() == [-(2 ** 31 - 1) + 5, 2 ** 31 - 1, -2 ** 31, 0, 7]
+    rows, valid = R.rows_of(idx, s, off)
+    assert [rows[t][valid[t]].tolist() for t in range(5)] == want
+    # every extreme the case is about is in it; the sums of tokens 1 and 2 leave the int32 range
+    assert idx[0, 0] == R.INT_MAX and rows[0, 0] == 5 and (idx == R.INT_MIN).any(axis=1).all()
+    assert idx[1, 0] == R.INT_MAX and rows[1, 0] == 2 ** 32 - 2 and idx[2, 2] == 5 and rows[2, 39] == -2 ** 32 and not valid[1:3].any()
+    assert [len(w) for w in want] == [4, 0, 0, 8, 2]                    # powers of two where there is a count

@@ -5,9 +5,11 @@ RNE_bf16(sum v / count) bit for bit: gather, masking and duplicates are checked 
 gives its value row bit for bit wherever it stands in the list.  Every kind of invalid position, the offsets, a strided kv whose every
 unselected row and every column >= 576 is NaN, and an index list that is a slice of a wider tensor go through the same check; normal
 samples in three orders of the list stay inside the derived bound on every element; a NaN poisons what selects it and nothing else; a
-captured graph follows rewritten operands; two calls give the same bytes."""
-import functools
-
+captured graph follows rewritten operands; two calls give the same bytes.  The uniform, random-data and two-runs tests run at every
+multiple of 16 heads up to 128, and so does a case in which every head of every token has a winning row of its own, which tells a head in
+the wrong lane group, wave or block apart exactly.  The derived bound is also held on peaked and on negated scores (four times the scale,
+plus and minus, in the three orders) and over 64 tiles; a zero scale gives the bits of q = 0; a cache of one row and indices and offsets
+at the ends of the int32 range are exact under q = 0."""
 import numpy as np
 import pytest
 import torch
@@ -16,7 +18,8 @@ import sparse_mla_ref as R
 
 pytestmark = pytest.mark.gpu
 
-HEADS = (16, 64, 128)
+HEADS = (16, 64, 128)                                                 # one wave of a workgroup, a whole workgroup, two
+ALL_HEADS = R.ALL_HEADS                                               # and every count between: a partly filled first or second block
 NAN_FILL = 0x7FC12345
 NAN_FILL16 = 0x7FC5
 
@@ -88,7 +91,7 @@ def _pow2(n):
 
 # ---- 1. exact, uniform ------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("h", HEADS)
+@pytest.mark.parametrize("h", ALL_HEADS)
 def test_uniform_weights_are_exact_at_power_of_two_counts(dga, h):
     s, topk = 200, 192
     rng = np.random.default_rng(h)
@@ -200,44 +203,17 @@ def test_masking_and_layout(dga, h, topk, layout):
 
 # ---- 4. the bound on random data -------------------------------------------------------------------------------------------------
 
-M4, S4, TOPK4, SCALE4 = 5, 700, 320, 576 ** -0.5
-
-
-@functools.lru_cache(maxsize=None)
-def _random_case(h):
-    """normal samples rounded to bf16 and an index list with a few invalid positions (read-only once built)"""
-    g = torch.Generator(device="cpu").manual_seed(31 + h)
-    q = torch.randn((M4, h, R.D_QK), generator=g).to(torch.bfloat16).float().numpy()
-    kv = torch.randn((S4, R.D_QK), generator=g).to(torch.bfloat16).float().numpy()
-    rng = np.random.default_rng(h)
-    idx = np.stack([rng.permutation(S4)[:TOPK4] for _ in range(M4)]).astype(np.int32)
-    idx[:, 17], idx[:, 200], idx[1, 300:] = -1, S4 + 3, -1
-    idx[2, 40] = idx[2, 41]                                            # a duplicate
-    for a in (q, kv, idx):
-        a.setflags(write=False)
-    return q, kv, idx
-
-
-def _ordered(q, kv, idx, order):
-    """the positions of every token's list reordered: as drawn, or by the score of head 0 (invalid positions keep to the end)"""
-    if order == "random":
-        return idx
-    out = idx.copy()
-    rows, valid = R.rows_of(idx, kv.shape[0])
-    for t in range(idx.shape[0]):
-        sc = kv[np.where(valid[t], rows[t], 0)].astype(np.float64) @ q[t, 0].astype(np.float64)
-        sc = np.where(valid[t], sc if order == "ascending" else -sc, np.inf)
-        out[t] = idx[t][np.argsort(sc, kind="stable")]
-    return out
+M4, S4, TOPK4, SCALE4 = R.M4, R.S4, R.TOPK4, R.SCALE4
+_random_case, _ordered = R.random_case, R.ordered               # (the generators: tests/sparse_mla_ref.py)
 
 
 @pytest.mark.parametrize("order", ("random", "ascending", "descending"))
-@pytest.mark.parametrize("h", HEADS)
+@pytest.mark.parametrize("h", ALL_HEADS)
 def test_derived_bound_on_random_data(dga, h, order):
     q, kv, base = _random_case(h)
     idx = _ordered(q, kv, base, order)
     ref = R.reference(q, kv, idx, SCALE4)
-    assert ref["count"].tolist() == [318, 298, 318, 318, 318]
+    assert ref["count"].tolist() == [318, 298, 318, 318, 318] == R.rows_of(base, S4)[1].sum(axis=1).tolist()
     worst, worst_lse = _check(_run(dga, _bf16(q), _bf16(kv), torch.from_numpy(idx.copy()).cuda(), SCALE4), ref, SCALE4, TOPK4)
     print("Hq=%d %s: worst error / bound = %.4f (out), %.4f (lse)" % (h, order, worst, worst_lse))
 
@@ -304,7 +280,7 @@ def test_a_captured_graph_follows_new_operands(dga):
 
 # ---- 7. outputs and determinism ---------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("h", HEADS)
+@pytest.mark.parametrize("h", ALL_HEADS)
 def test_outputs_in_place_and_two_runs_alike(dga, h):
     q, kv, idx = _random_case(h)
     q_d, kv_d, idx_d = _bf16(q), _bf16(kv), torch.from_numpy(idx.copy()).cuda()
@@ -321,3 +297,108 @@ def test_outputs_in_place_and_two_runs_alike(dga, h):
     # M == 0: nothing to launch, empty outputs
     none = dga.sparse_mla_fwd(q_d[:0], kv_d, idx_d[:0], SCALE4, sync=True)
     assert none[0].shape == (0, h, R.D_V) and none[1].shape == (0, h)
+
+
+# ---- 8. every head count, the heads told apart --------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("h", ALL_HEADS)
+def test_every_head_gets_its_own_winner_at_every_head_count(dga, h):
+    """A partly filled first (32, 48) or second (80, 96, 112) head block: which waves compute, which rows of the q image are filled and
+    how many heads the second block owns all follow Hq.  Every head of every token has a winner of its own, so a head in the wrong
+    lane group, wave or block shows as another row's bits."""
+    q, kv, idx, scale, win = R.winners_case(h)
+    ref = R.reference(q, kv, idx, scale)
+    assert np.array_equal(ref["lse"], np.full((R.WIN_M, h), 512.0))
+    out, bits, lse = got = _run(dga, _bf16(q), _bf16(kv), torch.from_numpy(idx.copy()).cuda(), scale)
+    assert R.heads_off_their_winner(bits, kv, win) == []
+    _check(got, ref, scale, R.WIN_TOPK, out_bound=False)               # (lse within its bound of 512; out is exact above)
+
+
+# ---- 9. the softmax off the flat distributions ------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("order", ("random", "ascending", "descending"))
+@pytest.mark.parametrize("sign", (1, -1), ids=("plus", "minus"))
+@pytest.mark.parametrize("h", R.PEAK_HEADS)
+def test_derived_bound_on_peaked_and_negated_scores(dga, h, sign, order):
+    """R.PEAK times the scale: a few positions hold nearly all the weight, the running maximum moves by large steps when the list
+    ascends and alpha becomes tiny; a negative scale turns the order of the scores round.  (test_sparse_mla.py: the spread stays below
+    60 nat, every weight of the reference is a normal fp32 number relative to the largest.)"""
+    scale = sign * R.PEAK * SCALE4
+    q, kv, base = _random_case(h)
+    idx = _ordered(q, kv, base, order)
+    ref = R.reference(q, kv, idx, scale)
+    worst, worst_lse = _check(_run(dga, _bf16(q), _bf16(kv), torch.from_numpy(idx.copy()).cuda(), scale), ref, scale, TOPK4)
+    print("Hq=%d scale %+d SCALE4 %s: worst error / bound = %.4f (out), %.4f (lse)" % (h, sign * R.PEAK, order, worst, worst_lse))
+
+
+@pytest.mark.parametrize("h", ALL_HEADS)
+def test_a_zero_scale_is_q_equal_to_zero_bit_for_bit(dga, h):
+    s, topk = 200, 192
+    rng = np.random.default_rng(300 + h)
+    idx = np.full((4, topk), -1, np.int32)
+    for t, count in enumerate((1, 2, 64, 128)):
+        idx[t, np.sort(rng.choice(topk, count, replace=False))] = rng.integers(0, s, count)
+    kv = _int_kv(s, R.D_QK, 6)
+    q = _random_case(h)[0][:4]
+    zero = np.zeros_like(q)
+    idx_d, kv_d = torch.from_numpy(idx).cuda(), _bf16(kv)
+    ref = R.reference(q, kv, idx, 0.0)
+    assert ref["count"].tolist() == [1, 2, 64, 128] and np.array_equal(ref["out"], R.reference(zero, kv, idx, 0.3)["out"])
+    base = _run(dga, _bf16(zero), kv_d, idx_d, 0.3)
+    for scale in (0.0, -0.0):
+        got = _run(dga, _bf16(q), kv_d, idx_d, scale)
+        _check(got, ref, scale, topk, exact_rows=range(4))
+        assert np.array_equal(got[1], base[1]) and np.array_equal(got[2].view(np.uint32), base[2].view(np.uint32))
+
+
+@pytest.mark.parametrize("h", (16, 128))
+def test_derived_bound_over_64_tiles(dga, h):
+    q, kv, idx = R.long_case(h)
+    topk = idx.shape[1]
+    assert topk == 2048 == 64 * R.TILE
+    ref = R.reference(q, kv, idx, SCALE4)
+    assert ref["count"].tolist() == [topk, topk]
+    q_d, kv_d, idx_d = _bf16(q), _bf16(kv), torch.from_numpy(idx.copy()).cuda()
+    a = _run(dga, q_d, kv_d, idx_d, SCALE4)
+    worst, worst_lse = _check(a, ref, SCALE4, topk)
+    print("Hq=%d topk=2048: worst error / bound = %.4f (out), %.4f (lse)" % (h, worst, worst_lse))
+    b = _run(dga, q_d, kv_d, idx_d, SCALE4)
+    assert np.array_equal(a[1], b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32))
+
+
+# ---- 10. the ends of the addressing ------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("layout", ("plain", "three"))
+@pytest.mark.parametrize("h", (16, 80))
+def test_a_cache_of_one_row(dga, h, layout):
+    topk = 70
+    kv = _int_kv(1, R.D_QK, 12)
+    idx = np.full((3, topk), -1, np.int32)
+    idx[0, 41] = 0                                                      # one valid position, in the second tile
+    idx[1, 3:67] = 0                                                    # 64 of them, over three tiles
+    idx[1, [0, 1, 67, 68]] = [1, 2 ** 31 - 1, -2 ** 31, 1]              # anything else is out of a range of one row
+    idx[2, ::2] = 1                                                     # nothing valid
+    kv_d = _bf16(kv) if layout == "plain" else _bf16(kv).view(1, 1, R.D_QK)
+    zero = np.zeros((3, h, R.D_QK), np.float32)
+    ref = R.reference(zero, kv, idx, 0.5)
+    assert ref["count"].tolist() == [1, 64, 0]
+    out, bits, lse = got = _run(dga, _bf16(zero), kv_d, torch.from_numpy(idx).cuda(), 0.5)
+    _check(got, ref, 0.5, topk, exact_rows=range(3))
+    assert np.array_equal(bits[:2], np.broadcast_to(R.bf16_bits(kv[0, :R.D_V]), (2, h, R.D_V)))     # the row itself, both times
+    # one token as well: M = 1, S = 1
+    got = _run(dga, _bf16(zero[:1]), kv_d, torch.from_numpy(idx[1:2].copy()).cuda(), 0.5)
+    _check(got, {k: v[1:2] for k, v in ref.items()}, 0.5, topk, exact_rows=range(1))
+
+
+@pytest.mark.parametrize("h", (16, 80))
+def test_indices_and_offsets_at_the_ends_of_int32(dga, h):
+    s = 40
+    idx, off, want = R.extremes_case(s)
+    keep = _selected(idx, s, off)
+    assert sorted(set(sum(want, []))) == keep.tolist() and len(keep) < s // 2
+    kv = _int_kv(s, R.D_QK, 13, keep)                                   # every row nobody selects is NaN
+    zero = np.zeros((5, h, R.D_QK), np.float32)
+    ref = R.reference(zero, kv, idx, 0.25, off)
+    assert ref["count"].tolist() == [4, 0, 0, 8, 2]
+    got = _run(dga, _bf16(zero), _bf16(kv), torch.from_numpy(idx).cuda(), 0.25, torch.from_numpy(off).cuda())
+    _check(got, ref, 0.25, idx.shape[1], exact_rows=range(5))
