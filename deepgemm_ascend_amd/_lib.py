@@ -194,6 +194,10 @@ SIGNATURES = {
                                  c_int, c_int64, c_void_p, c_void_p]),
     "dga_sparse_mla_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_double, c_int,
                                    c_void_p, c_void_p, c_void_p]),
+    "dga_sparse_mla_fwd_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                       c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                             c_void_p, c_int, c_void_p]),
     "dga_catlass_dynamic_matmul_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "dga_catlass_dynamic_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                            c_void_p]),

@@ -2056,6 +2056,106 @@ def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_
     return out, lse
 
 
+SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values
+
+
+def _mla_fp8_cache(kv_cache: torch.Tensor):
+    """Sparse MLA's paged fp8 latent cache, checked: uint8 [num_blocks, page_size, 1, 656] (stride(3) == 1, stride(1) == 656, blocks
+    stride(0) >= 656 page_size bytes apart) or [S, 656] (stride(1) == 1, rows stride(0) >= 656 apart: page_size 1), the stride a multiple
+    of 16, the base 16-byte aligned, 1 <= S < 2^31.  Returns (num_blocks, page_size, block stride)."""
+    row = SPARSE_MLA_FP8_ROW_BYTES
+    _require(kv_cache.dtype == torch.uint8, "kv_cache must be uint8, got %s", kv_cache.dtype)
+    _require(kv_cache.dim() in (2, 4) and kv_cache.shape[-1] == row and (kv_cache.dim() == 2 or kv_cache.shape[2] == 1),
+             "kv_cache must be [num_blocks, page_size, 1, %d] or [S, %d], got %s", row, row, list(kv_cache.shape))
+    nb, page = kv_cache.shape[0], (kv_cache.shape[1] if kv_cache.dim() == 4 else 1)
+    _require(nb >= 1 and page >= 1, "kv_cache must have at least one row")
+    _require(kv_cache.stride(-1) == 1 and (kv_cache.dim() == 2 or page == 1 or kv_cache.stride(1) == row),
+             "kv_cache must have contiguous rows, %d bytes apart inside a block (stride(1) == %d)", row, row)
+    stride = kv_cache.stride(0) if nb > 1 else page * row
+    _require(stride >= page * row and stride % 16 == 0,
+             "kv_cache blocks must be at least %d bytes apart and a multiple of 16, got stride(0) = %d", page * row, stride)
+    _require(nb * page < 1 << 31, "kv_cache must have fewer than 2^31 rows, got %d x %d", nb, page)
+    _require(kv_cache.data_ptr() % 16 == 0, "kv_cache must be 16-byte aligned")
+    return nb, page, stride
+
+
+def sparse_mla_fwd_fp8(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
+                       index_offsets: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+                       sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sparse_mla_fwd over a paged fp8 latent cache, read in place (dga_sparse_mla_fwd_fp8).  kv_cache uint8
+    [num_blocks, page_size, 1, 656] (stride(3) == 1, stride(1) == 656, stride(0) >= 656 page_size and a multiple of 16, any page_size >= 1)
+    or [S, 656] (stride(1) == 1, stride(0) >= 656 and a multiple of 16), the base 16-byte aligned, 1 <= S = num_blocks page_size < 2^31.
+    Row r lives at (r // page_size) stride(0) + (r % page_size) 656 and holds, in FlashMLA's layout of this model's cache: bytes 0 .. 511
+    the 512 e4m3fn codes of the latent part, bytes 512 .. 527 four float32 scales (one per 128 codes), bytes 528 .. 655 the 64 rope values
+    in bfloat16 (mla_kv_cast_to_fp8_paged writes it).  With page_size 64 and a block table, indexer_topk(block_tables=..., page_size=64)
+    emits exactly these row numbers.  The value of a row is defined on the bits:
+    deq[r, d] = RNE_bf16(fl32(e4m3(code[r, d]) scale[r, d // 128])) for d < 512 -- in torch
+    (codes.view(torch.float8_e4m3fn).float() * scales.repeat_interleave(128, -1)).to(torch.bfloat16) -- and the rope values as stored.
+    The result is sparse_mla_fwd(q, deq, ...)'s: out and lse byte for byte wherever that is not NaN, NaN in exactly the same elements;
+    q, indices, index_offsets, out, lse, the validity rule, the arithmetic and its bounds are that function's.  No byte of an unselected
+    row and no byte between a block's last row and the next block is read.  One launch, capturable; M == 0 returns without one."""
+    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
+             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
+    m, heads = q.shape[0], q.shape[1]
+    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
+             SPARSE_MLA_MAX_HEADS, heads)
+    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
+    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    nb, page, stride = _mla_fp8_cache(kv_cache)
+    _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
+    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
+             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
+    topk = indices.shape[-1]
+    idx_stride = indices.stride(0) if m > 1 else topk
+    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
+    if index_offsets is not None:
+        _want(index_offsets, "index_offsets", torch.int32, (m,))
+    if out is None:
+        out = torch.empty((m, heads, SPARSE_MLA_D_V), dtype=torch.bfloat16, device=q.device)
+    else:
+        _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    if lse is None:
+        lse = torch.empty((m, heads), dtype=torch.float32, device=q.device)
+    else:
+        _want(lse, "lse", torch.float32, (m, heads))
+    # (M == 0: the C entry returns before any launch)
+    _launch("sparse_mla_fwd_fp8", (q, kv_cache, indices, index_offsets, out, lse), lambda L, stream: L.dga_sparse_mla_fwd_fp8(
+        q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk, idx_stride,
+        float(sm_scale), _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
+    return out, lse
+
+
+def mla_kv_cast_to_fp8_paged(kv_c: torch.Tensor, k_pe: torch.Tensor, kv_cache: torch.Tensor, slot_mapping: torch.Tensor,
+                             use_ue8m0: bool = False, sync: bool = False) -> torch.Tensor:
+    """The writer of sparse_mla_fwd_fp8's cache (dga_cast_mla_kv_to_fp8_paged).  kv_c [T, 512] and k_pe [T, 64], float32 / bfloat16 /
+    float16 and both of one dtype, each with a contiguous last dimension and a row stride of its own, 16-byte aligned with rows a multiple
+    of 16 bytes apart (x[:, :512] and x[:, 512:] of one [T, 576] tensor are valid); kv_cache as there; slot_mapping int64 [T] on the device.
+    For every t with 0 <= slot_mapping[t] < S, row slot receives the 512 codes and 4 scales of per_token_cast_to_fp8(kv_c,
+    use_ue8m0=...) row t, byte for byte, and the rope part RNE_bf16(k_pe[t]) (bfloat16 input: its bits).  Any other slot value (engines pad
+    with -1) skips the token, whose inputs are not read; no other byte of the cache is touched.  Duplicate valid slots in one call are the
+    caller's error.  T == 0 returns without a launch.  Returns kv_cache."""
+    _require(kv_c.dim() == 2 and kv_c.shape[1] == SPARSE_MLA_D_V, "kv_c must be a [T, %d] tensor", SPARSE_MLA_D_V)
+    t = kv_c.shape[0]
+    _require(k_pe.dim() == 2 and k_pe.shape == (t, SPARSE_MLA_D_QK - SPARSE_MLA_D_V), "k_pe must be a [T, %d] tensor with kv_c's T",
+             SPARSE_MLA_D_QK - SPARSE_MLA_D_V)
+    _require(kv_c.dtype in _CAST_DT, "kv_c must be float32, bfloat16 or float16")
+    _require(k_pe.dtype == kv_c.dtype, "kv_c and k_pe must have one dtype, got %s and %s", kv_c.dtype, k_pe.dtype)
+    size = kv_c.element_size()
+    strides = []
+    for x, what in ((kv_c, "kv_c"), (k_pe, "k_pe")):
+        ld = x.stride(0) if t > 1 else x.shape[1]
+        _require(x.stride(1) == 1 and ld >= x.shape[1] and ld * size % 16 == 0 and x.data_ptr() % 16 == 0,
+                 "%s must have a contiguous last dimension, a 16-byte aligned base and rows a multiple of 16 bytes apart", what)
+        strides.append(ld)
+    nb, page, stride = _mla_fp8_cache(kv_cache)
+    _want(slot_mapping, "slot_mapping", torch.int64, (t,))
+    # (T == 0: the C entry returns before any launch)
+    _launch("mla_kv_cast_to_fp8_paged", (kv_c, k_pe, kv_cache, slot_mapping), lambda L, stream: L.dga_cast_mla_kv_to_fp8_paged(
+        kv_c.data_ptr(), strides[0], k_pe.data_ptr(), strides[1], _CAST_DT[kv_c.dtype], t, kv_cache.data_ptr(), nb, page, stride,
+        slot_mapping.data_ptr(), _lib.CAST_UE8M0 if use_ue8m0 else 0, stream), sync)
+    return kv_cache
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

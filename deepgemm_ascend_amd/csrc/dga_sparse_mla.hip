@@ -24,6 +24,16 @@
 // Nothing is dereferenced for an invalid position, no kv row outside the list and no column >= 576 is read.
 // Workgroup w of the grid takes the logical block (w % 8) chunk + w / 8, chunk = ceil(blocks / 8): workgroups go to the eight XCDs in
 // turn, so consecutive tokens -- which select largely the same rows -- share one XCD's L2 (DGA_SPARSE_MLA_LINEAR_GRID turns it off).
+//   dga_sparse_mla_fwd_fp8   the same over a paged fp8 latent cache: rows of DGA_SPARSE_MLA_FP8_ROW_BYTES = 656 bytes -- 512 e4m3fn codes,
+//                        4 fp32 scales (one per 128 codes), 64 bf16 rope values -- row r at (r / page_size) block_stride + (r % page_size) 656
+// One kernel text, instantiated on the cache (SmlaBf16Rows, SmlaFp8Rows): only the gather differs.  Of an fp8 row a thread loads the 16
+// bytes of scales, four 16-byte code chunks (chunks tid % 8 + 8 c, chunk c in scale group c) and one 16-byte rope chunk -- 6 staged uint4
+// for 9 -- and dequantises its 64 codes in 32 units of two, one unit behind each MFMA of O^T += V^T P^T, where its four vector
+// instructions issue while the MFMA runs: v_cvt_pk_f32_fp8 (exact), two v_mul_f32 by the group's scale, v_cvt_pk_bf16_f32 (RNE).  The staged
+// registers grow from 6 to 9 uint4 as the units replace codes by bf16, never beyond the bf16 gather's 9.  What goes to LDS at the top of the
+// loop is the row's dequantised image, deq[r, d] = RNE_bf16(fl32(e4m3(code) scale)), in the bf16 gather's format: from the barrier on the
+// two kernels run the same instructions on the same bytes, so dga_sparse_mla_fwd_fp8(cache) is dga_sparse_mla_fwd(deq(cache)) bit for bit.
+// ("Sparse MLA attention over a paged fp8 latent cache", has the schedules that were measured.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,13 +61,142 @@ typedef __bf16 smla_v4bf __attribute__((ext_vector_type(4)));
 typedef short smla_v4s __attribute__((ext_vector_type(4)));
 typedef short smla_v8s __attribute__((ext_vector_type(8)));
 typedef uint32_t smla_v4u __attribute__((ext_vector_type(4)));
+typedef float smla_v2f __attribute__((ext_vector_type(2)));
+typedef __bf16 smla_v2bf __attribute__((ext_vector_type(2)));
 
-__global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint16_t *__restrict__ q, const uint16_t *__restrict__ kv,
+constexpr int SMLA_FP8_ROW = DGA_SPARSE_MLA_FP8_ROW_BYTES;   // 656: 512 codes, 4 fp32 scales, 64 bf16
+constexpr int SMLA_FP8_SLICES = 8;                           // 16-byte chunks of bf16 a thread makes of its 64 codes per tile
+static_assert(SMLA_FP8_ROW == SMLA_DV + 16 + 2 * (SMLA_D - SMLA_DV) && SMLA_FP8_ROW % 16 == 0 && SMLA_FP8_SLICES == SMLA_CTILES / 4 &&
+              SMLA_FP8_SLICES + 1 == SMLA_STAGE, "the fp8 row, and eight 16-byte chunks of bf16 from its codes");
+
+// What the kernel gathers from.  A cache says where thread gsub (of the eight a row has) starts in row r, what it loads from there
+// (RAW uint4, all in flight together), and where chunk c of the nine it ends up with stands in the 1184-byte LDS row.
+// bf16 rows: the nine chunks gsub + 8 c of the row as they are.
+struct SmlaBf16Rows {
+    static constexpr bool FP8 = false;
+    static constexpr int RAW = SMLA_STAGE;
+    const uint16_t *kv;
+    int64_t kv_stride, s_rows;
+    static __device__ __forceinline__ SmlaBf16Rows make(const void *kv, int64_t stride, int64_t s_rows, int, int)
+    {
+        return SmlaBf16Rows{static_cast<const uint16_t *>(kv), stride, s_rows};
+    }
+    __device__ __forceinline__ const unsigned char *at(int64_t r, int gsub) const
+    {
+        return reinterpret_cast<const unsigned char *>(kv + r * kv_stride + gsub * 8);
+    }
+    static __device__ __forceinline__ void load(const unsigned char *p, int gsub, uint4 (&v)[RAW])
+    {
+#pragma unroll
+        for (int c = 0; c < RAW; ++c) v[c] = *reinterpret_cast<const uint4 *>(p + 128 * c);
+    }
+    static __device__ __forceinline__ int lds_at(int c, int gsub) { return gsub * 16 + 128 * c; }
+};
+// fp8 rows: v[0 .. 3] the code chunks gsub + 8 c (bytes 16 gsub + 128 c of the row: chunk c lies in scale group c), v[4] the four
+// scales (bytes 512 .. 527), v[5] the rope chunk gsub (bytes 528 + 16 gsub ..).  The codes 8 h .. 8 h + 7 of chunk c, image chunk 2 c + h,
+// become 16 bytes of bf16 at byte 32 (gsub + 8 c) + 16 h of the LDS row; the rope chunk goes where the bf16 gather puts its ninth.
+struct SmlaFp8Rows {
+    static constexpr bool FP8 = true;
+    static constexpr int RAW = 6;
+    const unsigned char *kv;
+    int64_t block_stride, s_rows;
+    int page_size, page_shift;                               // page_shift >= 0: page_size = 1 << page_shift
+    static __device__ __forceinline__ SmlaFp8Rows make(const void *kv, int64_t stride, int64_t s_rows, int page_size, int page_shift)
+    {
+        return SmlaFp8Rows{static_cast<const unsigned char *>(kv), stride, s_rows, page_size, page_shift};
+    }
+    __device__ __forceinline__ const unsigned char *at(int64_t r, int gsub) const
+    {
+        const uint32_t rr = (uint32_t)r;                     // (0 <= r < s_rows < 2^31)
+        const uint32_t blk = page_shift >= 0 ? rr >> page_shift : rr / (uint32_t)page_size;
+        const uint32_t in = rr - blk * (uint32_t)page_size;
+        return kv + (int64_t)blk * block_stride + (int64_t)in * SMLA_FP8_ROW + gsub * 16;
+    }
+    static __device__ __forceinline__ void load(const unsigned char *p, int gsub, uint4 (&v)[RAW])
+    {
+        v[4] = *reinterpret_cast<const uint4 *>(p - gsub * 16 + SMLA_DV);   // (first: the first slice needs them beside chunk 0)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = *reinterpret_cast<const uint4 *>(p + 128 * c);
+        v[5] = *reinterpret_cast<const uint4 *>(p + SMLA_DV + 16);
+    }
+    static __device__ __forceinline__ int lds_at(int c, int gsub)
+    {
+        return c < SMLA_FP8_SLICES ? gsub * 32 + 256 * (c >> 1) + 16 * (c & 1) : 2 * SMLA_DV + gsub * 16;
+    }
+};
+
+// two codes' exact fp32 values times the scale of their group, each product rounded once to bf16 (RNE): one dword of the image
+__device__ __forceinline__ uint32_t smla_deq2(smla_v2f v, float s)
+{
+    const float a = v[0] * s, b = v[1] * s;                  // (two v_mul_f32: packed fp32 arithmetic is a loss beside MFMAs)
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector((smla_v2f{a, b}), smla_v2bf));
+}
+// Unit u of the 32 a thread has per tile: the codes 2 (u & 1), 2 (u & 1) + 1 of dword (u >> 1) & 3 of code chunk u >> 3 -> one dword of the
+// bf16 image, four vector instructions: v_cvt_pk_f32_fp8 (one half of the dword), two v_mul_f32 by the group's scale, v_cvt_pk_bf16_f32.
+// PIN: the code dword goes in (once, at its even unit; the odd one takes it from `pinned`) and the bf16 dword comes out through empty asm
+// statements, which keep the unit where it is written.  Without them the compiler sees the same conversions on both sides of the loop's
+// `computes` branch, hoists the fp8 -> fp32 half above the branch -- straight behind the loads it then waits for -- and sinks the bf16
+// half below the join, parking 64 fp32 products in AGPRs.
+constexpr int SMLA_FP8_UNITS = 4 * SMLA_FP8_SLICES;
+template <bool PIN>
+__device__ __forceinline__ void smla_fp8_unit(int u, const uint4 (&raw)[SmlaFp8Rows::RAW], uint32_t (&pinned)[SMLA_FP8_UNITS / 2],
+                                              uint4 (&staged)[SMLA_STAGE])
+{
+    const int c = u >> 3, d = (u >> 1) & 3;
+    const float s = __uint_as_float(c == 0 ? raw[4].x : c == 1 ? raw[4].y : c == 2 ? raw[4].z : raw[4].w);
+    if (!(u & 1)) {
+        uint32_t w = d == 0 ? raw[c].x : d == 1 ? raw[c].y : d == 2 ? raw[c].z : raw[c].w;
+        if (PIN) asm volatile("" : "+v"(w));
+        pinned[u >> 1] = w;
+    }
+    const uint32_t w = pinned[u >> 1];
+    uint32_t o = smla_deq2((u & 1) ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), s);
+    if (PIN) asm volatile("" : "+v"(o));
+    uint4 &dst = staged[2 * c + (d >> 1)];
+    const int at = 2 * (d & 1) + (u & 1);
+    if (at == 0) dst.x = o;
+    else if (at == 1) dst.y = o;
+    else if (at == 2) dst.z = o;
+    else dst.w = o;
+}
+// The units are dealt evenly over the O loop's MFMAs 4 SMLA_FP8_FIRST_GROUP .. 31, one (or more) behind each: the number done before MFMA mf
+#ifndef DGA_SMLA_FP8_FIRST_GROUP
+#define DGA_SMLA_FP8_FIRST_GROUP 0
+#endif
+constexpr int SMLA_FP8_FIRST_MFMA = 4 * (DGA_SMLA_FP8_FIRST_GROUP);
+static_assert(SMLA_FP8_FIRST_MFMA >= 0 && SMLA_FP8_FIRST_MFMA < SMLA_CTILES, "the units start inside the O loop");
+__device__ __forceinline__ constexpr int smla_units_before(int mf)
+{
+    return mf <= SMLA_FP8_FIRST_MFMA ? 0 : (mf - SMLA_FP8_FIRST_MFMA) * SMLA_FP8_UNITS / (SMLA_CTILES - SMLA_FP8_FIRST_MFMA);
+}
+// what a thread has loaded -> the nine chunks it writes to LDS, units [first, last) of them; the ninth chunk comes with the last unit
+template <typename Cache, bool PIN = false>
+__device__ __forceinline__ void smla_stage(int first, int last, const uint4 (&raw)[Cache::RAW], uint32_t (&pinned)[SMLA_FP8_UNITS / 2],
+                                           uint4 (&staged)[SMLA_STAGE])
+{
+    if constexpr (Cache::FP8) {
+#pragma unroll
+        for (int u = first; u < last; ++u) smla_fp8_unit<PIN>(u, raw, pinned, staged);
+        if (last == SMLA_FP8_UNITS && first < last) staged[SMLA_FP8_SLICES] = raw[5];
+    } else {
+        if (last == SMLA_FP8_UNITS && first < last) {
+#pragma unroll
+            for (int c = 0; c < SMLA_STAGE; ++c) staged[c] = raw[c];
+        }
+    }
+}
+
+template <typename Cache>
+__global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint16_t *__restrict__ q, const void *__restrict__ kv,
                                                                       int64_t kv_stride, int64_t s_rows, const int32_t *__restrict__ indices,
                                                                       int64_t idx_stride, int topk, const int32_t *__restrict__ offsets,
                                                                       int heads, int head_blocks, int64_t blocks, int64_t chunk, float scale2,
-                                                                      uint16_t *__restrict__ out, float *__restrict__ lse)
+                                                                      uint16_t *__restrict__ out, float *__restrict__ lse, int page_size,
+                                                                      int page_shift)
 {
+    // (kv_stride: elements between bf16 rows, bytes between fp8 blocks; the last two are the fp8 cache's alone -- the bf16 kernel's
+    // arguments, and with them its machine code, are what they were before the fp8 cache existed)
+    const Cache cache = Cache::make(kv, kv_stride, s_rows, page_size, page_shift);
     __shared__ __attribute__((aligned(16))) unsigned char tile[SMLA_TILE * SMLA_ROW_BYTES];
     __shared__ __attribute__((aligned(16))) unsigned char qimg[64 * SMLA_ROW_BYTES];   // the block's q, one row a head
     __shared__ __attribute__((aligned(16))) int32_t live[SMLA_TILE];                      // 1 where the tile's position is valid
@@ -85,23 +224,21 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
         const int64_t pos = (int64_t)tl * SMLA_TILE + gpos;
         return irow[pos < topk ? pos : topk - 1];
     };
-    auto row_of = [&](int tl, int32_t i) -> const uint16_t * {
+    auto row_of = [&](int tl, int32_t i) -> const unsigned char * {
         const int64_t pos = (int64_t)tl * SMLA_TILE + gpos;
         const int64_t r = (int64_t)i + shift;
-        return (pos < topk && i >= 0 && r >= 0 && r < s_rows) ? kv + r * kv_stride + gsub * 8 : nullptr;
+        return (pos < topk && i >= 0 && r >= 0 && r < cache.s_rows) ? cache.at(r, gsub) : nullptr;
     };
-    auto fetch = [&](const uint16_t *row, uint4 (&v)[SMLA_STAGE]) {
+    // (an invalid position stages zeros: codes 0 under scales 0 are +0 as well)
+    auto fetch = [&](const unsigned char *row, uint4 (&v)[Cache::RAW]) {
 #pragma unroll
-        for (int c = 0; c < SMLA_STAGE; ++c) v[c] = uint4{0, 0, 0, 0};
-        if (row) {
-#pragma unroll
-            for (int c = 0; c < SMLA_STAGE; ++c) v[c] = *reinterpret_cast<const uint4 *>(row + 64 * c);
-        }
+        for (int c = 0; c < Cache::RAW; ++c) v[c] = uint4{0, 0, 0, 0};
+        if (row) Cache::load(row, gsub, v);
     };
 
-    uint4 staged[SMLA_STAGE];
-    const uint16_t *row = row_of(0, ask(0));
-    fetch(row, staged);
+    uint4 raw[Cache::RAW], staged[SMLA_STAGE];                // what is in flight, and the nine chunks of the row's image it becomes
+    const unsigned char *row = row_of(0, ask(0));
+    fetch(row, raw);
     int32_t asked = ask(1);
 
     // the block's slice of q goes to LDS once, in the tile's row format (the first barrier of the loop stands between this and its use):
@@ -118,6 +255,9 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
             for (int c = 0; c < SMLA_STAGE; ++c) *reinterpret_cast<uint4 *>(qimg + hb * SMLA_ROW_BYTES + gsub * 16 + 128 * c) = v[c];
         }
     }
+
+    uint32_t pinned[SMLA_FP8_UNITS / 2];                      // (an fp8 cache's code dwords between their two units)
+    smla_stage<Cache>(0, SMLA_FP8_UNITS, raw, pinned, staged);   // (the first tile's: nothing to hide it behind)
 
     smla_v4f acc[SMLA_CTILES];
 #pragma unroll
@@ -136,12 +276,12 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
         // the staged tile goes to LDS
 #pragma unroll
         for (int c = 0; c < SMLA_STAGE; ++c)
-            *reinterpret_cast<uint4 *>(tile + gpos * SMLA_ROW_BYTES + gsub * 16 + 128 * c) = staged[c];
+            *reinterpret_cast<uint4 *>(tile + gpos * SMLA_ROW_BYTES + Cache::lds_at(c, gsub)) = staged[c];
         if (gsub == 0) live[gpos] = row != nullptr;
         __syncthreads();
         // the next tile's rows are asked for now and written after this tile's products; the indices of the one after it behind them
         row = row_of(tl + 1, asked);
-        fetch(row, staged);
+        fetch(row, raw);
         asked = ask(tl + 2);
 
         if (computes) {
@@ -222,9 +362,18 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
                 for (int j = 0; j < 4; ++j) {
                     const smla_v8s vf = __builtin_shufflevector(vlo[grp & 1][j], vhi[grp & 1][j], 0, 1, 2, 3, 4, 5, 6, 7);
                     acc[4 * grp + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(smla_v8bf, vf), pf, acc[4 * grp + j], 0, 0, 0);
+                    if constexpr (Cache::FP8) {
+                        // a unit of the next tile's rows behind each MFMA: its four vector instructions issue while the MFMA runs
+                        // (the rows were asked for at the top of the loop, a whole S^T and softmax ago)
+                        smla_stage<Cache, true>(smla_units_before(4 * grp + j), smla_units_before(4 * grp + j + 1), raw, pinned, staged);
+                        if (j < 3) __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
+            if constexpr (!Cache::FP8) smla_stage<Cache>(0, SMLA_FP8_UNITS, raw, pinned, staged);   // (bf16 rows: as they came)
+        } else {
+            smla_stage<Cache>(0, SMLA_FP8_UNITS, raw, pinned, staged);   // (a wave beyond the last head tile: all of it at once)
         }
         __syncthreads();
     }
@@ -246,6 +395,23 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     if (g == 0) lse[t * heads + h0 + hl] = empty ? -__builtin_inff() : (mx + __builtin_amdgcn_logf(sum)) * 0.693147180559945309f;
 }
 
+// The launch both entries end in: one workgroup per token and block of 64 heads, the grid walked XCD by XCD unless it is linear
+template <typename Cache>
+static int launch_sparse_mla(const void *q, const void *kv, int64_t kv_stride, int64_t s_rows, int page_size, int page_shift, const int32_t *indices,
+                             const int32_t *index_offsets, int64_t m, int heads, int head_blocks, int64_t topk, int64_t idx_stride,
+                             double sm_scale, int flags, void *out, float *lse, void *stream)
+{
+    const int64_t blocks = m * head_blocks;
+    const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
+    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
+    const int64_t grid = linear ? blocks : chunk * 8;
+    hipLaunchKernelGGL(sparse_mla_fwd_kernel<Cache>, dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint16_t *>(q), kv, kv_stride, s_rows, indices, idx_stride, static_cast<int>(topk), index_offsets, heads,
+                       head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634), static_cast<uint16_t *>(out), lse, page_size,
+                       page_shift);
+    return record_hip(hipGetLastError());
+}
+
 }  // namespace dga
 
 extern "C" int dga_sparse_mla_fwd(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
@@ -265,13 +431,33 @@ extern "C" int dga_sparse_mla_fwd(const void *q, const void *kv, const int32_t *
     const int head_blocks = (heads + 63) / 64;
     if (s > 0x7FFFFFFFll || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
     if (kv_stride > 0x7FFFFFFFFFFFFFFFll / 2 / s || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
-    const int64_t blocks = m * head_blocks;
-    const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
-    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
-    const int64_t grid = linear ? blocks : chunk * 8;
-    hipLaunchKernelGGL(sparse_mla_fwd_kernel, dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint16_t *>(q), static_cast<const uint16_t *>(kv), kv_stride, s, indices, idx_stride,
-                       static_cast<int>(topk), index_offsets, heads, head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634),
-                       static_cast<uint16_t *>(out), lse);
-    return record_hip(hipGetLastError());
+    return launch_sparse_mla<SmlaBf16Rows>(q, kv, kv_stride, s, 0, 0, indices, index_offsets, m, heads, head_blocks, topk, idx_stride, sm_scale,
+                                           flags, out, lse, stream);
+}
+
+// The same checks in the same order, the cache's own in the place of kv's: s = num_blocks page_size rows, block_stride bytes a block
+extern "C" int dga_sparse_mla_fwd_fp8(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m,
+                                      int heads, int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride,
+                                      double sm_scale, int flags, void *out, float *lse, void *stream)
+{
+    using namespace dga;
+    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
+    // (block_stride / 656 < page_size says block_stride < 656 page_size without the product)
+    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || num_blocks < 1 || page_size < 1 || topk < 1 ||
+        block_stride / SMLA_FP8_ROW < page_size || idx_stride < topk)
+        return DGA_E_SHAPE;
+    if (m == 0) return DGA_OK;
+    if (!q || !kv_cache || !indices || !out || !lse) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv_cache) % 16 || reinterpret_cast<uintptr_t>(out) % 16 ||
+        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 || reinterpret_cast<uintptr_t>(lse) % 4 ||
+        block_stride % 16)
+        return DGA_E_ALIGN;
+    const int head_blocks = (heads + 63) / 64;
+    if (num_blocks > 0x7FFFFFFFll / page_size || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks)
+        return DGA_E_RANGE;
+    if (block_stride > 0x7FFFFFFFFFFFFFFFll / num_blocks || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
+    const int page = static_cast<int>(page_size);
+    const int shift = (page & (page - 1)) == 0 ? __builtin_ctz(page) : -1;
+    return launch_sparse_mla<SmlaFp8Rows>(q, kv_cache, block_stride, num_blocks * page_size, page, shift, indices, index_offsets, m, heads,
+                                          head_blocks, topk, idx_stride, sm_scale, flags, out, lse, stream);
 }

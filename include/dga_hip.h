@@ -1016,6 +1016,41 @@ int dga_indexer_topk(const float *logits, int64_t m, int64_t n, int64_t stride, 
 int dga_sparse_mla_fwd(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int64_t s,
                        int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, void *out, float *lse, void *stream);
 
+/* The same over a paged fp8 latent cache, read in place (csrc/dga_sparse_mla.hip, the same kernel text instantiated on the cache).  A row
+ * is DGA_SPARSE_MLA_FP8_ROW_BYTES = 656 bytes (FlashMLA's layout of this model's cache):
+ *   bytes 0 .. 511     512 OCP e4m3fn codes of the latent part
+ *   bytes 512 .. 527   4 fp32 scales, one per 128 codes
+ *   bytes 528 .. 655   64 bf16 values, the rope part, not quantised
+ * and row r, 0 <= r < s = num_blocks page_size, lives at byte (r / page_size) block_stride + (r % page_size) 656 of kv_cache (16-byte
+ * aligned; block_stride a multiple of 16 and >= 656 page_size; any page_size >= 1 -- page_size 1 is a flat [s, 656] array with rows
+ * block_stride apart).  The value a row stands for is defined on the bits:
+ *   deq[r, d] = RNE_bf16(fl32(e4m3(code[r, d]) scale[r, d / 128])), d < 512: the code converted exactly, one fp32 multiplication and one
+ *   rounding to bf16, subnormals kept in both; codes 0x7F / 0xFF are NaN;  deq[r, 512 + i] = the i-th rope value as stored.
+ * Contract: dga_sparse_mla_fwd_fp8(kv_cache) is dga_sparse_mla_fwd(deq) -- out and lse byte for byte wherever the latter is not NaN, NaN in
+ * exactly the same elements -- so that entry's validity rule, arithmetic, bounds and determinism hold unchanged; every other argument is
+ * that entry's.  No byte of an unselected row and no byte between a block's last row and the next block is read.  One launch.
+ * Checks, all before the launch, in that entry's order: DGA_E_RANGE (an unknown flag);  DGA_E_SHAPE (m < 0, heads, num_blocks < 1,
+ * page_size < 1, topk < 1, block_stride < 656 page_size, idx_stride < topk);  m == 0 -> DGA_OK;  DGA_E_NULL;  DGA_E_ALIGN (q, kv_cache or
+ * out not 16-byte, indices, index_offsets or lse not 4-byte aligned, block_stride not a multiple of 16);  DGA_E_RANGE (s >= 2^31, topk or
+ * the grid beyond int32, num_blocks block_stride or m idx_stride beyond int64). */
+#define DGA_SPARSE_MLA_FP8_ROW_BYTES 656
+int dga_sparse_mla_fwd_fp8(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
+                           int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride, double sm_scale,
+                           int flags, void *out, float *lse, void *stream);
+
+/* The writer of that cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
+ * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
+ * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
+ * of the cache receives the 512 codes and 4 scales of dga_cast_to_fp8_1x128 on kv_c's row t (flags: DGA_CAST_UE8M0), byte for byte, and
+ * RNE_bf16(k_pe[t]) (bf16 input: its bits).  Any other slot value skips the token, whose inputs are not read; no other byte of the cache
+ * is written.  Duplicate valid slots are the caller's error.
+ * Checks, all before the launch: DGA_E_RANGE (an unknown flag);  DGA_E_SHAPE (tokens < 0, num_blocks < 1, page_size < 1,
+ * block_stride < 656 page_size, ld_c < 512, ld_pe < 64);  tokens == 0 -> DGA_OK;  DGA_E_NULL;  DGA_E_DTYPE;  DGA_E_ALIGN;  DGA_E_RANGE
+ * (num_blocks page_size >= 2^31, num_blocks block_stride or tokens times a row pitch beyond int64, the grid). */
+int dga_cast_mla_kv_to_fp8_paged(const void *kv_c, int64_t ld_c, const void *k_pe, int64_t ld_pe, int x_dtype, int64_t tokens, void *kv_cache,
+                                 int64_t num_blocks, int64_t page_size, int64_t block_stride, const int64_t *slot_mapping, int flags,
+                                 void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
