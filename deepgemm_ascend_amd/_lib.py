@@ -196,6 +196,12 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_fwd_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
                                        c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "dga_sparse_mla_fwd_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_double,
+                                           c_int, c_int, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
+    "dga_sparse_mla_fwd_fp8_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                               c_double, c_int, c_int, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
+    "dga_sparse_mla_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                              c_void_p, c_int, c_void_p]),
     "dga_catlass_dynamic_matmul_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -1998,6 +1998,56 @@ SPARSE_MLA_D_V = 512                 # DGA_SPARSE_MLA_D_V
 SPARSE_MLA_MAX_HEADS = 128           # DGA_SPARSE_MLA_MAX_HEADS
 
 
+def _smla_query(q: torch.Tensor, d_v: int, sm_scale) -> Tuple[int, int]:
+    """q, d_v and sm_scale of the sparse MLA operators, checked: (M, Hq)"""
+    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
+             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
+    m, heads = q.shape[0], q.shape[1]
+    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
+             SPARSE_MLA_MAX_HEADS, heads)
+    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
+    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    return m, heads
+
+
+def _smla_bf16_rows(q: torch.Tensor, kv: torch.Tensor) -> Tuple[int, int]:
+    """kv of sparse_mla_fwd and its split forms, checked (and q's alignment with it): (S, kv_stride)"""
+    _require(kv.dtype == torch.bfloat16 and (kv.dim() == 2 or (kv.dim() == 3 and kv.shape[1] == 1)) and kv.shape[-1] == SPARSE_MLA_D_QK,
+             "kv must be a bfloat16 [S, %d] or [S, 1, %d] tensor", SPARSE_MLA_D_QK, SPARSE_MLA_D_QK)
+    s = kv.shape[0]
+    _require(1 <= s < 1 << 31, "kv must have between 1 and 2^31 - 1 rows, got %d", s)
+    kv_stride = kv.stride(0) if s > 1 else SPARSE_MLA_D_QK
+    _require(kv.stride(-1) == 1 and kv_stride >= SPARSE_MLA_D_QK and kv_stride % 8 == 0,
+             "kv must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 8, got %d", SPARSE_MLA_D_QK, kv_stride)
+    _require(kv.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0, "q and kv must be 16-byte aligned")
+    return s, kv_stride
+
+
+def _smla_indices(indices: torch.Tensor, index_offsets: Optional[torch.Tensor], m: int) -> Tuple[int, int]:
+    """indices and index_offsets of the sparse MLA operators, checked: (topk, idx_stride)"""
+    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
+             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
+    topk = indices.shape[-1]
+    idx_stride = indices.stride(0) if m > 1 else topk
+    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
+    if index_offsets is not None:
+        _want(index_offsets, "index_offsets", torch.int32, (m,))
+    return topk, idx_stride
+
+
+def _smla_outputs(out: Optional[torch.Tensor], lse: Optional[torch.Tensor], m: int, heads: int, device):
+    """out bfloat16 [M, Hq, 512] and lse float32 [M, Hq]: torch.empty, or the caller's, checked"""
+    if out is None:
+        out = torch.empty((m, heads, SPARSE_MLA_D_V), dtype=torch.bfloat16, device=device)
+    else:
+        _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    if lse is None:
+        lse = torch.empty((m, heads), dtype=torch.float32, device=device)
+    else:
+        _want(lse, "lse", torch.float32, (m, heads))
+    return out, lse
+
+
 def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
                    index_offsets: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
                    sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2019,36 +2069,10 @@ def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_
     list order; the weights rounded to bf16 (RNE) for the second product while their sum l stays unrounded fp32; one multiplication by
     1 / l at the end.  One writer per element, no atomics: two runs give the same bytes.  Returns (out, lse), the caller's out= / lse=
     when given.  One launch, capturable -- a replayed graph follows new indices, offsets, kv and q; M == 0 returns without one."""
-    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
-             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
-    m, heads = q.shape[0], q.shape[1]
-    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
-             SPARSE_MLA_MAX_HEADS, heads)
-    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
-    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
-    _require(kv.dtype == torch.bfloat16 and (kv.dim() == 2 or (kv.dim() == 3 and kv.shape[1] == 1)) and kv.shape[-1] == SPARSE_MLA_D_QK,
-             "kv must be a bfloat16 [S, %d] or [S, 1, %d] tensor", SPARSE_MLA_D_QK, SPARSE_MLA_D_QK)
-    s = kv.shape[0]
-    _require(1 <= s < 1 << 31, "kv must have between 1 and 2^31 - 1 rows, got %d", s)
-    kv_stride = kv.stride(0) if s > 1 else SPARSE_MLA_D_QK
-    _require(kv.stride(-1) == 1 and kv_stride >= SPARSE_MLA_D_QK and kv_stride % 8 == 0,
-             "kv must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 8, got %d", SPARSE_MLA_D_QK, kv_stride)
-    _require(kv.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0, "q and kv must be 16-byte aligned")
-    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
-             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
-    topk = indices.shape[-1]
-    idx_stride = indices.stride(0) if m > 1 else topk
-    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
-    if index_offsets is not None:
-        _want(index_offsets, "index_offsets", torch.int32, (m,))
-    if out is None:
-        out = torch.empty((m, heads, SPARSE_MLA_D_V), dtype=torch.bfloat16, device=q.device)
-    else:
-        _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
-    if lse is None:
-        lse = torch.empty((m, heads), dtype=torch.float32, device=q.device)
-    else:
-        _want(lse, "lse", torch.float32, (m, heads))
+    m, heads = _smla_query(q, d_v, sm_scale)
+    s, kv_stride = _smla_bf16_rows(q, kv)
+    topk, idx_stride = _smla_indices(indices, index_offsets, m)
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
     # (M == 0: the C entry returns before any launch)
     _launch("sparse_mla_fwd", (q, kv, indices, index_offsets, out, lse), lambda L, stream: L.dga_sparse_mla_fwd(
         q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale),
@@ -2094,34 +2118,191 @@ def sparse_mla_fwd_fp8(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.T
     The result is sparse_mla_fwd(q, deq, ...)'s: out and lse byte for byte wherever that is not NaN, NaN in exactly the same elements;
     q, indices, index_offsets, out, lse, the validity rule, the arithmetic and its bounds are that function's.  No byte of an unselected
     row and no byte between a block's last row and the next block is read.  One launch, capturable; M == 0 returns without one."""
-    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
-             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
-    m, heads = q.shape[0], q.shape[1]
-    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
-             SPARSE_MLA_MAX_HEADS, heads)
-    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
-    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    m, heads = _smla_query(q, d_v, sm_scale)
     nb, page, stride = _mla_fp8_cache(kv_cache)
     _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
-    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
-             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
-    topk = indices.shape[-1]
-    idx_stride = indices.stride(0) if m > 1 else topk
-    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
-    if index_offsets is not None:
-        _want(index_offsets, "index_offsets", torch.int32, (m,))
-    if out is None:
-        out = torch.empty((m, heads, SPARSE_MLA_D_V), dtype=torch.bfloat16, device=q.device)
-    else:
-        _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
-    if lse is None:
-        lse = torch.empty((m, heads), dtype=torch.float32, device=q.device)
-    else:
-        _want(lse, "lse", torch.float32, (m, heads))
+    topk, idx_stride = _smla_indices(indices, index_offsets, m)
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
     # (M == 0: the C entry returns before any launch)
     _launch("sparse_mla_fwd_fp8", (q, kv_cache, indices, index_offsets, out, lse), lambda L, stream: L.dga_sparse_mla_fwd_fp8(
         q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk, idx_stride,
         float(sm_scale), _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
+    return out, lse
+
+
+SPARSE_MLA_MAX_SPLITS = 64           # DGA_SPARSE_MLA_MAX_SPLITS
+
+
+def _smla_splits(num_splits, topk: int) -> int:
+    """num_splits of the split forms, checked: the effective P = min(num_splits, ceil(topk / 32))"""
+    _require(isinstance(num_splits, int) and not isinstance(num_splits, bool) and 1 <= num_splits <= SPARSE_MLA_MAX_SPLITS,
+             "num_splits must be an int in [1, %d], got %r", SPARSE_MLA_MAX_SPLITS, num_splits)
+    return min(num_splits, (topk + 31) // 32)
+
+
+def _smla_partials(partial_out, partial_lse, p: int, m: int, heads: int, device):
+    """partial_out float32 [P, M, Hq, 512] and partial_lse float32 [P, M, Hq]: torch.empty, or the first P splits of the caller's
+    contiguous [>= P, ...] buffers (what lies beyond them is not touched)"""
+    made = []
+    for t, what, shape in ((partial_out, "partial_out", (m, heads, SPARSE_MLA_D_V)), (partial_lse, "partial_lse", (m, heads))):
+        if t is None:
+            t = torch.empty((p,) + shape, dtype=torch.float32, device=device)
+        else:
+            _require(t.dtype == torch.float32 and t.dim() == len(shape) + 1 and tuple(t.shape[1:]) == shape and t.shape[0] >= p
+                     and t.is_contiguous(), "%s must be contiguous float32 [>= %d, %s]", what, p, ", ".join(map(str, shape)))
+            t = t[:p]
+        made.append(t)
+    return made
+
+
+def sparse_mla_fwd_partial(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, num_splits: int, d_v: int = 512,
+                           index_offsets: Optional[torch.Tensor] = None, partial_out: Optional[torch.Tensor] = None,
+                           partial_lse: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first half of split-topk sparse MLA decode (dga_sparse_mla_fwd_partial): sparse_mla_fwd with P workgroups a token and head block
+    in place of one, for the small M at which one workgroup a token leaves the device idle.  q, kv, indices, sm_scale, d_v and
+    index_offsets are sparse_mla_fwd's; num_splits an int in [1, 64].  With tiles = ceil(topk / 32) and P = min(num_splits, tiles), split p
+    owns the contiguous tiles [p tiles // P, (p + 1) tiles // P) of every token's list and writes its own attention result in float32, not
+    rounded to bfloat16: partial_out[p, m, h, :] = sum_j exp(s_j - partial_lse[p, m, h]) kv[r_j, :512] and
+    partial_lse[p, m, h] = ln sum_j exp(s_j) over the split's valid positions, +0 and -inf where it has none.  Per tile the arithmetic is
+    sparse_mla_fwd's.  Returns (partial_out float32 [P, M, Hq, 512], partial_lse float32 [P, M, Hq]) with the effective P as their first
+    dimension: fresh tensors, or the first P splits of the caller's contiguous float32 [>= P, M, Hq, 512] and [>= P, M, Hq] buffers, of which
+    every element is written and nothing beyond them is.  sparse_mla_merge turns them into (out, lse); with P = 1 the two calls give
+    sparse_mla_fwd's bytes.  One launch, capturable; two runs give the same bytes; M == 0 returns without a launch."""
+    m, heads = _smla_query(q, d_v, sm_scale)
+    s, kv_stride = _smla_bf16_rows(q, kv)
+    topk, idx_stride = _smla_indices(indices, index_offsets, m)
+    p = _smla_splits(num_splits, topk)
+    po, pl = _smla_partials(partial_out, partial_lse, p, m, heads, q.device)
+    # (M == 0: the C entry returns before any launch)
+    _launch("sparse_mla_fwd_partial", (q, kv, indices, index_offsets, po, pl), lambda L, stream: L.dga_sparse_mla_fwd_partial(
+        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale),
+        _flags, p, None, po.data_ptr(), pl.data_ptr(), stream), sync)
+    return po, pl
+
+
+def sparse_mla_fwd_fp8_partial(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.Tensor, sm_scale: float, num_splits: int, d_v: int = 512,
+                               index_offsets: Optional[torch.Tensor] = None, partial_out: Optional[torch.Tensor] = None,
+                               partial_lse: Optional[torch.Tensor] = None, sync: bool = False,
+                               _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sparse_mla_fwd_partial over sparse_mla_fwd_fp8's paged fp8 latent cache, read in place (dga_sparse_mla_fwd_fp8_partial).  kv_cache is
+    that function's, everything else sparse_mla_fwd_partial's.  Both partials are sparse_mla_fwd_partial(q, deq, ...)'s byte for byte
+    wherever those are not NaN, NaN in exactly the same elements.  One launch, capturable; M == 0 returns without one."""
+    m, heads = _smla_query(q, d_v, sm_scale)
+    nb, page, stride = _mla_fp8_cache(kv_cache)
+    _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
+    topk, idx_stride = _smla_indices(indices, index_offsets, m)
+    p = _smla_splits(num_splits, topk)
+    po, pl = _smla_partials(partial_out, partial_lse, p, m, heads, q.device)
+    # (M == 0: the C entry returns before any launch)
+    _launch("sparse_mla_fwd_fp8_partial", (q, kv_cache, indices, index_offsets, po, pl), lambda L, stream: L.dga_sparse_mla_fwd_fp8_partial(
+        q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk, idx_stride,
+        float(sm_scale), _flags, p, None, po.data_ptr(), pl.data_ptr(), stream), sync)
+    return po, pl
+
+
+def sparse_mla_merge(partial_out: torch.Tensor, partial_lse: torch.Tensor, out: Optional[torch.Tensor] = None,
+                     lse: Optional[torch.Tensor] = None, sync: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The merge of attention partials (dga_sparse_mla_merge): partial_out float32 [P, M, Hq, 512] and partial_lse float32 [P, M, Hq]
+    (natural log), both contiguous, 1 <= P <= 64 -- sparse_mla_fwd_partial's, or the (out, lse) of context-parallel ranks or of chunks of a
+    longer list in float32 -- into out bfloat16 [M, Hq, 512] and lse float32 [M, Hq]:
+    lse = ln sum_p exp(partial_lse[p]);  out = sum_p exp(partial_lse[p] - lse) partial_out[p];  every partial_lse -inf: +0 and -inf.
+    Arithmetic, float32, nothing contracted, p ascending: M = max_p partial_lse[p] (a NaN passed over), mu = M or 0 when M = -inf;
+    w_p = exp2((partial_lse[p] - mu) log2 e);  L = ((w_0 + w_1) + w_2) + ...;  N = ((w_0 po_0 + w_1 po_1) + w_2 po_2) + ...;
+    out = RNE_bf16(N (1 / L)), lse = mu + ln 2 log2 L.  A split of lse -inf weighs 0 (its partial_out must be finite: the partial kernels
+    write +0); a NaN partial_lse makes the head NaN.  With P = 1: out = RNE_bf16(partial_out[0]) and lse = partial_lse[0], bit for bit.
+    One writer per element, no atomics; nothing of a split beyond P is read.  Returns (out, lse), the caller's when given.  One launch,
+    capturable; M == 0 returns without one."""
+    _require(partial_out.dim() == 4 and partial_out.dtype == torch.float32 and partial_out.shape[3] == SPARSE_MLA_D_V
+             and partial_out.is_contiguous(), "partial_out must be a contiguous float32 [P, M, Hq, %d] tensor", SPARSE_MLA_D_V)
+    p, m, heads = partial_out.shape[0], partial_out.shape[1], partial_out.shape[2]
+    _require(1 <= p <= SPARSE_MLA_MAX_SPLITS, "partial_out must hold between 1 and %d splits, got %d", SPARSE_MLA_MAX_SPLITS, p)
+    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
+             SPARSE_MLA_MAX_HEADS, heads)
+    _want(partial_lse, "partial_lse", torch.float32, (p, m, heads))
+    _require(partial_out.data_ptr() % 16 == 0, "partial_out must be 16-byte aligned")
+    out, lse = _smla_outputs(out, lse, m, heads, partial_out.device)
+    # (M == 0: the C entry returns before any launch)
+    _launch("sparse_mla_merge", (partial_out, partial_lse, out, lse), lambda L, stream: L.dga_sparse_mla_merge(
+        partial_out.data_ptr(), partial_lse.data_ptr(), p, m, heads, out.data_ptr(), lse.data_ptr(), stream), sync)
+    return out, lse
+
+
+def sparse_mla_num_splits(m: int, heads: int, topk: int, device=None) -> int:
+    """The number of splits sparse_mla_fwd_split(num_splits=None) runs M tokens of Hq = heads heads and topk positions with
+    (dga_sparse_mla_splits): max(1, min(CUs // (M head_blocks), tiles // 4, 64)), head_blocks = ceil(Hq / 64), tiles = ceil(topk / 32) -- as
+    many splits as the device has idle compute units for, none shorter than four tiles (DGA_SPARSE_MLA_MIN_TILES: DESIGN.md has the sweep
+    behind it), 1 once M head_blocks workgroups fill the device.  The CU count is the library's, of `device` or of the current device."""
+    _require(all(isinstance(x, int) and x >= 1 for x in (m, heads, topk)), "m, heads and topk must be ints >= 1")
+    if device is None:
+        return int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
+    with torch.cuda.device(device):
+        return int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
+
+
+def _smla_split_launch(name: str, tensors, partial, p: int, m: int, heads: int, out: torch.Tensor, lse: torch.Tensor, sync: bool) -> None:
+    """The tail of the two split operators: partial(L, stream, partial_out, partial_lse) and the merge, two launches on one stream, the
+    partials in scratch of that device and stream"""
+    def call(L, stream):
+        rows = p * m * heads
+        ws, _ = _scratch("sparse_mla_split", out.device, rows * (SPARSE_MLA_D_V + 1) * 4, stream)
+        pl = None if ws is None else ws + rows * SPARSE_MLA_D_V * 4
+        return partial(L, stream, ws, pl) or L.dga_sparse_mla_merge(ws, pl, p, m, heads, out.data_ptr(), lse.data_ptr(), stream)
+    _launch(name, tensors, call, sync)
+
+
+def sparse_mla_fwd_split(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
+                         index_offsets: Optional[torch.Tensor] = None, num_splits: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                         lse: Optional[torch.Tensor] = None, sync: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sparse_mla_fwd for low-batch decode: the list split over num_splits workgroups a token and head block, and merged.  Arguments and
+    result are sparse_mla_fwd's.  num_splits=None applies sparse_mla_num_splits(M, Hq, topk) on q's device; when that is 1 -- M head_blocks
+    workgroups fill the device, or the list is short -- the call is sparse_mla_fwd itself, one launch.  An explicit num_splits in [1, 64], 1
+    included, always runs sparse_mla_fwd_partial and sparse_mla_merge: two launches on one stream, no memset, no flags, no atomics,
+    capturable -- a replayed graph follows new q, kv, indices and offsets -- with the partials in library scratch of that device and
+    stream.  The result is sparse_mla_merge(*sparse_mla_fwd_partial(..., num_splits)) byte for byte; with num_splits=1 sparse_mla_fwd's
+    bytes; otherwise within the bound of DESIGN.md, "Split-topk sparse MLA decode", of the exact result; NaN where sparse_mla_fwd has it."""
+    if num_splits is None:
+        m, heads = _smla_query(q, d_v, sm_scale)
+        topk, _ = _smla_indices(indices, index_offsets, m)
+        if q.is_cuda and m:
+            with _device_guard(q):
+                num_splits = int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
+        if num_splits is None or num_splits == 1:
+            return sparse_mla_fwd(q, kv, indices, sm_scale, d_v, index_offsets, out, lse, sync)
+    m, heads = _smla_query(q, d_v, sm_scale)
+    s, kv_stride = _smla_bf16_rows(q, kv)
+    topk, idx_stride = _smla_indices(indices, index_offsets, m)
+    p = _smla_splits(num_splits, topk)
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
+    _smla_split_launch("sparse_mla_fwd_split", (q, kv, indices, index_offsets, out, lse), lambda L, stream, po, pl: L.dga_sparse_mla_fwd_partial(
+        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale), 0,
+        p, None, po, pl, stream), p, m, heads, out, lse, sync)
+    return out, lse
+
+
+def sparse_mla_fwd_fp8_split(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
+                             index_offsets: Optional[torch.Tensor] = None, num_splits: Optional[int] = None,
+                             out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+                             sync: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sparse_mla_fwd_split over sparse_mla_fwd_fp8's paged fp8 latent cache: num_splits=None and a rule of 1 is sparse_mla_fwd_fp8 itself, an
+    explicit num_splits runs sparse_mla_fwd_fp8_partial and sparse_mla_merge.  The result is sparse_mla_fwd_split(q, deq, ...)'s."""
+    if num_splits is None:
+        m, heads = _smla_query(q, d_v, sm_scale)
+        topk, _ = _smla_indices(indices, index_offsets, m)
+        if q.is_cuda and m:
+            with _device_guard(q):
+                num_splits = int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
+        if num_splits is None or num_splits == 1:
+            return sparse_mla_fwd_fp8(q, kv_cache, indices, sm_scale, d_v, index_offsets, out, lse, sync)
+    m, heads = _smla_query(q, d_v, sm_scale)
+    nb, page, stride = _mla_fp8_cache(kv_cache)
+    _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
+    topk, idx_stride = _smla_indices(indices, index_offsets, m)
+    p = _smla_splits(num_splits, topk)
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
+    _smla_split_launch("sparse_mla_fwd_fp8_split", (q, kv_cache, indices, index_offsets, out, lse),
+                       lambda L, stream, po, pl: L.dga_sparse_mla_fwd_fp8_partial(
+                           q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk,
+                           idx_stride, float(sm_scale), 0, p, None, po, pl, stream), p, m, heads, out, lse, sync)
     return out, lse
 
 

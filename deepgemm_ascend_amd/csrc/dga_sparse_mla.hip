@@ -34,6 +34,13 @@
 // loop is the row's dequantised image, deq[r, d] = RNE_bf16(fl32(e4m3(code) scale)), in the bf16 gather's format: from the barrier on the
 // two kernels run the same instructions on the same bytes, so dga_sparse_mla_fwd_fp8(cache) is dga_sparse_mla_fwd(deq(cache)) bit for bit.
 // ("Sparse MLA attention over a paged fp8 latent cache", has the schedules that were measured.)
+//   dga_sparse_mla_fwd_partial, dga_sparse_mla_fwd_fp8_partial   split-topk decode: the third axis of the one kernel text, <Cache, PARTIAL>.
+// With tiles = ceil(topk / 32) and P <= min(tiles, 64) splits the grid is m head_blocks P workgroups, the splits of one token and head block
+// adjacent in the same XCD mapping; split p runs the loop above over the tiles [p tiles / P, (p + 1) tiles / P) only (wave-uniform, in
+// SGPRs; the read-ahead stops at the split's end) and stores, in fp32 and not rounded, partial_out[p, t, h, :] = O (1 / l) by 16-byte stores
+// of a lane's four columns and partial_lse[p, t, h] = ln 2 (m + log2 l) -- +0 and -inf for a split without a valid position.  Every element
+// of [P, m, heads, 512] and [P, m, heads] is written.  dga_sparse_mla_merge (dga_sparse_mla_merge.hip) turns them into out and lse; with
+// P = 1 the two launches reproduce the one-pass kernel byte for byte.  The one-pass instantiations <Cache, false> are what they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -186,16 +193,18 @@ __device__ __forceinline__ void smla_stage(int first, int last, const uint4 (&ra
     }
 }
 
-template <typename Cache>
+template <typename Cache, bool PARTIAL>
 __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint16_t *__restrict__ q, const void *__restrict__ kv,
                                                                       int64_t kv_stride, int64_t s_rows, const int32_t *__restrict__ indices,
                                                                       int64_t idx_stride, int topk, const int32_t *__restrict__ offsets,
                                                                       int heads, int head_blocks, int64_t blocks, int64_t chunk, float scale2,
                                                                       uint16_t *__restrict__ out, float *__restrict__ lse, int page_size,
-                                                                      int page_shift)
+                                                                      int page_shift, float *__restrict__ partial_out,
+                                                                      float *__restrict__ partial_lse, int num_splits, int64_t split_rows)
 {
     // (kv_stride: elements between bf16 rows, bytes between fp8 blocks; the last two are the fp8 cache's alone -- the bf16 kernel's
-    // arguments, and with them its machine code, are what they were before the fp8 cache existed)
+    // arguments, and with them its machine code, are what they were before the fp8 cache existed; the last four are the PARTIAL
+    // instantiations' alone, appended for the same reason: split_rows = m heads, the rows of one split's partial_lse)
     const Cache cache = Cache::make(kv, kv_stride, s_rows, page_size, page_shift);
     __shared__ __attribute__((aligned(16))) unsigned char tile[SMLA_TILE * SMLA_ROW_BYTES];
     __shared__ __attribute__((aligned(16))) unsigned char qimg[64 * SMLA_ROW_BYTES];   // the block's q, one row a head
@@ -207,6 +216,12 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     int64_t block = blockIdx.x;
     if (chunk) block = (block & 7) * chunk + (block >> 3);
     if (block >= blocks) return;                             // (the whole workgroup alike, before any barrier)
+    // PARTIAL: the splits of one token and head block are adjacent blocks; what is left of the number is the one-pass kernel's
+    int split = 0;
+    if constexpr (PARTIAL) {
+        split = (int)(block % num_splits);
+        block = block / num_splits;
+    }
     const int64_t t = block / head_blocks;
     const int h0 = (int)(block % head_blocks) * 64 + wave * 16;
     const bool computes = h0 < heads;                        // (a wave beyond the last head tile only gathers)
@@ -214,6 +229,11 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     const int32_t *irow = indices + t * idx_stride;
     const int64_t shift = offsets ? (int64_t)offsets[t] : 0;
     const int tiles = (topk + SMLA_TILE - 1) / SMLA_TILE;
+    // the tiles [tile_lo, tile_hi) this workgroup walks, wave-uniform: all of them, or split `split` of num_splits <= tiles (never empty);
+    // positions from `limit` on are not gathered (PARTIAL: the next split's first tile is not this one's to read ahead)
+    const int tile_lo = PARTIAL ? (int)((int64_t)split * tiles / num_splits) : 0;
+    const int tile_hi = PARTIAL ? (int)((int64_t)(split + 1) * tiles / num_splits) : tiles;
+    const int64_t limit = PARTIAL && tile_hi < tiles ? (int64_t)tile_hi * SMLA_TILE : (int64_t)topk;
 
     // The gather: eight threads a position (position tid / 8 of the tile), thread tid % 8 of them the 16-byte chunks tid % 8 + 8 c,
     // c = 0 .. 8, of the row -- 128 contiguous bytes of a row per eight lanes and step.  A position's index is read one tile ahead of its
@@ -227,7 +247,7 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     auto row_of = [&](int tl, int32_t i) -> const unsigned char * {
         const int64_t pos = (int64_t)tl * SMLA_TILE + gpos;
         const int64_t r = (int64_t)i + shift;
-        return (pos < topk && i >= 0 && r >= 0 && r < cache.s_rows) ? cache.at(r, gsub) : nullptr;
+        return (pos < limit && i >= 0 && r >= 0 && r < cache.s_rows) ? cache.at(r, gsub) : nullptr;
     };
     // (an invalid position stages zeros: codes 0 under scales 0 are +0 as well)
     auto fetch = [&](const unsigned char *row, uint4 (&v)[Cache::RAW]) {
@@ -237,9 +257,9 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     };
 
     uint4 raw[Cache::RAW], staged[SMLA_STAGE];                // what is in flight, and the nine chunks of the row's image it becomes
-    const unsigned char *row = row_of(0, ask(0));
+    const unsigned char *row = row_of(tile_lo, ask(tile_lo));
     fetch(row, raw);
-    int32_t asked = ask(1);
+    int32_t asked = ask(tile_lo + 1);
 
     // the block's slice of q goes to LDS once, in the tile's row format (the first barrier of the loop stands between this and its use):
     // eight threads a head, 32 heads a pass
@@ -272,7 +292,7 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     const uint32_t q_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)qimg + (wave * 16 + hl) * SMLA_ROW_BYTES + 16 * g;
 
 #pragma unroll 1
-    for (int tl = 0; tl < tiles; ++tl) {
+    for (int tl = tile_lo; tl < tile_hi; ++tl) {
         // the staged tile goes to LDS
 #pragma unroll
         for (int c = 0; c < SMLA_STAGE; ++c)
@@ -384,15 +404,29 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     sum = sum + __shfl_xor(sum, 32, 64);
     const bool empty = sum == 0.f;                           // no valid position (a NaN is not equal to 0 and goes through)
     const float inv = empty ? 0.f : 1.0f / sum;
-    uint16_t *orow = out + ((t * heads + h0 + hl) * SMLA_DV + 4 * g);
+    if constexpr (PARTIAL) {
+        // the split's own result, O (1 / l) before its rounding to bf16: 16-byte stores of the lane's four columns
+        const int64_t prow = split * split_rows + t * heads + h0 + hl;
+        float *orow = partial_out + (prow * SMLA_DV + 4 * g);
 #pragma unroll
-    for (int ct = 0; ct < SMLA_CTILES; ++ct) {
-        smla_v4bf o;
+        for (int ct = 0; ct < SMLA_CTILES; ++ct) {
+            smla_v4f o;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = (__bf16)(empty ? 0.f : acc[ct][i] * inv);
-        *reinterpret_cast<uint2 *>(orow + 16 * ct) = __builtin_bit_cast(uint2, o);
+            for (int i = 0; i < 4; ++i) o[i] = empty ? 0.f : acc[ct][i] * inv;
+            *reinterpret_cast<smla_v4f *>(orow + 16 * ct) = o;
+        }
+        if (g == 0) partial_lse[prow] = empty ? -__builtin_inff() : (mx + __builtin_amdgcn_logf(sum)) * 0.693147180559945309f;
+    } else {
+        uint16_t *orow = out + ((t * heads + h0 + hl) * SMLA_DV + 4 * g);
+#pragma unroll
+        for (int ct = 0; ct < SMLA_CTILES; ++ct) {
+            smla_v4bf o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = (__bf16)(empty ? 0.f : acc[ct][i] * inv);
+            *reinterpret_cast<uint2 *>(orow + 16 * ct) = __builtin_bit_cast(uint2, o);
+        }
+        if (g == 0) lse[t * heads + h0 + hl] = empty ? -__builtin_inff() : (mx + __builtin_amdgcn_logf(sum)) * 0.693147180559945309f;
     }
-    if (g == 0) lse[t * heads + h0 + hl] = empty ? -__builtin_inff() : (mx + __builtin_amdgcn_logf(sum)) * 0.693147180559945309f;
 }
 
 // The launch both entries end in: one workgroup per token and block of 64 heads, the grid walked XCD by XCD unless it is linear
@@ -405,12 +439,89 @@ static int launch_sparse_mla(const void *q, const void *kv, int64_t kv_stride, i
     const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
     const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
     const int64_t grid = linear ? blocks : chunk * 8;
-    hipLaunchKernelGGL(sparse_mla_fwd_kernel<Cache>, dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint16_t *>(q), kv, kv_stride, s_rows, indices, idx_stride, static_cast<int>(topk), index_offsets, heads,
-                       head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634), static_cast<uint16_t *>(out), lse, page_size,
-                       page_shift);
+    hipLaunchKernelGGL((sparse_mla_fwd_kernel<Cache, false>), dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(q), kv, kv_stride, s_rows, indices, idx_stride,
+                       static_cast<int>(topk), index_offsets, heads, head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634),
+                       static_cast<uint16_t *>(out), lse, page_size, page_shift, static_cast<float *>(nullptr), static_cast<float *>(nullptr), 1,
+                       static_cast<int64_t>(0));
     return record_hip(hipGetLastError());
 }
+
+// The partial entries' tail: num_splits and the partial pointers checked, then m head_blocks P workgroups over the same mapping
+template <typename Cache>
+static int launch_sparse_mla_partial(const void *q, const void *kv, int64_t kv_stride, int64_t s_rows, int page_size, int page_shift,
+                                     const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int head_blocks, int64_t topk,
+                                     int64_t idx_stride, double sm_scale, int flags, int num_splits, int *effective_splits, float *partial_out,
+                                     float *partial_lse, void *stream)
+{
+    if (num_splits < 1 || num_splits > DGA_SPARSE_MLA_MAX_SPLITS) return DGA_E_RANGE;
+    const int64_t tiles = (topk + SMLA_TILE - 1) / SMLA_TILE;
+    const int splits = num_splits > tiles ? static_cast<int>(tiles) : num_splits;
+    if (m > (0x7FFFFFFFll - 8) / head_blocks / splits) return DGA_E_RANGE;
+    if (!partial_out || !partial_lse) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(partial_out) % 16 || reinterpret_cast<uintptr_t>(partial_lse) % 4) return DGA_E_ALIGN;
+    if (effective_splits) *effective_splits = splits;
+    const int64_t blocks = m * head_blocks * splits;
+    const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
+    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
+    const int64_t grid = linear ? blocks : chunk * 8;
+    hipLaunchKernelGGL((sparse_mla_fwd_kernel<Cache, true>), dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(q), kv, kv_stride, s_rows, indices, idx_stride,
+                       static_cast<int>(topk), index_offsets, heads, head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634),
+                       static_cast<uint16_t *>(nullptr), static_cast<float *>(nullptr), page_size, page_shift, partial_out, partial_lse, splits,
+                       m * heads);
+    return record_hip(hipGetLastError());
+}
+
+// The checks of the bf16 entries, in the documented order; *launch is set when a launch is to follow (not for m == 0).  outputs: out and
+// lse are this entry's (the partial entries check theirs afterwards)
+static int check_sparse_mla(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int64_t s,
+                            int64_t kv_stride, int64_t topk, int64_t idx_stride, int flags, bool outputs, const void *out, const void *lse,
+                            bool *launch)
+{
+    *launch = false;
+    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
+    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || s < 1 || topk < 1 || kv_stride < SMLA_D || idx_stride < topk)
+        return DGA_E_SHAPE;
+    if (m == 0) return DGA_OK;
+    if (!q || !kv || !indices || (outputs && (!out || !lse))) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv) % 16 || (outputs && reinterpret_cast<uintptr_t>(out) % 16) ||
+        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 ||
+        (outputs && reinterpret_cast<uintptr_t>(lse) % 4) || kv_stride % 8)
+        return DGA_E_ALIGN;
+    const int head_blocks = (heads + 63) / 64;
+    if (s > 0x7FFFFFFFll || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
+    if (kv_stride > 0x7FFFFFFFFFFFFFFFll / 2 / s || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
+    *launch = true;
+    return DGA_OK;
+}
+
+// The same checks in the same order, the cache's own in the place of kv's: s = num_blocks page_size rows, block_stride bytes a block
+static int check_sparse_mla_fp8(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
+                                int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride, int flags,
+                                bool outputs, const void *out, const void *lse, bool *launch)
+{
+    *launch = false;
+    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
+    // (block_stride / 656 < page_size says block_stride < 656 page_size without the product)
+    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || num_blocks < 1 || page_size < 1 || topk < 1 ||
+        block_stride / SMLA_FP8_ROW < page_size || idx_stride < topk)
+        return DGA_E_SHAPE;
+    if (m == 0) return DGA_OK;
+    if (!q || !kv_cache || !indices || (outputs && (!out || !lse))) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv_cache) % 16 || (outputs && reinterpret_cast<uintptr_t>(out) % 16) ||
+        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 ||
+        (outputs && reinterpret_cast<uintptr_t>(lse) % 4) || block_stride % 16)
+        return DGA_E_ALIGN;
+    const int head_blocks = (heads + 63) / 64;
+    if (num_blocks > 0x7FFFFFFFll / page_size || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks)
+        return DGA_E_RANGE;
+    if (block_stride > 0x7FFFFFFFFFFFFFFFll / num_blocks || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
+    *launch = true;
+    return DGA_OK;
+}
+
+static int page_shift_of(int page) { return (page & (page - 1)) == 0 ? __builtin_ctz(page) : -1; }
 
 }  // namespace dga
 
@@ -419,45 +530,52 @@ extern "C" int dga_sparse_mla_fwd(const void *q, const void *kv, const int32_t *
                                   float *lse, void *stream)
 {
     using namespace dga;
-    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
-    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || s < 1 || topk < 1 || kv_stride < SMLA_D || idx_stride < topk)
-        return DGA_E_SHAPE;
-    if (m == 0) return DGA_OK;
-    if (!q || !kv || !indices || !out || !lse) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv) % 16 || reinterpret_cast<uintptr_t>(out) % 16 ||
-        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 || reinterpret_cast<uintptr_t>(lse) % 4 ||
-        kv_stride % 8)
-        return DGA_E_ALIGN;
-    const int head_blocks = (heads + 63) / 64;
-    if (s > 0x7FFFFFFFll || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
-    if (kv_stride > 0x7FFFFFFFFFFFFFFFll / 2 / s || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
-    return launch_sparse_mla<SmlaBf16Rows>(q, kv, kv_stride, s, 0, 0, indices, index_offsets, m, heads, head_blocks, topk, idx_stride, sm_scale,
-                                           flags, out, lse, stream);
+    bool launch;
+    const int rc = check_sparse_mla(q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, flags, true, out, lse, &launch);
+    if (!launch) return rc;
+    return launch_sparse_mla<SmlaBf16Rows>(q, kv, kv_stride, s, 0, 0, indices, index_offsets, m, heads, (heads + 63) / 64, topk, idx_stride,
+                                           sm_scale, flags, out, lse, stream);
 }
 
-// The same checks in the same order, the cache's own in the place of kv's: s = num_blocks page_size rows, block_stride bytes a block
 extern "C" int dga_sparse_mla_fwd_fp8(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m,
                                       int heads, int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride,
                                       double sm_scale, int flags, void *out, float *lse, void *stream)
 {
     using namespace dga;
-    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
-    // (block_stride / 656 < page_size says block_stride < 656 page_size without the product)
-    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || num_blocks < 1 || page_size < 1 || topk < 1 ||
-        block_stride / SMLA_FP8_ROW < page_size || idx_stride < topk)
-        return DGA_E_SHAPE;
-    if (m == 0) return DGA_OK;
-    if (!q || !kv_cache || !indices || !out || !lse) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv_cache) % 16 || reinterpret_cast<uintptr_t>(out) % 16 ||
-        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 || reinterpret_cast<uintptr_t>(lse) % 4 ||
-        block_stride % 16)
-        return DGA_E_ALIGN;
-    const int head_blocks = (heads + 63) / 64;
-    if (num_blocks > 0x7FFFFFFFll / page_size || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks)
-        return DGA_E_RANGE;
-    if (block_stride > 0x7FFFFFFFFFFFFFFFll / num_blocks || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
+    bool launch;
+    const int rc = check_sparse_mla_fp8(q, kv_cache, indices, index_offsets, m, heads, num_blocks, page_size, block_stride, topk, idx_stride, flags,
+                                        true, out, lse, &launch);
+    if (!launch) return rc;
     const int page = static_cast<int>(page_size);
-    const int shift = (page & (page - 1)) == 0 ? __builtin_ctz(page) : -1;
-    return launch_sparse_mla<SmlaFp8Rows>(q, kv_cache, block_stride, num_blocks * page_size, page, shift, indices, index_offsets, m, heads,
-                                          head_blocks, topk, idx_stride, sm_scale, flags, out, lse, stream);
+    return launch_sparse_mla<SmlaFp8Rows>(q, kv_cache, block_stride, num_blocks * page_size, page, page_shift_of(page), indices, index_offsets, m,
+                                          heads, (heads + 63) / 64, topk, idx_stride, sm_scale, flags, out, lse, stream);
+}
+
+// Split-topk decode: the same checks, then num_splits and the partial pointers (launch_sparse_mla_partial)
+extern "C" int dga_sparse_mla_fwd_partial(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
+                                          int64_t s, int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags,
+                                          int num_splits, int *effective_splits, float *partial_out, float *partial_lse, void *stream)
+{
+    using namespace dga;
+    bool launch;
+    const int rc = check_sparse_mla(q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, flags, false, nullptr, nullptr, &launch);
+    if (!launch) return rc;
+    return launch_sparse_mla_partial<SmlaBf16Rows>(q, kv, kv_stride, s, 0, 0, indices, index_offsets, m, heads, (heads + 63) / 64, topk, idx_stride,
+                                                   sm_scale, flags, num_splits, effective_splits, partial_out, partial_lse, stream);
+}
+
+extern "C" int dga_sparse_mla_fwd_fp8_partial(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m,
+                                              int heads, int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk,
+                                              int64_t idx_stride, double sm_scale, int flags, int num_splits, int *effective_splits,
+                                              float *partial_out, float *partial_lse, void *stream)
+{
+    using namespace dga;
+    bool launch;
+    const int rc = check_sparse_mla_fp8(q, kv_cache, indices, index_offsets, m, heads, num_blocks, page_size, block_stride, topk, idx_stride, flags,
+                                        false, nullptr, nullptr, &launch);
+    if (!launch) return rc;
+    const int page = static_cast<int>(page_size);
+    return launch_sparse_mla_partial<SmlaFp8Rows>(q, kv_cache, block_stride, num_blocks * page_size, page, page_shift_of(page), indices,
+                                                  index_offsets, m, heads, (heads + 63) / 64, topk, idx_stride, sm_scale, flags, num_splits,
+                                                  effective_splits, partial_out, partial_lse, stream);
 }

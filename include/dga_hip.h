@@ -1038,7 +1038,46 @@ int dga_sparse_mla_fwd_fp8(const void *q, const void *kv_cache, const int32_t *i
                            int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride, double sm_scale,
                            int flags, void *out, float *lse, void *stream);
 
-/* The writer of that cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
+/* Split-topk sparse MLA decode: the same attention as several workgroups a token and a merge (csrc/dga_sparse_mla.hip, the same kernel
+ * text; csrc/dga_sparse_mla_merge.hip).  With tiles = ceil(topk / DGA_SPARSE_MLA_TILE) and P = min(num_splits, tiles) splits, split p owns
+ * the contiguous tiles [p tiles / P, (p + 1) tiles / P) of every token's list and writes, in fp32 and not rounded to bf16,
+ *   partial_out[p, t, h, :] = O (1 / l)  (fp32 [P, m, heads, 512] contiguous, 16-byte aligned)
+ *   partial_lse[p, t, h]    = ln sum over the split's valid positions of exp(s_j)  (fp32 [P, m, heads] contiguous)
+ * a split without a valid position +0 and -inf.  Every element of both is written at every call, nothing of a split >= P is touched.
+ * The grid is m head_blocks P workgroups, the splits of one token and head block adjacent; everything else -- arguments, validity rule,
+ * arithmetic per tile, flags -- is dga_sparse_mla_fwd's / dga_sparse_mla_fwd_fp8's, and the fp8 entry's partials are the bf16 entry's on
+ * the dequantised rows, byte for byte.  *effective_splits (may be NULL) receives P.
+ * Checks: the one-pass entry's, in its order (out and lse apart), with the grid's range counting P;  then DGA_E_RANGE (num_splits < 1 or
+ * > DGA_SPARSE_MLA_MAX_SPLITS; num_splits > tiles is clamped to tiles);  DGA_E_NULL (partial_out, partial_lse);  DGA_E_ALIGN (partial_out
+ * not 16-byte, partial_lse not 4-byte aligned).  m == 0 -> DGA_OK with nothing touched.
+ *
+ * dga_sparse_mla_merge: partial_out fp32 [num_splits, m, heads, 512], partial_lse fp32 [num_splits, m, heads] -> out bf16 [m, heads, 512],
+ * lse fp32 [m, heads].  Per (t, h), fp32, nothing contracted, p ascending, L2E = (float)log2 e, LN2 = (float)ln 2:
+ *   M = fmax_p partial_lse[p] from -inf (a NaN is passed over);  mu = M, or 0 when M = -inf;  w_p = v_exp_f32((partial_lse[p] - mu) L2E);
+ *   L = ((w_0 + w_1) + w_2) + ...;  N[c] = ((w_0 po_0[c] + w_1 po_1[c]) + w_2 po_2[c]) + ...;
+ *   L == 0 (a NaN is not 0): out = +0, lse = -inf;  else out[c] = RNE_bf16(N[c] (1 / L)), lse = mu + LN2 v_log_f32(L).
+ * With num_splits = 1 that is out = RNE_bf16(po) and lse = partial_lse: partial + merge reproduces the one-pass entry byte for byte.
+ * One writer per output, no atomics, nothing of a split >= num_splits is read.  One launch; m == 0 returns without one.
+ * Checks: DGA_E_SHAPE (m < 0, heads, num_splits outside [1, DGA_SPARSE_MLA_MAX_SPLITS]);  m == 0 -> DGA_OK;  DGA_E_NULL;  DGA_E_ALIGN
+ * (partial_out or out not 16-byte, partial_lse or lse not 4-byte aligned);  DGA_E_RANGE (the grid beyond int32, the partials beyond int64).
+ *
+ * dga_sparse_mla_splits: the number of splits worth launching, max(1, min(cus / (m head_blocks), tiles / DGA_SPARSE_MLA_MIN_TILES,
+ * DGA_SPARSE_MLA_MAX_SPLITS)) -- as many as there are idle CUs for, none shorter than DGA_SPARSE_MLA_MIN_TILES tiles.  A pure function;
+ * cus <= 0 asks the current device; m, heads or topk < 1 give 1. */
+#define DGA_SPARSE_MLA_MAX_SPLITS 64
+#define DGA_SPARSE_MLA_MIN_TILES 4
+int dga_sparse_mla_fwd_partial(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
+                               int64_t s, int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, int num_splits,
+                               int *effective_splits, float *partial_out, float *partial_lse, void *stream);
+int dga_sparse_mla_fwd_fp8_partial(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m,
+                                   int heads, int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride,
+                                   double sm_scale, int flags, int num_splits, int *effective_splits, float *partial_out, float *partial_lse,
+                                   void *stream);
+int dga_sparse_mla_merge(const float *partial_out, const float *partial_lse, int num_splits, int64_t m, int heads, void *out, float *lse,
+                         void *stream);
+int dga_sparse_mla_splits(int64_t m, int heads, int64_t topk, int cus);
+
+/* The writer of the paged fp8 latent cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
  * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
  * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
  * of the cache receives the 512 codes and 4 scales of dga_cast_to_fp8_1x128 on kv_c's row t (flags: DGA_CAST_UE8M0), byte for byte, and
