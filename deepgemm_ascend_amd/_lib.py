@@ -107,6 +107,16 @@ ALL_TO_ALL_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_int, c_void_p, c_void
 DT_FP16, DT_BF16, DT_FP8_E4M3FN, DT_FP32 = 1, 2, 3, 4
 LAYOUT_ROW_MAJOR, LAYOUT_COLUMN_MAJOR = 0, 1
 
+
+def _smla_args(geometry, outputs):
+    """The four sparse MLA attention entries: q, the rows, indices, offsets, m, heads | the row source's geometry (s, kv_stride or num_blocks,
+    page_size, block_stride) | topk, idx_stride, sm_scale, flags | the outputs of its kind and the stream"""
+    return [c_void_p] * 4 + [c_int64, c_int] + geometry + [c_int64, c_int64, c_double, c_int] + outputs
+
+
+_SMLA_ONE_PASS = [c_void_p] * 3                                            # out, lse, stream
+_SMLA_PARTIAL = [c_int, POINTER(c_int)] + [c_void_p] * 3                   # num_splits, effective_splits, partial_out, partial_lse, stream
+
 # name -> (restype, argtypes): every symbol include/dga_hip.h declares
 SIGNATURES = {
     "dga_infer_shape": (c_int, [POINTER(c_int64), c_int, POINTER(c_int64), c_int, POINTER(c_int64)]),
@@ -192,14 +202,10 @@ SIGNATURES = {
     "dga_cast_to_fp8_1x128_paged": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "dga_indexer_topk": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64,
                                  c_int, c_int64, c_void_p, c_void_p]),
-    "dga_sparse_mla_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_double, c_int,
-                                   c_void_p, c_void_p, c_void_p]),
-    "dga_sparse_mla_fwd_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
-                                       c_double, c_int, c_void_p, c_void_p, c_void_p]),
-    "dga_sparse_mla_fwd_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_double,
-                                           c_int, c_int, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
-    "dga_sparse_mla_fwd_fp8_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
-                                               c_double, c_int, c_int, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
+    "dga_sparse_mla_fwd": (c_int, _smla_args([c_int64] * 2, _SMLA_ONE_PASS)),
+    "dga_sparse_mla_fwd_fp8": (c_int, _smla_args([c_int64] * 3, _SMLA_ONE_PASS)),
+    "dga_sparse_mla_fwd_partial": (c_int, _smla_args([c_int64] * 2, _SMLA_PARTIAL)),
+    "dga_sparse_mla_fwd_fp8_partial": (c_int, _smla_args([c_int64] * 3, _SMLA_PARTIAL)),
     "dga_sparse_mla_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,

@@ -1998,18 +1998,6 @@ SPARSE_MLA_D_V = 512                 # DGA_SPARSE_MLA_D_V
 SPARSE_MLA_MAX_HEADS = 128           # DGA_SPARSE_MLA_MAX_HEADS
 
 
-def _smla_query(q: torch.Tensor, d_v: int, sm_scale) -> Tuple[int, int]:
-    """q, d_v and sm_scale of the sparse MLA operators, checked: (M, Hq)"""
-    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
-             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
-    m, heads = q.shape[0], q.shape[1]
-    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
-             SPARSE_MLA_MAX_HEADS, heads)
-    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
-    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
-    return m, heads
-
-
 def _smla_bf16_rows(q: torch.Tensor, kv: torch.Tensor) -> Tuple[int, int]:
     """kv of sparse_mla_fwd and its split forms, checked (and q's alignment with it): (S, kv_stride)"""
     _require(kv.dtype == torch.bfloat16 and (kv.dim() == 2 or (kv.dim() == 3 and kv.shape[1] == 1)) and kv.shape[-1] == SPARSE_MLA_D_QK,
@@ -2023,18 +2011,6 @@ def _smla_bf16_rows(q: torch.Tensor, kv: torch.Tensor) -> Tuple[int, int]:
     return s, kv_stride
 
 
-def _smla_indices(indices: torch.Tensor, index_offsets: Optional[torch.Tensor], m: int) -> Tuple[int, int]:
-    """indices and index_offsets of the sparse MLA operators, checked: (topk, idx_stride)"""
-    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
-             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
-    topk = indices.shape[-1]
-    idx_stride = indices.stride(0) if m > 1 else topk
-    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
-    if index_offsets is not None:
-        _want(index_offsets, "index_offsets", torch.int32, (m,))
-    return topk, idx_stride
-
-
 def _smla_outputs(out: Optional[torch.Tensor], lse: Optional[torch.Tensor], m: int, heads: int, device):
     """out bfloat16 [M, Hq, 512] and lse float32 [M, Hq]: torch.empty, or the caller's, checked"""
     if out is None:
@@ -2045,6 +2021,51 @@ def _smla_outputs(out: Optional[torch.Tensor], lse: Optional[torch.Tensor], m: i
         lse = torch.empty((m, heads), dtype=torch.float32, device=device)
     else:
         _want(lse, "lse", torch.float32, (m, heads))
+    return out, lse
+
+
+# The six attention forms are one problem -- q, a row source, indices -- run by three bodies: one pass, partials, partials and merge.  The
+# row source is bf16 rows (fp8=False: _smla_bf16_rows) or the paged fp8 latent cache (fp8=True: _mla_fp8_cache, below); the C entries of
+# the two differ by "_fp8" in the name and by the source's geometry among the arguments.
+_SMLA_ENTRY = {False: "sparse_mla_fwd", True: "sparse_mla_fwd_fp8"}
+
+
+def _smla_problem(fp8: bool, q: torch.Tensor, rows: torch.Tensor, indices: torch.Tensor, sm_scale, d_v: int,
+                  index_offsets: Optional[torch.Tensor]):
+    """What every attention form checks, in the order every form reports: q, the rows, indices.  Returns (M, Hq, topk, args): what the
+    bodies size their outputs by, and the arguments that follow the four pointers in every C entry of the family -- M, Hq, the source's
+    geometry, topk, idx_stride, sm_scale.  (The pointers are taken at the launch, behind the guard: a refused call pays for its checks.)"""
+    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
+             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
+    m, heads = q.shape[0], q.shape[1]
+    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
+             SPARSE_MLA_MAX_HEADS, heads)
+    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
+    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    if fp8:
+        geometry = _mla_fp8_cache(rows)
+        _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
+    else:
+        geometry = _smla_bf16_rows(q, rows)
+    _require(indices.dtype == torch.int32 and (indices.dim() == 2 or (indices.dim() == 3 and indices.shape[1] == 1))
+             and indices.shape[0] == m and indices.shape[-1] >= 1, "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1")
+    topk = indices.shape[-1]
+    idx_stride = indices.stride(0) if m > 1 else topk
+    _require((topk == 1 or indices.stride(-1) == 1) and idx_stride >= topk, "indices must have a contiguous last dimension and stride(0) >= topk")
+    if index_offsets is not None:
+        _want(index_offsets, "index_offsets", torch.int32, (m,))
+    return m, heads, topk, (m, heads, *geometry, topk, idx_stride, float(sm_scale))
+
+
+def _smla_one_pass(fp8: bool, q, rows, indices, sm_scale, d_v, index_offsets, out, lse, sync: bool, flags: int, checked=None):
+    """The body of sparse_mla_fwd / sparse_mla_fwd_fp8: the checks (or `checked`, what _smla_problem returned to the split body), the
+    outputs, one launch"""
+    m, heads, _, args = checked or _smla_problem(fp8, q, rows, indices, sm_scale, d_v, index_offsets)
+    name = _SMLA_ENTRY[fp8]
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
+    # (M == 0: the C entry returns before any launch)
+    _launch(name, (q, rows, indices, index_offsets, out, lse), lambda L, stream: getattr(L, "dga_" + name)(
+        q.data_ptr(), rows.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, flags, out.data_ptr(), lse.data_ptr(), stream), sync)
     return out, lse
 
 
@@ -2069,15 +2090,7 @@ def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_
     list order; the weights rounded to bf16 (RNE) for the second product while their sum l stays unrounded fp32; one multiplication by
     1 / l at the end.  One writer per element, no atomics: two runs give the same bytes.  Returns (out, lse), the caller's out= / lse=
     when given.  One launch, capturable -- a replayed graph follows new indices, offsets, kv and q; M == 0 returns without one."""
-    m, heads = _smla_query(q, d_v, sm_scale)
-    s, kv_stride = _smla_bf16_rows(q, kv)
-    topk, idx_stride = _smla_indices(indices, index_offsets, m)
-    out, lse = _smla_outputs(out, lse, m, heads, q.device)
-    # (M == 0: the C entry returns before any launch)
-    _launch("sparse_mla_fwd", (q, kv, indices, index_offsets, out, lse), lambda L, stream: L.dga_sparse_mla_fwd(
-        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale),
-        _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
-    return out, lse
+    return _smla_one_pass(False, q, kv, indices, sm_scale, d_v, index_offsets, out, lse, sync, _flags)
 
 
 SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values
@@ -2118,16 +2131,7 @@ def sparse_mla_fwd_fp8(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.T
     The result is sparse_mla_fwd(q, deq, ...)'s: out and lse byte for byte wherever that is not NaN, NaN in exactly the same elements;
     q, indices, index_offsets, out, lse, the validity rule, the arithmetic and its bounds are that function's.  No byte of an unselected
     row and no byte between a block's last row and the next block is read.  One launch, capturable; M == 0 returns without one."""
-    m, heads = _smla_query(q, d_v, sm_scale)
-    nb, page, stride = _mla_fp8_cache(kv_cache)
-    _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
-    topk, idx_stride = _smla_indices(indices, index_offsets, m)
-    out, lse = _smla_outputs(out, lse, m, heads, q.device)
-    # (M == 0: the C entry returns before any launch)
-    _launch("sparse_mla_fwd_fp8", (q, kv_cache, indices, index_offsets, out, lse), lambda L, stream: L.dga_sparse_mla_fwd_fp8(
-        q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk, idx_stride,
-        float(sm_scale), _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
-    return out, lse
+    return _smla_one_pass(True, q, kv_cache, indices, sm_scale, d_v, index_offsets, out, lse, sync, _flags)
 
 
 SPARSE_MLA_MAX_SPLITS = 64           # DGA_SPARSE_MLA_MAX_SPLITS
@@ -2155,6 +2159,18 @@ def _smla_partials(partial_out, partial_lse, p: int, m: int, heads: int, device)
     return made
 
 
+def _smla_partial(fp8: bool, q, rows, indices, sm_scale, num_splits, d_v, index_offsets, partial_out, partial_lse, sync: bool, flags: int):
+    """The body of sparse_mla_fwd_partial / sparse_mla_fwd_fp8_partial: the checks, num_splits, the partials, one launch"""
+    m, heads, topk, args = _smla_problem(fp8, q, rows, indices, sm_scale, d_v, index_offsets)
+    name = _SMLA_ENTRY[fp8] + "_partial"
+    p = _smla_splits(num_splits, topk)
+    po, pl = _smla_partials(partial_out, partial_lse, p, m, heads, q.device)
+    # (M == 0: the C entry returns before any launch)
+    _launch(name, (q, rows, indices, index_offsets, po, pl), lambda L, stream: getattr(L, "dga_" + name)(
+        q.data_ptr(), rows.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, flags, p, None, po.data_ptr(), pl.data_ptr(), stream), sync)
+    return po, pl
+
+
 def sparse_mla_fwd_partial(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, num_splits: int, d_v: int = 512,
                            index_offsets: Optional[torch.Tensor] = None, partial_out: Optional[torch.Tensor] = None,
                            partial_lse: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2168,16 +2184,7 @@ def sparse_mla_fwd_partial(q: torch.Tensor, kv: torch.Tensor, indices: torch.Ten
     dimension: fresh tensors, or the first P splits of the caller's contiguous float32 [>= P, M, Hq, 512] and [>= P, M, Hq] buffers, of which
     every element is written and nothing beyond them is.  sparse_mla_merge turns them into (out, lse); with P = 1 the two calls give
     sparse_mla_fwd's bytes.  One launch, capturable; two runs give the same bytes; M == 0 returns without a launch."""
-    m, heads = _smla_query(q, d_v, sm_scale)
-    s, kv_stride = _smla_bf16_rows(q, kv)
-    topk, idx_stride = _smla_indices(indices, index_offsets, m)
-    p = _smla_splits(num_splits, topk)
-    po, pl = _smla_partials(partial_out, partial_lse, p, m, heads, q.device)
-    # (M == 0: the C entry returns before any launch)
-    _launch("sparse_mla_fwd_partial", (q, kv, indices, index_offsets, po, pl), lambda L, stream: L.dga_sparse_mla_fwd_partial(
-        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale),
-        _flags, p, None, po.data_ptr(), pl.data_ptr(), stream), sync)
-    return po, pl
+    return _smla_partial(False, q, kv, indices, sm_scale, num_splits, d_v, index_offsets, partial_out, partial_lse, sync, _flags)
 
 
 def sparse_mla_fwd_fp8_partial(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.Tensor, sm_scale: float, num_splits: int, d_v: int = 512,
@@ -2187,17 +2194,7 @@ def sparse_mla_fwd_fp8_partial(q: torch.Tensor, kv_cache: torch.Tensor, indices:
     """sparse_mla_fwd_partial over sparse_mla_fwd_fp8's paged fp8 latent cache, read in place (dga_sparse_mla_fwd_fp8_partial).  kv_cache is
     that function's, everything else sparse_mla_fwd_partial's.  Both partials are sparse_mla_fwd_partial(q, deq, ...)'s byte for byte
     wherever those are not NaN, NaN in exactly the same elements.  One launch, capturable; M == 0 returns without one."""
-    m, heads = _smla_query(q, d_v, sm_scale)
-    nb, page, stride = _mla_fp8_cache(kv_cache)
-    _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
-    topk, idx_stride = _smla_indices(indices, index_offsets, m)
-    p = _smla_splits(num_splits, topk)
-    po, pl = _smla_partials(partial_out, partial_lse, p, m, heads, q.device)
-    # (M == 0: the C entry returns before any launch)
-    _launch("sparse_mla_fwd_fp8_partial", (q, kv_cache, indices, index_offsets, po, pl), lambda L, stream: L.dga_sparse_mla_fwd_fp8_partial(
-        q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk, idx_stride,
-        float(sm_scale), _flags, p, None, po.data_ptr(), pl.data_ptr(), stream), sync)
-    return po, pl
+    return _smla_partial(True, q, kv_cache, indices, sm_scale, num_splits, d_v, index_offsets, partial_out, partial_lse, sync, _flags)
 
 
 def sparse_mla_merge(partial_out: torch.Tensor, partial_lse: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -2233,21 +2230,34 @@ def sparse_mla_num_splits(m: int, heads: int, topk: int, device=None) -> int:
     many splits as the device has idle compute units for, none shorter than four tiles (DGA_SPARSE_MLA_MIN_TILES: DESIGN.md has the sweep
     behind it), 1 once M head_blocks workgroups fill the device.  The CU count is the library's, of `device` or of the current device."""
     _require(all(isinstance(x, int) and x >= 1 for x in (m, heads, topk)), "m, heads and topk must be ints >= 1")
-    if device is None:
-        return int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
-    with torch.cuda.device(device):
+    with _NO_GUARD if device is None else torch.cuda.device(device):
         return int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
 
 
-def _smla_split_launch(name: str, tensors, partial, p: int, m: int, heads: int, out: torch.Tensor, lse: torch.Tensor, sync: bool) -> None:
-    """The tail of the two split operators: partial(L, stream, partial_out, partial_lse) and the merge, two launches on one stream, the
-    partials in scratch of that device and stream"""
+def _smla_split(fp8: bool, q, rows, indices, sm_scale, d_v, index_offsets, num_splits, out, lse, sync: bool):
+    """The body of sparse_mla_fwd_split / sparse_mla_fwd_fp8_split: the checks, once.  num_splits=None: the rule, on q's device; a rule of 1
+    is the one-pass body on what has been checked.  Otherwise the partial entry and the merge, two launches on one stream, the partials in
+    scratch of that device and stream."""
+    checked = m, heads, topk, args = _smla_problem(fp8, q, rows, indices, sm_scale, d_v, index_offsets)
+    if num_splits is None:
+        if q.is_cuda and m:
+            with _device_guard(q):
+                num_splits = int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
+        if num_splits is None or num_splits == 1:
+            return _smla_one_pass(fp8, q, rows, indices, sm_scale, d_v, index_offsets, out, lse, sync, 0, checked)
+    name = _SMLA_ENTRY[fp8]
+    p = _smla_splits(num_splits, topk)
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
+
     def call(L, stream):
-        rows = p * m * heads
-        ws, _ = _scratch("sparse_mla_split", out.device, rows * (SPARSE_MLA_D_V + 1) * 4, stream)
-        pl = None if ws is None else ws + rows * SPARSE_MLA_D_V * 4
-        return partial(L, stream, ws, pl) or L.dga_sparse_mla_merge(ws, pl, p, m, heads, out.data_ptr(), lse.data_ptr(), stream)
-    _launch(name, tensors, call, sync)
+        n = p * m * heads
+        ws, _ = _scratch("sparse_mla_split", out.device, n * (SPARSE_MLA_D_V + 1) * 4, stream)
+        pl = None if ws is None else ws + n * SPARSE_MLA_D_V * 4
+        return getattr(L, "dga_" + name + "_partial")(
+            q.data_ptr(), rows.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, 0, p, None, ws, pl, stream) or L.dga_sparse_mla_merge(
+            ws, pl, p, m, heads, out.data_ptr(), lse.data_ptr(), stream)
+    _launch(name + "_split", (q, rows, indices, index_offsets, out, lse), call, sync)
+    return out, lse
 
 
 def sparse_mla_fwd_split(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
@@ -2260,23 +2270,7 @@ def sparse_mla_fwd_split(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tenso
     capturable -- a replayed graph follows new q, kv, indices and offsets -- with the partials in library scratch of that device and
     stream.  The result is sparse_mla_merge(*sparse_mla_fwd_partial(..., num_splits)) byte for byte; with num_splits=1 sparse_mla_fwd's
     bytes; otherwise within the bound of DESIGN.md, "Split-topk sparse MLA decode", of the exact result; NaN where sparse_mla_fwd has it."""
-    if num_splits is None:
-        m, heads = _smla_query(q, d_v, sm_scale)
-        topk, _ = _smla_indices(indices, index_offsets, m)
-        if q.is_cuda and m:
-            with _device_guard(q):
-                num_splits = int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
-        if num_splits is None or num_splits == 1:
-            return sparse_mla_fwd(q, kv, indices, sm_scale, d_v, index_offsets, out, lse, sync)
-    m, heads = _smla_query(q, d_v, sm_scale)
-    s, kv_stride = _smla_bf16_rows(q, kv)
-    topk, idx_stride = _smla_indices(indices, index_offsets, m)
-    p = _smla_splits(num_splits, topk)
-    out, lse = _smla_outputs(out, lse, m, heads, q.device)
-    _smla_split_launch("sparse_mla_fwd_split", (q, kv, indices, index_offsets, out, lse), lambda L, stream, po, pl: L.dga_sparse_mla_fwd_partial(
-        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, s, kv_stride, topk, idx_stride, float(sm_scale), 0,
-        p, None, po, pl, stream), p, m, heads, out, lse, sync)
-    return out, lse
+    return _smla_split(False, q, kv, indices, sm_scale, d_v, index_offsets, num_splits, out, lse, sync)
 
 
 def sparse_mla_fwd_fp8_split(q: torch.Tensor, kv_cache: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
@@ -2285,25 +2279,7 @@ def sparse_mla_fwd_fp8_split(q: torch.Tensor, kv_cache: torch.Tensor, indices: t
                              sync: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """sparse_mla_fwd_split over sparse_mla_fwd_fp8's paged fp8 latent cache: num_splits=None and a rule of 1 is sparse_mla_fwd_fp8 itself, an
     explicit num_splits runs sparse_mla_fwd_fp8_partial and sparse_mla_merge.  The result is sparse_mla_fwd_split(q, deq, ...)'s."""
-    if num_splits is None:
-        m, heads = _smla_query(q, d_v, sm_scale)
-        topk, _ = _smla_indices(indices, index_offsets, m)
-        if q.is_cuda and m:
-            with _device_guard(q):
-                num_splits = int(_lib.lib().dga_sparse_mla_splits(m, heads, topk, 0))
-        if num_splits is None or num_splits == 1:
-            return sparse_mla_fwd_fp8(q, kv_cache, indices, sm_scale, d_v, index_offsets, out, lse, sync)
-    m, heads = _smla_query(q, d_v, sm_scale)
-    nb, page, stride = _mla_fp8_cache(kv_cache)
-    _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
-    topk, idx_stride = _smla_indices(indices, index_offsets, m)
-    p = _smla_splits(num_splits, topk)
-    out, lse = _smla_outputs(out, lse, m, heads, q.device)
-    _smla_split_launch("sparse_mla_fwd_fp8_split", (q, kv_cache, indices, index_offsets, out, lse),
-                       lambda L, stream, po, pl: L.dga_sparse_mla_fwd_fp8_partial(
-                           q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), _ptr(index_offsets), m, heads, nb, page, stride, topk,
-                           idx_stride, float(sm_scale), 0, p, None, po, pl, stream), p, m, heads, out, lse, sync)
-    return out, lse
+    return _smla_split(True, q, kv_cache, indices, sm_scale, d_v, index_offsets, num_splits, out, lse, sync)
 
 
 def mla_kv_cast_to_fp8_paged(kv_c: torch.Tensor, k_pe: torch.Tensor, kv_cache: torch.Tensor, slot_mapping: torch.Tensor,

@@ -429,99 +429,85 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     }
 }
 
-// The launch both entries end in: one workgroup per token and block of 64 heads, the grid walked XCD by XCD unless it is linear
-template <typename Cache>
-static int launch_sparse_mla(const void *q, const void *kv, int64_t kv_stride, int64_t s_rows, int page_size, int page_shift, const int32_t *indices,
-                             const int32_t *index_offsets, int64_t m, int heads, int head_blocks, int64_t topk, int64_t idx_stride,
-                             double sm_scale, int flags, void *out, float *lse, void *stream)
-{
-    const int64_t blocks = m * head_blocks;
-    const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
-    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
-    const int64_t grid = linear ? blocks : chunk * 8;
-    hipLaunchKernelGGL((sparse_mla_fwd_kernel<Cache, false>), dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0,
-                       static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(q), kv, kv_stride, s_rows, indices, idx_stride,
-                       static_cast<int>(topk), index_offsets, heads, head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634),
-                       static_cast<uint16_t *>(out), lse, page_size, page_shift, static_cast<float *>(nullptr), static_cast<float *>(nullptr), 1,
-                       static_cast<int64_t>(0));
-    return record_hip(hipGetLastError());
-}
+// What the four entries hand to the one check and the one launch below: the call without its row source and outputs, the row source, and
+// the outputs of either kind.  A new row source is one more maker of SmlaSource with its clauses in the four questions the check asks; a
+// new axis of the kernel is one more template parameter of the launch.
+struct SmlaCall {
+    const void *q;
+    const int32_t *indices, *index_offsets;
+    int64_t m;
+    int heads;
+    int64_t topk, idx_stride;
+    double sm_scale;
+    int flags;
+    void *stream;
+};
 
-// The partial entries' tail: num_splits and the partial pointers checked, then m head_blocks P workgroups over the same mapping
-template <typename Cache>
-static int launch_sparse_mla_partial(const void *q, const void *kv, int64_t kv_stride, int64_t s_rows, int page_size, int page_shift,
-                                     const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int head_blocks, int64_t topk,
-                                     int64_t idx_stride, double sm_scale, int flags, int num_splits, int *effective_splits, float *partial_out,
-                                     float *partial_lse, void *stream)
-{
-    if (num_splits < 1 || num_splits > DGA_SPARSE_MLA_MAX_SPLITS) return DGA_E_RANGE;
-    const int64_t tiles = (topk + SMLA_TILE - 1) / SMLA_TILE;
-    const int splits = num_splits > tiles ? static_cast<int>(tiles) : num_splits;
-    if (m > (0x7FFFFFFFll - 8) / head_blocks / splits) return DGA_E_RANGE;
-    if (!partial_out || !partial_lse) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(partial_out) % 16 || reinterpret_cast<uintptr_t>(partial_lse) % 4) return DGA_E_ALIGN;
-    if (effective_splits) *effective_splits = splits;
-    const int64_t blocks = m * head_blocks * splits;
-    const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
-    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
-    const int64_t grid = linear ? blocks : chunk * 8;
-    hipLaunchKernelGGL((sparse_mla_fwd_kernel<Cache, true>), dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0,
-                       static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(q), kv, kv_stride, s_rows, indices, idx_stride,
-                       static_cast<int>(topk), index_offsets, heads, head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634),
-                       static_cast<uint16_t *>(nullptr), static_cast<float *>(nullptr), page_size, page_shift, partial_out, partial_lse, splits,
-                       m * heads);
-    return record_hip(hipGetLastError());
-}
-
-// The checks of the bf16 entries, in the documented order; *launch is set when a launch is to follow (not for m == 0).  outputs: out and
-// lse are this entry's (the partial entries check theirs afterwards)
-static int check_sparse_mla(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int64_t s,
-                            int64_t kv_stride, int64_t topk, int64_t idx_stride, int flags, bool outputs, const void *out, const void *lse,
-                            bool *launch)
-{
-    *launch = false;
-    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
-    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || s < 1 || topk < 1 || kv_stride < SMLA_D || idx_stride < topk)
-        return DGA_E_SHAPE;
-    if (m == 0) return DGA_OK;
-    if (!q || !kv || !indices || (outputs && (!out || !lse))) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv) % 16 || (outputs && reinterpret_cast<uintptr_t>(out) % 16) ||
-        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 ||
-        (outputs && reinterpret_cast<uintptr_t>(lse) % 4) || kv_stride % 8)
-        return DGA_E_ALIGN;
-    const int head_blocks = (heads + 63) / 64;
-    if (s > 0x7FFFFFFFll || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
-    if (kv_stride > 0x7FFFFFFFFFFFFFFFll / 2 / s || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
-    *launch = true;
-    return DGA_OK;
-}
-
-// The same checks in the same order, the cache's own in the place of kv's: s = num_blocks page_size rows, block_stride bytes a block
-static int check_sparse_mla_fp8(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
-                                int64_t num_blocks, int64_t page_size, int64_t block_stride, int64_t topk, int64_t idx_stride, int flags,
-                                bool outputs, const void *out, const void *lse, bool *launch)
-{
-    *launch = false;
-    if (flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
-    // (block_stride / 656 < page_size says block_stride < 656 page_size without the product)
-    if (m < 0 || heads < 16 || heads > DGA_SPARSE_MLA_MAX_HEADS || heads % 16 || num_blocks < 1 || page_size < 1 || topk < 1 ||
-        block_stride / SMLA_FP8_ROW < page_size || idx_stride < topk)
-        return DGA_E_SHAPE;
-    if (m == 0) return DGA_OK;
-    if (!q || !kv_cache || !indices || (outputs && (!out || !lse))) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(kv_cache) % 16 || (outputs && reinterpret_cast<uintptr_t>(out) % 16) ||
-        reinterpret_cast<uintptr_t>(indices) % 4 || reinterpret_cast<uintptr_t>(index_offsets) % 4 ||
-        (outputs && reinterpret_cast<uintptr_t>(lse) % 4) || block_stride % 16)
-        return DGA_E_ALIGN;
-    const int head_blocks = (heads + 63) / 64;
-    if (num_blocks > 0x7FFFFFFFll / page_size || topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || m > (0x7FFFFFFFll - 8) / head_blocks)
-        return DGA_E_RANGE;
-    if (block_stride > 0x7FFFFFFFFFFFFFFFll / num_blocks || idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / m) return DGA_E_RANGE;
-    *launch = true;
-    return DGA_OK;
-}
+// count units of page_size rows each, `stride` apart: bf16 rows (s of them, one a unit, kv_stride elements apart) or the blocks of the
+// paged fp8 cache (block_stride bytes apart).  The range clauses divide by what the shape clause has vouched for.
+struct SmlaSource {
+    bool fp8;
+    const void *rows;
+    int64_t count, page_size, stride;
+    // (stride / 656 < page_size says block_stride < 656 page_size without the product)
+    bool shape() const { return count >= 1 && page_size >= 1 && (fp8 ? stride / SMLA_FP8_ROW >= page_size : stride >= SMLA_D); }
+    bool aligned() const { return reinterpret_cast<uintptr_t>(rows) % 16 == 0 && stride % (fp8 ? 16 : 8) == 0; }
+    bool rows_in_range() const { return count <= 0x7FFFFFFFll / page_size; }
+    bool bytes_in_range() const { return stride <= 0x7FFFFFFFFFFFFFFFll / (fp8 ? 1 : 2) / count; }
+};
 
 static int page_shift_of(int page) { return (page & (page - 1)) == 0 ? __builtin_ctz(page) : -1; }
+
+// The checks of all four entries, in the documented order: flags, shape, m == 0, null, alignment, range; *launch is set when a launch is
+// to follow (not for m == 0).  out and lse are the one-pass entries' (null and unchecked for the partial ones, whose outputs the launch
+// checks afterwards).
+static int check_sparse_mla(const SmlaCall &c, const SmlaSource &src, bool outputs, const void *out, const void *lse, bool *launch)
+{
+    *launch = false;
+    if (c.flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
+    if (c.m < 0 || c.heads < 16 || c.heads > DGA_SPARSE_MLA_MAX_HEADS || c.heads % 16 || !src.shape() || c.topk < 1 || c.idx_stride < c.topk)
+        return DGA_E_SHAPE;
+    if (c.m == 0) return DGA_OK;
+    if (!c.q || !src.rows || !c.indices || (outputs && (!out || !lse))) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(c.q) % 16 || !src.aligned() || reinterpret_cast<uintptr_t>(out) % 16 ||
+        reinterpret_cast<uintptr_t>(c.indices) % 4 || reinterpret_cast<uintptr_t>(c.index_offsets) % 4 || reinterpret_cast<uintptr_t>(lse) % 4)
+        return DGA_E_ALIGN;
+    const int head_blocks = (c.heads + 63) / 64;
+    if (!src.rows_in_range() || c.topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || c.m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
+    if (!src.bytes_in_range() || c.idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / c.m) return DGA_E_RANGE;
+    *launch = true;
+    return DGA_OK;
+}
+
+// The launch all four entries end in: one workgroup per token, block of 64 heads and split, the grid walked XCD by XCD unless it is linear.
+// PARTIAL: num_splits and the partial pointers are checked first, behind the common checks; *effective_splits is written on success only.
+template <typename Cache, bool PARTIAL>
+static int launch_sparse_mla(const SmlaCall &c, const SmlaSource &src, void *out, float *lse, int num_splits, int *effective_splits,
+                             float *partial_out, float *partial_lse)
+{
+    const int head_blocks = (c.heads + 63) / 64;
+    int splits = 1;
+    if constexpr (PARTIAL) {
+        if (num_splits < 1 || num_splits > DGA_SPARSE_MLA_MAX_SPLITS) return DGA_E_RANGE;
+        const int64_t tiles = (c.topk + SMLA_TILE - 1) / SMLA_TILE;
+        splits = num_splits > tiles ? static_cast<int>(tiles) : num_splits;
+        if (c.m > (0x7FFFFFFFll - 8) / head_blocks / splits) return DGA_E_RANGE;
+        if (!partial_out || !partial_lse) return DGA_E_NULL;
+        if (reinterpret_cast<uintptr_t>(partial_out) % 16 || reinterpret_cast<uintptr_t>(partial_lse) % 4) return DGA_E_ALIGN;
+        if (effective_splits) *effective_splits = splits;
+    }
+    const int64_t blocks = c.m * head_blocks * splits;
+    const bool linear = (c.flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
+    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
+    const int64_t grid = linear ? blocks : chunk * 8;
+    const int page = src.fp8 ? static_cast<int>(src.page_size) : 0;
+    hipLaunchKernelGGL((sparse_mla_fwd_kernel<Cache, PARTIAL>), dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0,
+                       static_cast<hipStream_t>(c.stream), static_cast<const uint16_t *>(c.q), src.rows, src.stride, src.count * src.page_size,
+                       c.indices, c.idx_stride, static_cast<int>(c.topk), c.index_offsets, c.heads, head_blocks, blocks, chunk,
+                       static_cast<float>(c.sm_scale * 1.4426950408889634), static_cast<uint16_t *>(out), lse, page,
+                       src.fp8 ? page_shift_of(page) : 0, partial_out, partial_lse, splits, PARTIAL ? c.m * c.heads : static_cast<int64_t>(0));
+    return record_hip(hipGetLastError());
+}
 
 }  // namespace dga
 
@@ -530,11 +516,11 @@ extern "C" int dga_sparse_mla_fwd(const void *q, const void *kv, const int32_t *
                                   float *lse, void *stream)
 {
     using namespace dga;
+    const SmlaCall c{q, indices, index_offsets, m, heads, topk, idx_stride, sm_scale, flags, stream};
+    const SmlaSource src{false, kv, s, 1, kv_stride};
     bool launch;
-    const int rc = check_sparse_mla(q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, flags, true, out, lse, &launch);
-    if (!launch) return rc;
-    return launch_sparse_mla<SmlaBf16Rows>(q, kv, kv_stride, s, 0, 0, indices, index_offsets, m, heads, (heads + 63) / 64, topk, idx_stride,
-                                           sm_scale, flags, out, lse, stream);
+    const int rc = check_sparse_mla(c, src, true, out, lse, &launch);
+    return launch ? launch_sparse_mla<SmlaBf16Rows, false>(c, src, out, lse, 1, nullptr, nullptr, nullptr) : rc;
 }
 
 extern "C" int dga_sparse_mla_fwd_fp8(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m,
@@ -542,26 +528,24 @@ extern "C" int dga_sparse_mla_fwd_fp8(const void *q, const void *kv_cache, const
                                       double sm_scale, int flags, void *out, float *lse, void *stream)
 {
     using namespace dga;
+    const SmlaCall c{q, indices, index_offsets, m, heads, topk, idx_stride, sm_scale, flags, stream};
+    const SmlaSource src{true, kv_cache, num_blocks, page_size, block_stride};
     bool launch;
-    const int rc = check_sparse_mla_fp8(q, kv_cache, indices, index_offsets, m, heads, num_blocks, page_size, block_stride, topk, idx_stride, flags,
-                                        true, out, lse, &launch);
-    if (!launch) return rc;
-    const int page = static_cast<int>(page_size);
-    return launch_sparse_mla<SmlaFp8Rows>(q, kv_cache, block_stride, num_blocks * page_size, page, page_shift_of(page), indices, index_offsets, m,
-                                          heads, (heads + 63) / 64, topk, idx_stride, sm_scale, flags, out, lse, stream);
+    const int rc = check_sparse_mla(c, src, true, out, lse, &launch);
+    return launch ? launch_sparse_mla<SmlaFp8Rows, false>(c, src, out, lse, 1, nullptr, nullptr, nullptr) : rc;
 }
 
-// Split-topk decode: the same checks, then num_splits and the partial pointers (launch_sparse_mla_partial)
+// Split-topk decode: the same checks, then num_splits and the partial pointers (launch_sparse_mla<Cache, true>)
 extern "C" int dga_sparse_mla_fwd_partial(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
                                           int64_t s, int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags,
                                           int num_splits, int *effective_splits, float *partial_out, float *partial_lse, void *stream)
 {
     using namespace dga;
+    const SmlaCall c{q, indices, index_offsets, m, heads, topk, idx_stride, sm_scale, flags, stream};
+    const SmlaSource src{false, kv, s, 1, kv_stride};
     bool launch;
-    const int rc = check_sparse_mla(q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, flags, false, nullptr, nullptr, &launch);
-    if (!launch) return rc;
-    return launch_sparse_mla_partial<SmlaBf16Rows>(q, kv, kv_stride, s, 0, 0, indices, index_offsets, m, heads, (heads + 63) / 64, topk, idx_stride,
-                                                   sm_scale, flags, num_splits, effective_splits, partial_out, partial_lse, stream);
+    const int rc = check_sparse_mla(c, src, false, nullptr, nullptr, &launch);
+    return launch ? launch_sparse_mla<SmlaBf16Rows, true>(c, src, nullptr, nullptr, num_splits, effective_splits, partial_out, partial_lse) : rc;
 }
 
 extern "C" int dga_sparse_mla_fwd_fp8_partial(const void *q, const void *kv_cache, const int32_t *indices, const int32_t *index_offsets, int64_t m,
@@ -570,12 +554,9 @@ extern "C" int dga_sparse_mla_fwd_fp8_partial(const void *q, const void *kv_cach
                                               float *partial_out, float *partial_lse, void *stream)
 {
     using namespace dga;
+    const SmlaCall c{q, indices, index_offsets, m, heads, topk, idx_stride, sm_scale, flags, stream};
+    const SmlaSource src{true, kv_cache, num_blocks, page_size, block_stride};
     bool launch;
-    const int rc = check_sparse_mla_fp8(q, kv_cache, indices, index_offsets, m, heads, num_blocks, page_size, block_stride, topk, idx_stride, flags,
-                                        false, nullptr, nullptr, &launch);
-    if (!launch) return rc;
-    const int page = static_cast<int>(page_size);
-    return launch_sparse_mla_partial<SmlaFp8Rows>(q, kv_cache, block_stride, num_blocks * page_size, page, page_shift_of(page), indices,
-                                                  index_offsets, m, heads, (heads + 63) / 64, topk, idx_stride, sm_scale, flags, num_splits,
-                                                  effective_splits, partial_out, partial_lse, stream);
+    const int rc = check_sparse_mla(c, src, false, nullptr, nullptr, &launch);
+    return launch ? launch_sparse_mla<SmlaFp8Rows, true>(c, src, nullptr, nullptr, num_splits, effective_splits, partial_out, partial_lse) : rc;
 }

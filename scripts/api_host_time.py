@@ -50,6 +50,20 @@ def rows():
     dest = torch.randperm(64 * 8, device=dev).view(64, 8)
     yield "combine_tokens T64 k8 H512", lambda: dga.combine_tokens(src, dest, weights)
 
+    # sparse MLA decode, one token: beside a kernel of some 20 us (profiles/sparse_mla_split_timing.txt) the wrapper's checks count
+    hq, topk, s = 16, 64, 64
+    q, kv, cache = bf(1, hq, 576), bf(s, 576), torch.zeros(1, 64, 1, 656, dtype=torch.uint8, device=dev)
+    idx = torch.randperm(s, device=dev)[:topk].to(torch.int32).view(1, topk)
+    o, l = torch.empty(1, hq, 512, dtype=torch.bfloat16, device=dev), torch.empty(1, hq, dtype=torch.float32, device=dev)
+    po, pl = dga.sparse_mla_fwd_partial(q, kv, idx, 0.04, 2)
+    shape = f"M1 Hq{hq} topk{topk}, out="
+    yield f"sparse_mla_fwd {shape}", lambda: dga.sparse_mla_fwd(q, kv, idx, 0.04, out=o, lse=l)
+    yield f"sparse_mla_fwd_fp8 {shape}", lambda: dga.sparse_mla_fwd_fp8(q, cache, idx, 0.04, out=o, lse=l)
+    yield f"sparse_mla_fwd_split(num_splits=None) {shape}", lambda: dga.sparse_mla_fwd_split(q, kv, idx, 0.04, out=o, lse=l)
+    yield f"sparse_mla_fwd_split(num_splits=2) {shape}", lambda: dga.sparse_mla_fwd_split(q, kv, idx, 0.04, num_splits=2, out=o, lse=l)
+    yield f"sparse_mla_fwd_fp8_split(num_splits=2) {shape}", lambda: dga.sparse_mla_fwd_fp8_split(q, cache, idx, 0.04, num_splits=2, out=o, lse=l)
+    yield f"sparse_mla_merge P2 M1 Hq{hq}, out=", lambda: dga.sparse_mla_merge(po, pl, out=o, lse=l)
+
 
 def load_ext(path):
     if not path:

@@ -55,7 +55,26 @@ VALID = {
     "router_balance_loss_backward": lambda: dict(dloss=z(2), counts=z(2, 8, dtype=I32), scores=z(6, 8), k=2, score_func="sigmoid", seq_len=3,
                                                  add_to=z(6, 8), out=z(6, 8, dtype=F16)),
     "router_bias_update": lambda: dict(bias=z(8), counts=z(2, 8, dtype=I32), rate=0.5),
+    "mla_kv_cast_to_fp8_paged": lambda: dict(kv_c=z(3, 512, dtype=BF16), k_pe=z(3, 64, dtype=BF16), kv_cache=z(2, 2, 1, 656, dtype=U8),
+                                             slot_mapping=z(3, dtype=I64)),
+    "sparse_mla_merge": lambda: dict(partial_out=z(2, 2, 16, 512), partial_lse=z(2, 2, 16), out=z(2, 16, 512, dtype=BF16), lse=z(2, 16)),
 }
+
+
+def _smla_valid(fp8, outputs):
+    """the attention forms of sparse MLA: M = 2, Hq = 16, 4 rows, topk = 40 (two tiles, so that num_splits = 2 is P = 2)"""
+    rows = dict(kv_cache=z(2, 2, 1, 656, dtype=U8)) if fp8 else dict(kv=z(4, 576, dtype=BF16))
+    return lambda: dict(q=z(2, 16, 576, dtype=BF16), **rows, indices=z(2, 40, dtype=I32), sm_scale=0.1, index_offsets=z(2, dtype=I32),
+                        **outputs())
+
+
+SMLA_OUT = lambda: dict(out=z(2, 16, 512, dtype=BF16), lse=z(2, 16))
+SMLA_PARTIAL = lambda: dict(num_splits=2, partial_out=z(2, 2, 16, 512), partial_lse=z(2, 2, 16))
+SMLA_SPLIT = lambda: dict(num_splits=2, **SMLA_OUT())
+SMLA_FORMS = [("sparse_mla_fwd", False, SMLA_OUT), ("sparse_mla_fwd_fp8", True, SMLA_OUT), ("sparse_mla_fwd_partial", False, SMLA_PARTIAL),
+              ("sparse_mla_fwd_fp8_partial", True, SMLA_PARTIAL), ("sparse_mla_fwd_split", False, SMLA_SPLIT),
+              ("sparse_mla_fwd_fp8_split", True, SMLA_SPLIT)]
+VALID.update({name: _smla_valid(fp8, outputs) for name, fp8, outputs in SMLA_FORMS})
 
 
 def call(name, kw):
@@ -97,6 +116,155 @@ def _dense(name, out, sfb, more=()):
         rows.append((name, fault, msg.format(out=out, sfb=sfb, name=name)))
     return rows
 
+
+# Sparse MLA: six attention forms (one-pass, partial, split; over bf16 rows or the paged fp8 cache), the merge, and the cache's writer.
+# The forms check in one order -- q, the rows, indices, num_splits, the outputs -- and share the wording of each part.
+Q_MSG = "q must be a contiguous bfloat16 [M, Hq, 576] tensor"
+KV_MSG = "kv must be a bfloat16 [S, 576] or [S, 1, 576] tensor"
+KV_STRIDE_MSG = "kv must have a contiguous last dimension and a stride(0) >= 576 that is a multiple of 8, got %d"
+QKV_ALIGN_MSG = "q and kv must be 16-byte aligned"
+CACHE_ROWS_MSG = "kv_cache must have contiguous rows, 656 bytes apart inside a block (stride(1) == 656)"
+CACHE_STRIDE_MSG = "kv_cache blocks must be at least %d bytes apart and a multiple of 16, got stride(0) = %d"
+IDX_MSG = "indices must be an int32 [M, topk] or [M, 1, topk] tensor with topk >= 1"
+IDX_STRIDE_MSG = "indices must have a contiguous last dimension and stride(0) >= topk"
+SPLITS_MSG = "num_splits must be an int in [1, 64], got %s"
+OUT_MSG, LSE_MSG = "out must be contiguous bfloat16 [2, 16, 512]", "lse must be contiguous float32 [2, 16]"
+PO_MSG, PL_MSG = "partial_out must be contiguous float32 [>= 2, 2, 16, 512]", "partial_lse must be contiguous float32 [>= 2, 2, 16]"
+
+
+def misaligned(*shape, dtype, by=8):
+    """a contiguous tensor that starts `by` bytes past a 16-byte boundary"""
+    skip, n = by // z(1, dtype=dtype).element_size(), 1
+    for d in shape:
+        n *= d
+    return z(skip + n, dtype=dtype)[skip:].view(*shape)
+
+
+SMLA_QUERY = [
+    (dict(q=z(2, 16, 576)), Q_MSG), (dict(q=z(16, 576, dtype=BF16)), Q_MSG), (dict(q=z(2, 16, 512, dtype=BF16)), Q_MSG),
+    (dict(q=z(2, 32, 576, dtype=BF16)[:, ::2]), Q_MSG), (dict(q=z(2, 8, 576, dtype=BF16)), "Hq must be a multiple of 16 in [16, 128], got 8"),
+    (dict(q=z(2, 144, 576, dtype=BF16)), "Hq must be a multiple of 16 in [16, 128], got 144"), (dict(d_v=576), "d_v must be 512"),
+    (dict(sm_scale="0.1"), "sm_scale must be a number"),
+]
+SMLA_BF16_ROWS = [
+    (dict(kv=z(4, 576, dtype=F16)), KV_MSG), (dict(kv=z(2, 2, 576, dtype=BF16)), KV_MSG), (dict(kv=z(4, 512, dtype=BF16)), KV_MSG),
+    (dict(kv=z(0, 576, dtype=BF16)), "kv must have between 1 and 2^31 - 1 rows, got 0"),
+    (dict(kv=torch.empty((1 << 31, 576), dtype=BF16, device="meta")), "kv must have between 1 and 2^31 - 1 rows, got 2147483648"),
+    (dict(kv=z(4, 1152, dtype=BF16)[:, ::2]), KV_STRIDE_MSG % 1152), (dict(kv=z(4, 580, dtype=BF16)[:, :576]), KV_STRIDE_MSG % 580),
+    (dict(kv=z(4 * 576, dtype=BF16).as_strided((4, 576), (568, 1))), KV_STRIDE_MSG % 568),
+    (dict(kv=misaligned(4, 576, dtype=BF16)), QKV_ALIGN_MSG), (dict(q=misaligned(2, 16, 576, dtype=BF16)), QKV_ALIGN_MSG),
+    # two faults: q before the rows, the rows before indices
+    (dict(q=z(2, 16, 576), kv=z(4, 512, dtype=BF16)), Q_MSG), (dict(sm_scale=None, kv=z(0, 576, dtype=BF16)), "sm_scale must be a number"),
+    (dict(kv=z(4, 580, dtype=BF16)[:, :576], indices=z(2, 40, dtype=I64)), KV_STRIDE_MSG % 580),
+    (dict(q=misaligned(2, 16, 576, dtype=BF16), indices=z(2, 0, dtype=I32)), QKV_ALIGN_MSG),
+]
+MLA_FP8_CACHE = [   # _mla_fp8_cache, in its order: the attention forms' and the writer's
+    (dict(kv_cache=z(2, 2, 1, 656, dtype=torch.int8)), "kv_cache must be uint8, got torch.int8"),
+    (dict(kv_cache=z(2, 2, 656, dtype=U8)), "kv_cache must be [num_blocks, page_size, 1, 656] or [S, 656], got [2, 2, 656]"),
+    (dict(kv_cache=z(4, 576, dtype=U8)), "kv_cache must be [num_blocks, page_size, 1, 656] or [S, 656], got [4, 576]"),
+    (dict(kv_cache=z(2, 1, 2, 656, dtype=U8)), "kv_cache must be [num_blocks, page_size, 1, 656] or [S, 656], got [2, 1, 2, 656]"),
+    (dict(kv_cache=z(0, 2, 1, 656, dtype=U8)), "kv_cache must have at least one row"), (dict(kv_cache=z(2, 0, 1, 656, dtype=U8)), "kv_cache must have at least one row"),
+    (dict(kv_cache=z(2, 2, 1, 672, dtype=U8)[..., :656]), CACHE_ROWS_MSG), (dict(kv_cache=z(4, 1312, dtype=U8)[:, ::2]), CACHE_ROWS_MSG),
+    (dict(kv_cache=z(2, 2 * 656 + 8, dtype=U8)[:, :2 * 656].view(2, 2, 1, 656)), CACHE_STRIDE_MSG % (1312, 1320)),
+    (dict(kv_cache=z(4, 664, dtype=U8)[:, :656]), CACHE_STRIDE_MSG % (656, 664)),
+    (dict(kv_cache=z(2 * 2 * 656, dtype=U8).as_strided((2, 2, 1, 656), (656 + 16, 656, 656, 1))), CACHE_STRIDE_MSG % (1312, 672)),
+    (dict(kv_cache=torch.empty((1 << 25, 64, 1, 656), dtype=U8, device="meta")), "kv_cache must have fewer than 2^31 rows, got 33554432 x 64"),
+    (dict(kv_cache=misaligned(2, 2, 1, 656, dtype=U8)), "kv_cache must be 16-byte aligned"),
+    # two faults inside the cache: the shape before the stride before the alignment
+    (dict(kv_cache=z(2, 2 * 656 + 8, dtype=torch.int8)[:, :2 * 656].view(2, 2, 1, 656)), "kv_cache must be uint8, got torch.int8"),
+    (dict(kv_cache=misaligned(2, 2 * 656 + 8, dtype=U8)[:, :2 * 656].view(2, 2, 1, 656)), CACHE_STRIDE_MSG % (1312, 1320)),
+]
+SMLA_FP8_ROWS = MLA_FP8_CACHE + [
+    (dict(q=misaligned(2, 16, 576, dtype=BF16)), "q must be 16-byte aligned"),
+    # two faults: q before the cache, the cache before q's alignment before indices
+    (dict(q=z(2, 16, 576), kv_cache=z(4, 576, dtype=U8)), Q_MSG), (dict(d_v=256, kv_cache=z(0, 2, 1, 656, dtype=U8)), "d_v must be 512"),
+    (dict(kv_cache=misaligned(2, 2, 1, 656, dtype=U8), q=misaligned(2, 16, 576, dtype=BF16)), "kv_cache must be 16-byte aligned"),
+    (dict(kv_cache=z(4, 664, dtype=U8)[:, :656], indices=z(2, 40, dtype=I64)), CACHE_STRIDE_MSG % (656, 664)),
+    (dict(q=misaligned(2, 16, 576, dtype=BF16), indices=z(2, 0, dtype=I32)), "q must be 16-byte aligned"),
+]
+SMLA_INDICES = [
+    (dict(indices=z(2, 40, dtype=I64)), IDX_MSG), (dict(indices=z(40, dtype=I32)), IDX_MSG), (dict(indices=z(1, 40, dtype=I32)), IDX_MSG),
+    (dict(indices=z(2, 0, dtype=I32)), IDX_MSG), (dict(indices=z(2, 2, 40, dtype=I32)), IDX_MSG),
+    (dict(indices=z(2, 80, dtype=I32)[:, ::2]), IDX_STRIDE_MSG), (dict(indices=z(2 * 40, dtype=I32).as_strided((2, 40), (32, 1))), IDX_STRIDE_MSG),
+    (dict(index_offsets=z(2, dtype=I64)), "index_offsets must be contiguous int32 [2]"),
+    (dict(index_offsets=z(3, dtype=I32)), "index_offsets must be contiguous int32 [2]"),
+    (dict(indices=z(2, 40, dtype=I64), index_offsets=z(3, dtype=I32)), IDX_MSG),
+]
+SMLA_NUM_SPLITS = [
+    (dict(num_splits=0), SPLITS_MSG % "0"), (dict(num_splits=65), SPLITS_MSG % "65"), (dict(num_splits=2.0), SPLITS_MSG % "2.0"),
+    (dict(num_splits=True), SPLITS_MSG % "True"),
+    # two faults: indices before num_splits
+    (dict(indices=z(2, 80, dtype=I32)[:, ::2], num_splits=0), IDX_STRIDE_MSG), (dict(index_offsets=z(3, dtype=I32), num_splits=65), "index_offsets must be contiguous int32 [2]"),
+]
+SMLA_OUTPUTS = {
+    SMLA_OUT: [
+        (dict(out=z(2, 16, 576, dtype=BF16)), OUT_MSG), (dict(out=z(2, 16, 512)), OUT_MSG), (dict(out=z(2, 16, 1024, dtype=BF16)[..., ::2]), OUT_MSG),
+        (dict(lse=z(2, 16, 1)), LSE_MSG), (dict(lse=z(2, 16, dtype=BF16)), LSE_MSG),
+        # two faults: indices before the outputs, out before lse
+        (dict(index_offsets=z(3, dtype=I32), out=z(2, 16, 512)), "index_offsets must be contiguous int32 [2]"),
+        (dict(out=z(2, 16, 512), lse=z(2, 16, 1)), OUT_MSG),
+    ],
+    SMLA_PARTIAL: SMLA_NUM_SPLITS + [
+        (dict(num_splits=None), SPLITS_MSG % "None"),
+        (dict(partial_out=z(2, 2, 16, 512, dtype=BF16)), PO_MSG), (dict(partial_out=z(1, 2, 16, 512)), PO_MSG),
+        (dict(partial_out=z(2, 2, 16, 576)), PO_MSG), (dict(partial_out=z(2, 16, 512)), PO_MSG), (dict(partial_out=z(4, 2, 16, 512)[::2]), PO_MSG),
+        (dict(partial_lse=z(2, 2, 16, dtype=F64)), PL_MSG), (dict(partial_lse=z(2, 2, 16, 1)), PL_MSG), (dict(partial_lse=z(1, 2, 16)), PL_MSG),
+        # a list of one tile: P = min(num_splits, 1), and the buffers need hold no more
+        (dict(indices=z(2, 32, dtype=I32), partial_out=z(1, 2, 16, 576)), "partial_out must be contiguous float32 [>= 1, 2, 16, 512]"),
+        # two faults: num_splits before partial_out before partial_lse
+        (dict(num_splits=0, partial_out=z(2, 16, 512)), SPLITS_MSG % "0"), (dict(partial_out=z(2, 16, 512), partial_lse=z(1, 2, 16)), PO_MSG),
+    ],
+    SMLA_SPLIT: SMLA_NUM_SPLITS + [
+        (dict(out=z(2, 16, 576, dtype=BF16)), OUT_MSG), (dict(lse=z(2, 16, dtype=BF16)), LSE_MSG),
+        # two faults: num_splits before out before lse
+        (dict(num_splits=65, out=z(2, 16, 512)), SPLITS_MSG % "65"), (dict(out=z(2, 16, 512), lse=z(2, 16, 1)), OUT_MSG),
+    ],
+}
+
+
+def _smla(name, fp8, outputs):
+    rows = SMLA_QUERY + (SMLA_FP8_ROWS if fp8 else SMLA_BF16_ROWS) + SMLA_INDICES + SMLA_OUTPUTS[outputs]
+    if outputs is SMLA_SPLIT:
+        # num_splits=None checks what an explicit num_splits checks, in the same order.  NEW ORDER: the rows with one fault in q's alignment
+        # or the row source and one in indices report the former since the forms share one checker; until then None alone checked indices
+        # first, and reported the latter.
+        rows = rows + [({**fault, "num_splits": None}, msg) for fault, msg in rows if "num_splits" not in fault]
+    return [(name, fault, msg) for fault, msg in rows]
+
+
+PO4_MSG = "partial_out must be a contiguous float32 [P, M, Hq, 512] tensor"
+SMLA_CASES = [row for form in SMLA_FORMS for row in _smla(*form)] + [
+    ("sparse_mla_merge", dict(partial_out=z(2, 2, 16, 512, dtype=F64)), PO4_MSG), ("sparse_mla_merge", dict(partial_out=z(2, 16, 512)), PO4_MSG),
+    ("sparse_mla_merge", dict(partial_out=z(2, 2, 16, 576)), PO4_MSG), ("sparse_mla_merge", dict(partial_out=z(4, 2, 16, 512)[::2]), PO4_MSG),
+    ("sparse_mla_merge", dict(partial_out=z(0, 2, 16, 512), partial_lse=z(0, 2, 16)), "partial_out must hold between 1 and 64 splits, got 0"),
+    ("sparse_mla_merge", dict(partial_out=torch.empty((65, 2, 16, 512), device="meta")), "partial_out must hold between 1 and 64 splits, got 65"),
+    ("sparse_mla_merge", dict(partial_out=z(2, 2, 24, 512)), "Hq must be a multiple of 16 in [16, 128], got 24"),
+    ("sparse_mla_merge", dict(partial_lse=z(2, 2, 16, dtype=F64)), "partial_lse must be contiguous float32 [2, 2, 16]"),
+    ("sparse_mla_merge", dict(partial_lse=z(1, 2, 16)), "partial_lse must be contiguous float32 [2, 2, 16]"),
+    ("sparse_mla_merge", dict(partial_lse=z(2, 2, 32)[..., ::2]), "partial_lse must be contiguous float32 [2, 2, 16]"),
+    ("sparse_mla_merge", dict(partial_out=misaligned(2, 2, 16, 512, dtype=F32)), "partial_out must be 16-byte aligned"),
+    ("sparse_mla_merge", dict(out=z(2, 16, 576, dtype=BF16)), OUT_MSG), ("sparse_mla_merge", dict(out=z(2, 16, 512)), OUT_MSG),
+    ("sparse_mla_merge", dict(lse=z(2, 2, 16)), LSE_MSG), ("sparse_mla_merge", dict(lse=z(2, 16, dtype=F16)), LSE_MSG),
+    # two faults: partial_out before partial_lse before its alignment before out before lse
+    ("sparse_mla_merge", dict(partial_out=z(2, 2, 16, 576), partial_lse=z(1, 2, 16)), PO4_MSG),
+    ("sparse_mla_merge", dict(partial_out=misaligned(2, 2, 16, 512, dtype=F32), partial_lse=z(1, 2, 16)), "partial_lse must be contiguous float32 [2, 2, 16]"),
+    ("sparse_mla_merge", dict(partial_lse=z(1, 2, 16), out=z(2, 16, 512)), "partial_lse must be contiguous float32 [2, 2, 16]"),
+    ("sparse_mla_merge", dict(partial_out=misaligned(2, 2, 16, 512, dtype=F32), out=z(2, 16, 512)), "partial_out must be 16-byte aligned"),
+    ("sparse_mla_merge", dict(out=z(2, 16, 512), lse=z(2, 2, 16)), OUT_MSG),
+] + [("mla_kv_cast_to_fp8_paged", fault, msg) for fault, msg in [
+    (dict(kv_c=z(3, 576, dtype=BF16)), "kv_c must be a [T, 512] tensor"), (dict(kv_c=z(512, dtype=BF16)), "kv_c must be a [T, 512] tensor"),
+    (dict(k_pe=z(3, 128, dtype=BF16)), "k_pe must be a [T, 64] tensor with kv_c's T"), (dict(k_pe=z(2, 64, dtype=BF16)), "k_pe must be a [T, 64] tensor with kv_c's T"),
+    (dict(kv_c=z(3, 512, dtype=F64), k_pe=z(3, 64, dtype=F64)), "kv_c must be float32, bfloat16 or float16"),
+    (dict(k_pe=z(3, 64, dtype=F16)), "kv_c and k_pe must have one dtype, got torch.bfloat16 and torch.float16"),
+    (dict(kv_c=z(3, 1024, dtype=BF16)[:, ::2]), "kv_c must have a contiguous last dimension, a 16-byte aligned base and rows a multiple of 16 bytes apart"),
+    (dict(kv_c=z(3, 516, dtype=BF16)[:, :512]), "kv_c must have a contiguous last dimension, a 16-byte aligned base and rows a multiple of 16 bytes apart"),
+    (dict(k_pe=z(3, 72, dtype=BF16)[:, 4:68]), "k_pe must have a contiguous last dimension, a 16-byte aligned base and rows a multiple of 16 bytes apart"),
+    (dict(slot_mapping=z(3, dtype=I32)), "slot_mapping must be contiguous int64 [3]"), (dict(slot_mapping=z(2, dtype=I64)), "slot_mapping must be contiguous int64 [3]"),
+    (dict(slot_mapping=z(6, dtype=I64)[::2]), "slot_mapping must be contiguous int64 [3]"),
+    # two faults: the inputs before the cache before slot_mapping
+    (dict(k_pe=z(3, 72, dtype=BF16)[:, 4:68], kv_cache=z(4, 576, dtype=U8)), "k_pe must have a contiguous last dimension, a 16-byte aligned base and rows a multiple of 16 bytes apart"),
+    (dict(kv_cache=z(0, 2, 1, 656, dtype=U8), slot_mapping=z(3, dtype=I32)), "kv_cache must have at least one row"),
+] + MLA_FP8_CACHE]
 
 CASES = _dense("gemm_fp8_fp8_bf16_nt", "bfloat16", "[1,2]") + _dense("gemm_fp8_fp8_fp32_nt", "float32", "[1,2]", FP32_C) + \
     _dense("wgrad_gemm_fp8_fp8_fp32_nt", "float32", "[8,2]", FP32_C) + [
@@ -265,7 +433,7 @@ CASES = _dense("gemm_fp8_fp8_bf16_nt", "bfloat16", "[1,2]") + _dense("gemm_fp8_f
     ("router_bias_update", dict(counts=z(2, 8)), "counts must be a contiguous int32 [B, 8] tensor"),
     ("router_bias_update", dict(bias=z(2, 4), counts=z(2, 8)), "bias must be a contiguous float32 [E] tensor"),
     ("router_bias_update", dict(bias=z(7), counts=z(2, 8, dtype=I32)), "counts must be a contiguous int32 [B, 7] tensor"),
-]
+] + SMLA_CASES
 
 
 def whole(msg: str) -> str:

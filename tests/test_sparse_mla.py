@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import sparse_mla_ref as R
+from sparse_mla_support import _args
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -76,13 +77,6 @@ def test_c_entry_checks_before_any_launch(dga):
     assert a != 0 and a == call(q=p + 2) == call(out=p + 4) == call(lse=p + 2) == call(off=p + 1) == call(kv_stride=580)
     r = call(flags=2)
     assert r != 0 and r == call(s=1 << 31) and r not in codes and r != a
-
-
-def _args(m=2, h=16, s=8, topk=4):
-    q = torch.zeros((m, h, 576), dtype=torch.bfloat16)
-    kv = torch.zeros((s, 576), dtype=torch.bfloat16)
-    idx = torch.zeros((m, topk), dtype=torch.int32)
-    return q, kv, idx
 
 
 def test_every_refusal_comes_from_the_wrapper(dga):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import sparse_mla_fp8_ref as F
+from sparse_mla_support import _aligned, _bad_caches, _cache, _refused
 
 ROOT = Path(__file__).resolve().parent.parent
 SCALES = (1.0, 0.3, 2.0 ** -140, 2.0 ** 120, 0.0, -1.5, np.inf, np.nan)   # ordinary, subnormal products, bf16 overflow, zero, negative, inf, NaN
@@ -117,11 +118,6 @@ def test_symbols_are_declared_exported_and_in_the_table(dga):
     assert _lib.lib().dga_abi_version() == 7                            # the change only adds
 
 
-def _aligned():
-    buf = ctypes.create_string_buffer(8192 + 64)
-    return buf, (ctypes.addressof(buf) + 63) & ~63
-
-
 def test_attention_c_entry_checks_before_any_launch(dga):
     """the C entry's own refusals and M == 0, none of which touches a device"""
     from deepgemm_ascend_amd import _lib
@@ -171,45 +167,8 @@ def test_writer_c_entry_checks_before_any_launch(dga):
     assert r == call(tokens=1 << 40, ld_c=1 << 24)                      # tokens times the row pitch leaves int64
 
 
-def _cache(nb=3, page=4, pad=0):
-    return torch.zeros((nb, page * 656 + pad), dtype=torch.uint8)[:, :page * 656].view(nb, page, 1, 656)
-
-
 def _args(m=2, h=16, topk=4):
     return torch.zeros((m, h, 576), dtype=torch.bfloat16), _cache(), torch.zeros((m, topk), dtype=torch.int32)
-
-
-def _refused(dga, bad, accepted):
-    for what, call in bad.items():
-        with pytest.raises(dga.DGAError) as e:
-            call()
-        assert "HIP device" not in str(e.value), what                  # refused for what it is, not for where it lives
-    for call in accepted:                                               # nothing to refuse but the device
-        with pytest.raises(dga.DGAError) as e:
-            call()
-        assert "HIP device" in str(e.value)
-
-
-def _bad_caches():
-    """every way a cache is refused, by name"""
-    return {
-        "cache dtype": _cache().view(torch.int8),
-        "cache rank": torch.zeros((3, 4, 656), dtype=torch.uint8),
-        "cache row width": torch.zeros((3, 4, 1, 640), dtype=torch.uint8),
-        "cache flat row width": torch.zeros((12, 576), dtype=torch.uint8),
-        "cache third dimension": torch.zeros((3, 2, 2, 656), dtype=torch.uint8),
-        "cache empty": _cache()[:0],
-        "cache stride(1) != 656": torch.zeros((3, 4, 1, 672), dtype=torch.uint8)[..., :656],
-        "cache stride(3) != 1": torch.zeros((3, 4, 1, 1312), dtype=torch.uint8)[..., ::2],
-        "cache flat stride(1) != 1": torch.zeros((12, 1312), dtype=torch.uint8)[:, ::2],
-        "cache block stride not a multiple of 16": _cache(pad=8),
-        "cache flat stride not a multiple of 16": torch.zeros((12, 664), dtype=torch.uint8)[:, :656],
-        "cache block stride too small": torch.zeros((3 * 4 * 656,), dtype=torch.uint8).as_strided((3, 4, 1, 656), (3 * 656 + 16, 656, 656, 1)),
-        "cache flat stride too small": torch.zeros((12 * 656,), dtype=torch.uint8).as_strided((12, 656), (640, 1)),
-        "cache misaligned": torch.zeros((3 * 4 * 656 + 8,), dtype=torch.uint8)[8:].view(3, 4, 1, 656),
-        "cache of 2^31 rows": torch.empty((1 << 25, 64, 1, 656), dtype=torch.uint8, device="meta"),      # (no storage behind it)
-        "cache flat of 2^31 rows": torch.empty((1 << 31, 656), dtype=torch.uint8, device="meta"),
-    }
 
 
 def test_every_attention_refusal_comes_from_the_wrapper(dga):

@@ -12,7 +12,7 @@ import torch
 
 import sparse_mla_fp8_ref as F
 import sparse_mla_ref as R
-from test_sparse_mla_gpu import _bf16, _filled
+from sparse_mla_support import _bf16, _deq_tensor, _filled, _nan16, _nan32, _view, _written_by_the_writer
 
 pytestmark = pytest.mark.gpu
 
@@ -22,35 +22,12 @@ FINITE_SCALES = (1.0, 0.3, 2.0 ** -140, 2.0 ** 120, 0.0, -1.5)          # the fi
 
 # ---- helpers ----------------------------------------------------------------------------------------------------------------------
 
-def _view(t, page):
-    """the operators' view of a uint8 [num_blocks, block_stride] buffer: [num_blocks, page, 1, 656], or flat [S, 656] for page 1"""
-    nb = t.shape[0]
-    return t[:, :F.ROW] if page == 1 else t[:, :page * F.ROW].view(nb, page, 1, F.ROW)
-
-
-def _bf16_from_bits(bits):
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(torch.bfloat16).cuda()
-
-
-def _deq_tensor(buf, page):
-    """bf16 [S, 576] on the device: the values the rows of a host buffer stand for"""
-    return _bf16_from_bits(F.deq_bits(*F.unpack(buf, page)))
-
-
 def _call(fn, q, kv, idx, scale, offsets=None):
     """(out bits uint16, lse bits uint32) of one call into pre-filled outputs"""
     out, lse = _filled(q.shape[0], q.shape[1])
     got = fn(q, kv, idx, scale, 512, offsets, out=out, lse=lse, sync=True)
     assert got[0].data_ptr() == out.data_ptr() and got[1].data_ptr() == lse.data_ptr()
     return out.view(torch.int16).cpu().numpy().view(np.uint16), lse.cpu().numpy().view(np.uint32)
-
-
-def _nan16(b):
-    return (b & 0x7FFF) > 0x7F80
-
-
-def _nan32(b):
-    return (b & 0x7FFFFFFF) > 0x7F800000
 
 
 def _same(got, want):
@@ -80,17 +57,6 @@ def _random_rows(s, seed, finite=True):
     scales = (rng.choice([-1.0, 1.0], (s, F.GROUPS)) * 2.0 ** rng.uniform(-9, -5, (s, F.GROUPS))).astype(np.float32)
     rope = F.bf16_bits(rng.standard_normal((s, F.ROPE)).astype(np.float32))
     return codes, scales, rope
-
-
-def _written_by_the_writer(dga, kv, page, pad, fill=0):
-    """the host copy of a cache of ceil(S / page) blocks, `pad` bytes between blocks, whose rows 0 .. S - 1 the new writer wrote from the
-    bf16 rows kv [S, 576]"""
-    s = kv.shape[0]
-    nb, stride = F.geometry(s, page, page * F.ROW + pad)
-    t = torch.full((nb, stride), fill, dtype=torch.uint8, device="cuda")
-    both = _bf16(kv)
-    dga.mla_kv_cast_to_fp8_paged(both[:, :F.LATENT], both[:, F.LATENT:], _view(t, page), torch.arange(s, dtype=torch.int64, device="cuda"), sync=True)
-    return t.cpu().numpy()
 
 
 _CASES = {}

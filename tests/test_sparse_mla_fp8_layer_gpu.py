@@ -12,10 +12,10 @@ import indexer_topk_ref as T
 import paged_mqa_logits_ref as P
 import sparse_mla_fp8_ref as F
 import sparse_mla_ref as R
+from sparse_mla_support import _check
+from sparse_mla_support import _filled as _filled_attention
 from test_indexer_layer_gpu import _decode_case
 from test_mqa_logits_gpu import _dev, _filled
-from test_sparse_mla_gpu import _check
-from test_sparse_mla_gpu import _filled as _filled_attention
 
 pytestmark = pytest.mark.gpu
 

@@ -15,29 +15,12 @@ import pytest
 import torch
 
 import sparse_mla_ref as R
+from sparse_mla_support import _bf16, _check, _filled
 
 pytestmark = pytest.mark.gpu
 
 HEADS = (16, 64, 128)                                                 # one wave of a workgroup, a whole workgroup, two
 ALL_HEADS = R.ALL_HEADS                                               # and every count between: a partly filled first or second block
-NAN_FILL = 0x7FC12345
-NAN_FILL16 = 0x7FC5
-
-
-def _bf16(a):
-    """the bf16 device tensor of float values that bf16 holds exactly (NaN allowed)"""
-    a = np.asarray(a, dtype=np.float32)
-    t = torch.from_numpy(a.copy()).to(torch.bfloat16)
-    assert np.array_equal(t.float().numpy(), a, equal_nan=True)
-    return t.cuda()
-
-
-def _filled(m, h):
-    out = torch.full((m, h, R.D_V), NAN_FILL16, dtype=torch.int16, device="cuda").view(torch.bfloat16)
-    lse = torch.full((m, h), NAN_FILL, dtype=torch.int32, device="cuda").view(torch.float32)
-    return out, lse
-
-
 def _run(dga, q, kv, idx, scale, offsets=None):
     """(out as float64, its bits, lse float32) of one call into pre-filled outputs"""
     out, lse = _filled(q.shape[0], q.shape[1])
@@ -45,27 +28,6 @@ def _run(dga, q, kv, idx, scale, offsets=None):
     assert got[0].data_ptr() == out.data_ptr() and got[1].data_ptr() == lse.data_ptr()
     bits = out.view(torch.int16).cpu().numpy().view(np.uint16)
     return out.float().cpu().numpy().astype(np.float64), bits, lse.cpu().numpy()
-
-
-def _check(got, ref, scale, topk, exact_rows=(), out_bound=True):
-    """every element of out and lse against the reference: +0 and -inf for a token without a valid position, the bits of
-    RNE_bf16(out) on the tokens of exact_rows, the derived bounds everywhere (out_bound=False: of lse alone -- the bound of out is
-    relative to the weighted values and has no room for weights that underflow fp32, which the one-hot case is made of)"""
-    out, bits, lse = got
-    assert not np.isnan(out).any() and not np.isnan(lse).any()
-    empty = ref["count"] == 0
-    assert (bits[empty] == 0).all() and np.isneginf(lse[empty]).all()
-    assert np.isfinite(lse[~empty]).all()
-    for t in exact_rows:
-        assert np.array_equal(bits[t], R.bf16_bits(ref["out"][t])), t
-    err, bar = np.abs(out - ref["out"]), R.bound_out(ref, scale, topk)
-    if not out_bound:
-        err = np.zeros_like(err)
-    assert (err <= bar).all(), (int((err > bar).sum()), np.argwhere(err > bar)[:4])
-    lerr, lbar = np.abs(lse[~empty].astype(np.float64) - ref["lse"][~empty]), R.bound_lse(ref, scale, topk)[~empty]
-    assert (lerr <= lbar).all(), (float((lerr / lbar).max()), np.argwhere(lerr > lbar)[:4])
-    both = float((err[~empty] / np.maximum(bar[~empty], 1e-300)).max()) if (~empty).any() else 0.0
-    return both, float((lerr / lbar).max()) if (~empty).any() else 0.0
 
 
 def _int_kv(s, width, seed, keep=None):

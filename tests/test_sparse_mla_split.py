@@ -13,6 +13,8 @@ import torch
 
 import sparse_mla_ref as R
 import sparse_mla_split_ref as X
+from sparse_mla_support import _aligned, _bad_caches, _cache, _refused
+from sparse_mla_support import _args as _short_args
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "deepgemm_ascend_amd" / "csrc"
@@ -108,11 +110,6 @@ def test_symbols_are_declared_exported_and_in_the_table(dga):
     assert _lib.lib().dga_abi_version() == 7                            # the change only adds
 
 
-def _aligned():
-    buf = ctypes.create_string_buffer(8192 + 64)
-    return buf, (ctypes.addressof(buf) + 63) & ~63
-
-
 def test_partial_c_entries_check_in_the_documented_order_before_any_launch(dga):
     """the one-pass entries' refusals with their statuses, then num_splits, then the partial pointers; none touches a device"""
     from deepgemm_ascend_amd import _lib
@@ -175,23 +172,8 @@ def test_merge_c_entry_checks_shape_null_alignment_range(dga):
 
 # ---- the wrappers --------------------------------------------------------------------------------------------------------------------
 
-def _refused(dga, bad, accepted):
-    for what, call in bad.items():
-        with pytest.raises(dga.DGAError) as e:
-            call()
-        assert "HIP device" not in str(e.value), what                  # refused for what it is, not for where it lives
-    for call in accepted:                                               # nothing to refuse but the device
-        with pytest.raises(dga.DGAError) as e:
-            call()
-        assert "HIP device" in str(e.value)
-
-
-def _cache(nb=3, page=4):
-    return torch.zeros((nb, page, 1, 656), dtype=torch.uint8)
-
-
-def _args(m=2, h=16, s=8, topk=70):
-    return torch.zeros((m, h, 576), dtype=torch.bfloat16), torch.zeros((s, 576), dtype=torch.bfloat16), torch.zeros((m, topk), dtype=torch.int32)
+def _args(m=2, h=16, s=8, topk=70):                                     # (three tiles: num_splits up to 3 is the effective P)
+    return _short_args(m, h, s, topk)
 
 
 def _operand_refusals(fn, q, kv, idx, bad_kv, *more):
@@ -219,9 +201,7 @@ def _operand_refusals(fn, q, kv, idx, bad_kv, *more):
 BAD_KV = {"kv dtype": torch.zeros((8, 576), dtype=torch.float16), "kv d": torch.zeros((8, 512), dtype=torch.bfloat16),
           "kv stride 580": torch.zeros((8, 580), dtype=torch.bfloat16)[:, :576], "kv empty": torch.zeros((0, 576), dtype=torch.bfloat16),
           "an fp8 cache": _cache()}
-BAD_CACHE = {"cache dtype": _cache().view(torch.int8), "cache rank": torch.zeros((3, 4, 656), dtype=torch.uint8),
-             "cache row width": torch.zeros((3, 4, 1, 640), dtype=torch.uint8), "a bf16 cache": torch.zeros((8, 576), dtype=torch.bfloat16),
-             "cache block stride not a multiple of 16": torch.zeros((3, 4 * 656 + 8), dtype=torch.uint8)[:, :4 * 656].view(3, 4, 1, 656)}
+BAD_CACHE = {**_bad_caches(), "a bf16 cache": torch.zeros((8, 576), dtype=torch.bfloat16)}
 
 
 @pytest.mark.parametrize("cache", ("bf16", "fp8"))

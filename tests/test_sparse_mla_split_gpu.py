@@ -12,8 +12,7 @@ import torch
 import sparse_mla_fp8_ref as F
 import sparse_mla_ref as R
 import sparse_mla_split_ref as X
-from test_sparse_mla_fp8_gpu import _deq_tensor, _nan16, _nan32, _view, _written_by_the_writer
-from test_sparse_mla_gpu import NAN_FILL, _bf16, _filled
+from sparse_mla_support import NAN_FILL, _bf16, _deq_tensor, _filled, _nan16, _nan32, _view, _written_by_the_writer
 
 pytestmark = pytest.mark.gpu
 
