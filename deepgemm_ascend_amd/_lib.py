@@ -109,13 +109,14 @@ LAYOUT_ROW_MAJOR, LAYOUT_COLUMN_MAJOR = 0, 1
 
 
 def _smla_args(geometry, outputs):
-    """The four sparse MLA attention entries: q, the rows, indices, offsets, m, heads | the row source's geometry (s, kv_stride or num_blocks,
+    """The sparse MLA attention entries (four forward forms, the backward): q, the rows, indices, offsets, m, heads | the row source's geometry (s, kv_stride or num_blocks,
     page_size, block_stride) | topk, idx_stride, sm_scale, flags | the outputs of its kind and the stream"""
     return [c_void_p] * 4 + [c_int64, c_int] + geometry + [c_int64, c_int64, c_double, c_int] + outputs
 
 
 _SMLA_ONE_PASS = [c_void_p] * 3                                            # out, lse, stream
 _SMLA_PARTIAL = [c_int, POINTER(c_int)] + [c_void_p] * 3                   # num_splits, effective_splits, partial_out, partial_lse, stream
+_SMLA_BACKWARD = [c_void_p] * 5 + [c_int64, c_void_p]                      # out, d_out, lse, dq, dkv, dkv_stride, stream
 
 # name -> (restype, argtypes): every symbol include/dga_hip.h declares
 SIGNATURES = {
@@ -206,6 +207,7 @@ SIGNATURES = {
     "dga_sparse_mla_fwd_fp8": (c_int, _smla_args([c_int64] * 3, _SMLA_ONE_PASS)),
     "dga_sparse_mla_fwd_partial": (c_int, _smla_args([c_int64] * 2, _SMLA_PARTIAL)),
     "dga_sparse_mla_fwd_fp8_partial": (c_int, _smla_args([c_int64] * 3, _SMLA_PARTIAL)),
+    "dga_sparse_mla_bwd": (c_int, _smla_args([c_int64] * 2, _SMLA_BACKWARD)),
     "dga_sparse_mla_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,

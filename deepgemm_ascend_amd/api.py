@@ -2093,6 +2093,49 @@ def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_
     return _smla_one_pass(False, q, kv, indices, sm_scale, d_v, index_offsets, out, lse, sync, _flags)
 
 
+def sparse_mla_bwd(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, indices: torch.Tensor, lse: torch.Tensor,
+                   sm_scale: float, d_v: int = 512, index_offsets: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
+                   dkv: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The backward of sparse_mla_fwd (dga_sparse_mla_bwd): (dq, dkv) from d_out.  q, kv, indices, index_offsets, sm_scale and d_v are
+    sparse_mla_fwd's, with its validity rule;  out and d_out bfloat16 [M, Hq, 512], contiguous and 16-byte aligned, lse float32 [M, Hq]
+    contiguous -- out and lse normally what the forward returned;  dq bfloat16 [M, Hq, 576] (torch.empty when None; every element is
+    written);  dkv float32 [S, 576] with a contiguous last dimension, stride(0) >= 576 and a multiple of 4, 16-byte aligned: the kernel
+    ADDS INTO it -- None allocates torch.zeros, a caller's tensor accumulates over calls (a sequence fed in chunks of M).
+    Over the valid positions, r_j the row:  p_j = exp(s_j - lse[m, h]);  delta = sum_c out[m, h, c] d_out[m, h, c];
+    dP_j = sum_c d_out[m, h, c] kv[r_j, c] (c < 512);  dS_j = sm_scale p_j (dP_j - delta);  dq[m, h, :] = sum_j dS_j kv[r_j, :576];
+    dkv[r_j, :576] += sum_h dS_j q[m, h, :];  dkv[r_j, :512] += sum_h p_j d_out[m, h, :].  An invalid position dereferences nothing and
+    adds nothing; a duplicate counts once per position; a token with no valid position gets dq = +0 and touches no row of dkv whatever
+    its lse holds; no row of dkv that no valid position names, and no byte beyond column 575, is written.
+    Arithmetic: the scores and dP on the matrix pipe in fp32, p and dS rounded to bf16 (RNE) for the three products that follow, all
+    sums fp32, dq rounded once at the end, dkv added by the hardware's fp32 atomic add.
+    Determinism: dq is byte-reproducible.  dkv is NOT -- the first output of this package that is not: the order of the atomic adds onto
+    a row varies from run to run, so two runs agree to fp32 rounding of the sum, and bit for bit only where the contributions to an
+    element are exactly summable or there is a single one.
+    Returns (dq, dkv).  One launch, capturable, everything read on the device; M == 0 returns without one."""
+    m, heads, _, args = _smla_problem(False, q, kv, indices, sm_scale, d_v, index_offsets)
+    s = kv.shape[0]
+    _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    _want(d_out, "d_out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    _want(lse, "lse", torch.float32, (m, heads))
+    if dq is None:
+        dq = torch.empty((m, heads, SPARSE_MLA_D_QK), dtype=torch.bfloat16, device=q.device)
+    else:
+        _want(dq, "dq", torch.bfloat16, (m, heads, SPARSE_MLA_D_QK))
+    if dkv is None:
+        dkv = torch.zeros((s, SPARSE_MLA_D_QK), dtype=torch.float32, device=q.device)
+    _require(dkv.dtype == torch.float32 and dkv.dim() == 2 and tuple(dkv.shape) == (s, SPARSE_MLA_D_QK),
+             "dkv must be a float32 [S, %d] tensor with kv's S = %d rows", SPARSE_MLA_D_QK, s)
+    dkv_stride = dkv.stride(0) if s > 1 else SPARSE_MLA_D_QK
+    _require(dkv.stride(1) == 1 and dkv_stride >= SPARSE_MLA_D_QK and dkv_stride % 4 == 0,
+             "dkv must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", SPARSE_MLA_D_QK, dkv_stride)
+    _require(all(x.data_ptr() % 16 == 0 for x in (out, d_out, dq, dkv)), "out, d_out, dq and dkv must be 16-byte aligned")
+    # (M == 0: the C entry returns before any launch)
+    _launch("sparse_mla_bwd", (q, kv, indices, index_offsets, out, d_out, lse, dq, dkv), lambda L, stream: L.dga_sparse_mla_bwd(
+        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, _flags, out.data_ptr(), d_out.data_ptr(),
+        lse.data_ptr(), dq.data_ptr(), dkv.data_ptr(), dkv_stride, stream), sync)
+    return dq, dkv
+
+
 SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values
 
 

@@ -82,4 +82,55 @@ void complete_from_menu(dga_tiling_t &t);
 struct MenuEntry;
 const MenuEntry *find_build(int bm, int bn, int stages = 0, bool loaders = false);
 }
+
+// What the sparse MLA attention entries (dga_sparse_mla.hip: the four forward forms; dga_sparse_mla_bwd.hip: the backward) hand to the one
+// check below and to their launches: the call without its row source and outputs, the row source, and the outputs of either kind.  A new
+// row source is one more maker of SmlaSource with its clauses in the four questions the check asks.
+struct SmlaCall {
+    const void *q;
+    const int32_t *indices, *index_offsets;
+    int64_t m;
+    int heads;
+    int64_t topk, idx_stride;
+    double sm_scale;
+    int flags;
+    void *stream;
+};
+
+// count units of page_size rows each, `stride` apart: bf16 rows (s of them, one a unit, kv_stride elements apart) or the blocks of the
+// paged fp8 cache (block_stride bytes apart).  The range clauses divide by what the shape clause has vouched for.
+struct SmlaSource {
+    bool fp8;
+    const void *rows;
+    int64_t count, page_size, stride;
+    // (stride / 656 < page_size says block_stride < 656 page_size without the product)
+    bool shape() const
+    {
+        return count >= 1 && page_size >= 1 && (fp8 ? stride / DGA_SPARSE_MLA_FP8_ROW_BYTES >= page_size : stride >= DGA_SPARSE_MLA_D_QK);
+    }
+    bool aligned() const { return reinterpret_cast<uintptr_t>(rows) % 16 == 0 && stride % (fp8 ? 16 : 8) == 0; }
+    bool rows_in_range() const { return count <= 0x7FFFFFFFll / page_size; }
+    bool bytes_in_range() const { return stride <= 0x7FFFFFFFFFFFFFFFll / (fp8 ? 1 : 2) / count; }
+};
+
+// The checks of every entry, in the documented order: flags, shape, m == 0, null, alignment, range; *launch is set when a launch is
+// to follow (not for m == 0).  out and lse are the one-pass forward entries' (null and unchecked for the partial ones and the backward,
+// which check their own outputs afterwards).
+inline int check_sparse_mla(const SmlaCall &c, const SmlaSource &src, bool outputs, const void *out, const void *lse, bool *launch)
+{
+    *launch = false;
+    if (c.flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
+    if (c.m < 0 || c.heads < 16 || c.heads > DGA_SPARSE_MLA_MAX_HEADS || c.heads % 16 || !src.shape() || c.topk < 1 || c.idx_stride < c.topk)
+        return DGA_E_SHAPE;
+    if (c.m == 0) return DGA_OK;
+    if (!c.q || !src.rows || !c.indices || (outputs && (!out || !lse))) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(c.q) % 16 || !src.aligned() || reinterpret_cast<uintptr_t>(out) % 16 ||
+        reinterpret_cast<uintptr_t>(c.indices) % 4 || reinterpret_cast<uintptr_t>(c.index_offsets) % 4 || reinterpret_cast<uintptr_t>(lse) % 4)
+        return DGA_E_ALIGN;
+    const int head_blocks = (c.heads + 63) / 64;
+    if (!src.rows_in_range() || c.topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || c.m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
+    if (!src.bytes_in_range() || c.idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / c.m) return DGA_E_RANGE;
+    *launch = true;
+    return DGA_OK;
+}
 }  // namespace dga

@@ -46,59 +46,18 @@
 
 #include "dga_hip.h"
 #include "dga_internal.hpp"
+#include "dga_sparse_mla_device.hpp"
 
 #pragma clang fp contract(off)
 
 namespace dga {
-
-constexpr int SMLA_D = DGA_SPARSE_MLA_D_QK;                  // 576
-constexpr int SMLA_DV = DGA_SPARSE_MLA_D_V;                  // 512
-constexpr int SMLA_THREADS = 256;
-constexpr int SMLA_TILE = 32;                                // positions of one gathered tile
-constexpr int SMLA_ROW_BYTES = SMLA_D * 2 + 32;              // 1184: 296 dwords = 40 mod 64, both kinds of read are free of bank conflicts
-constexpr int SMLA_CHUNKS = SMLA_D / 8;                      // 16-byte chunks of a row: 72
-constexpr int SMLA_STAGE = SMLA_CHUNKS / 8;                  // chunks a thread gathers per tile: 9, of one row
-constexpr int SMLA_KSTEPS = SMLA_D / 32;                     // 18
-constexpr int SMLA_CTILES = SMLA_DV / 16;                    // 32
-static_assert(SMLA_KSTEPS % 2 == 0 && SMLA_CTILES % 4 == 0 && SMLA_TILE * 8 == SMLA_THREADS && SMLA_CHUNKS == 8 * SMLA_STAGE && SMLA_D % 32 == 0 && SMLA_DV % 16 == 0, "the kernel's geometry");
-
-typedef float smla_v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 smla_v8bf __attribute__((ext_vector_type(8)));
-typedef __bf16 smla_v4bf __attribute__((ext_vector_type(4)));
-typedef short smla_v4s __attribute__((ext_vector_type(4)));
-typedef short smla_v8s __attribute__((ext_vector_type(8)));
-typedef uint32_t smla_v4u __attribute__((ext_vector_type(4)));
-typedef float smla_v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 smla_v2bf __attribute__((ext_vector_type(2)));
 
 constexpr int SMLA_FP8_ROW = DGA_SPARSE_MLA_FP8_ROW_BYTES;   // 656: 512 codes, 4 fp32 scales, 64 bf16
 constexpr int SMLA_FP8_SLICES = 8;                           // 16-byte chunks of bf16 a thread makes of its 64 codes per tile
 static_assert(SMLA_FP8_ROW == SMLA_DV + 16 + 2 * (SMLA_D - SMLA_DV) && SMLA_FP8_ROW % 16 == 0 && SMLA_FP8_SLICES == SMLA_CTILES / 4 &&
               SMLA_FP8_SLICES + 1 == SMLA_STAGE, "the fp8 row, and eight 16-byte chunks of bf16 from its codes");
 
-// What the kernel gathers from.  A cache says where thread gsub (of the eight a row has) starts in row r, what it loads from there
-// (RAW uint4, all in flight together), and where chunk c of the nine it ends up with stands in the 1184-byte LDS row.
-// bf16 rows: the nine chunks gsub + 8 c of the row as they are.
-struct SmlaBf16Rows {
-    static constexpr bool FP8 = false;
-    static constexpr int RAW = SMLA_STAGE;
-    const uint16_t *kv;
-    int64_t kv_stride, s_rows;
-    static __device__ __forceinline__ SmlaBf16Rows make(const void *kv, int64_t stride, int64_t s_rows, int, int)
-    {
-        return SmlaBf16Rows{static_cast<const uint16_t *>(kv), stride, s_rows};
-    }
-    __device__ __forceinline__ const unsigned char *at(int64_t r, int gsub) const
-    {
-        return reinterpret_cast<const unsigned char *>(kv + r * kv_stride + gsub * 8);
-    }
-    static __device__ __forceinline__ void load(const unsigned char *p, int gsub, uint4 (&v)[RAW])
-    {
-#pragma unroll
-        for (int c = 0; c < RAW; ++c) v[c] = *reinterpret_cast<const uint4 *>(p + 128 * c);
-    }
-    static __device__ __forceinline__ int lds_at(int c, int gsub) { return gsub * 16 + 128 * c; }
-};
+// What the kernel gathers from: SmlaBf16Rows (dga_sparse_mla_device.hpp, which says what a cache is), or
 // fp8 rows: v[0 .. 3] the code chunks gsub + 8 c (bytes 16 gsub + 128 c of the row: chunk c lies in scale group c), v[4] the four
 // scales (bytes 512 .. 527), v[5] the rope chunk gsub (bytes 528 + 16 gsub ..).  The codes 8 h .. 8 h + 7 of chunk c, image chunk 2 c + h,
 // become 16 bytes of bf16 at byte 32 (gsub + 8 c) + 16 h of the LDS row; the rope chunk goes where the bf16 gather puts its ninth.
@@ -429,55 +388,9 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_fwd_kernel(const uint
     }
 }
 
-// What the four entries hand to the one check and the one launch below: the call without its row source and outputs, the row source, and
-// the outputs of either kind.  A new row source is one more maker of SmlaSource with its clauses in the four questions the check asks; a
-// new axis of the kernel is one more template parameter of the launch.
-struct SmlaCall {
-    const void *q;
-    const int32_t *indices, *index_offsets;
-    int64_t m;
-    int heads;
-    int64_t topk, idx_stride;
-    double sm_scale;
-    int flags;
-    void *stream;
-};
-
-// count units of page_size rows each, `stride` apart: bf16 rows (s of them, one a unit, kv_stride elements apart) or the blocks of the
-// paged fp8 cache (block_stride bytes apart).  The range clauses divide by what the shape clause has vouched for.
-struct SmlaSource {
-    bool fp8;
-    const void *rows;
-    int64_t count, page_size, stride;
-    // (stride / 656 < page_size says block_stride < 656 page_size without the product)
-    bool shape() const { return count >= 1 && page_size >= 1 && (fp8 ? stride / SMLA_FP8_ROW >= page_size : stride >= SMLA_D); }
-    bool aligned() const { return reinterpret_cast<uintptr_t>(rows) % 16 == 0 && stride % (fp8 ? 16 : 8) == 0; }
-    bool rows_in_range() const { return count <= 0x7FFFFFFFll / page_size; }
-    bool bytes_in_range() const { return stride <= 0x7FFFFFFFFFFFFFFFll / (fp8 ? 1 : 2) / count; }
-};
-
+// (SmlaCall, SmlaSource and check_sparse_mla, what the four entries hand to the one check and the one launch below, are
+// dga_internal.hpp's: the backward's entry shares them.)
 static int page_shift_of(int page) { return (page & (page - 1)) == 0 ? __builtin_ctz(page) : -1; }
-
-// The checks of all four entries, in the documented order: flags, shape, m == 0, null, alignment, range; *launch is set when a launch is
-// to follow (not for m == 0).  out and lse are the one-pass entries' (null and unchecked for the partial ones, whose outputs the launch
-// checks afterwards).
-static int check_sparse_mla(const SmlaCall &c, const SmlaSource &src, bool outputs, const void *out, const void *lse, bool *launch)
-{
-    *launch = false;
-    if (c.flags & ~DGA_SPARSE_MLA_LINEAR_GRID) return DGA_E_RANGE;
-    if (c.m < 0 || c.heads < 16 || c.heads > DGA_SPARSE_MLA_MAX_HEADS || c.heads % 16 || !src.shape() || c.topk < 1 || c.idx_stride < c.topk)
-        return DGA_E_SHAPE;
-    if (c.m == 0) return DGA_OK;
-    if (!c.q || !src.rows || !c.indices || (outputs && (!out || !lse))) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(c.q) % 16 || !src.aligned() || reinterpret_cast<uintptr_t>(out) % 16 ||
-        reinterpret_cast<uintptr_t>(c.indices) % 4 || reinterpret_cast<uintptr_t>(c.index_offsets) % 4 || reinterpret_cast<uintptr_t>(lse) % 4)
-        return DGA_E_ALIGN;
-    const int head_blocks = (c.heads + 63) / 64;
-    if (!src.rows_in_range() || c.topk > 0x7FFFFFFFll - DGA_SPARSE_MLA_TILE || c.m > (0x7FFFFFFFll - 8) / head_blocks) return DGA_E_RANGE;
-    if (!src.bytes_in_range() || c.idx_stride > 0x7FFFFFFFFFFFFFFFll / 4 / c.m) return DGA_E_RANGE;
-    *launch = true;
-    return DGA_OK;
-}
 
 // The launch all four entries end in: one workgroup per token, block of 64 heads and split, the grid walked XCD by XCD unless it is linear.
 // PARTIAL: num_splits and the partial pointers are checked first, behind the common checks; *effective_splits is written on success only.

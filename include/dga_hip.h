@@ -1077,6 +1077,36 @@ int dga_sparse_mla_merge(const float *partial_out, const float *partial_lse, int
                          void *stream);
 int dga_sparse_mla_splits(int64_t m, int heads, int64_t topk, int cus);
 
+/* The backward of dga_sparse_mla_fwd (csrc/dga_sparse_mla_bwd.hip): dq and dkv from d_out, the forward's out and lse.
+ *   q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, sm_scale, flags: dga_sparse_mla_fwd's, the validity rule too
+ *   out, d_out    bf16 [m, heads, 512] contiguous, 16-byte aligned; lse fp32 [m, heads] (natural log) -- out and lse normally the forward's
+ *   dq            bf16 [m, heads, 576] contiguous, 16-byte aligned: every element is written
+ *   dkv           fp32 [s, 576], rows dkv_stride elements apart (>= 576 and a multiple of 4), 16-byte aligned: ADDED INTO -- the caller
+ *                 zeroes it, or keeps accumulating over calls (a sequence fed in chunks of m)
+ *   over the valid positions j of token t, r_j the row, L2E = (float)log2 e:
+ *     p_j   = exp2(S_j (float)(sm_scale log2 e) - lse[t, h] L2E),  S_j = sum_d q[t, h, d] kv[r_j, d]
+ *     delta = sum_c out[t, h, c] d_out[t, h, c],  dP_j = sum_c d_out[t, h, c] kv[r_j, c]  (c < 512)
+ *     dS_j  = ((float)sm_scale p_j) (dP_j - delta)
+ *     dq[t, h, :] = sum_j dS_j kv[r_j, :576];   dkv[r_j, :576] += sum_h dS_j q[t, h, :];   dkv[r_j, :512] += sum_h p_j d_out[t, h, :]
+ *   an invalid position dereferences nothing and adds nothing; a duplicate counts once per position; a token without a valid position
+ *   gets dq = +0 and touches no row of dkv whatever its lse, out and d_out hold; no row of dkv that no valid position names is written,
+ *   and no column >= 576 of any row.
+ * Arithmetic: S, dP by v_mfma_f32_16x16x32_bf16 over d ascending; delta in fp32 in a fixed order; p and dS rounded to bf16 (RNE) for the
+ * three products that follow, whose sums are fp32 on the matrix pipe: dq over tiles of DGA_SPARSE_MLA_TILE positions in list order, one
+ * rounding to bf16 at the end; a tile's share of dkv over the DGA_SPARSE_MLA_BWD_HEADS heads of a workgroup, then global_atomic_add_f32.
+ * Determinism: dq has one writer per element and a fixed order: two runs give the same bytes.  dkv does NOT: the order in which the
+ * atomic adds reach an element varies from run to run, so two runs agree to fp32 rounding of the sum, and bit for bit only where the
+ * contributions to an element are exactly summable or there is a single one.
+ * One launch (capturable), everything read on the device; flags as the forward's.
+ * Checks, all before the launch: dga_sparse_mla_fwd's in its order (out and lse apart; m == 0 -> DGA_OK with nothing touched), then
+ * DGA_E_SHAPE (dkv_stride < 576);  DGA_E_NULL (out, d_out, lse, dq, dkv);  DGA_E_ALIGN (out, d_out, dq or dkv not 16-byte, lse not 4-byte
+ * aligned, dkv_stride not a multiple of 4);  DGA_E_RANGE (the grid of m ceil(heads / 32) workgroups beyond int32, s dkv_stride beyond
+ * int64). */
+#define DGA_SPARSE_MLA_BWD_HEADS 32
+int dga_sparse_mla_bwd(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int64_t s,
+                       int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const void *out, const void *d_out,
+                       const float *lse, void *dq, float *dkv, int64_t dkv_stride, void *stream);
+
 /* The writer of the paged fp8 latent cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
  * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
  * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
