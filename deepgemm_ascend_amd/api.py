@@ -1799,6 +1799,23 @@ MQA_LOGITS_HEAD_DIM, MQA_LOGITS_HEADS = 128, (32, 64)
 MQA_LOGITS_BLOCK_M, MQA_LOGITS_BLOCK_N = 64, 256   # the kernel's token run and key block (DGA_MQA_LOGITS_BLOCK_*)
 
 
+def _mqa_operands(q: torch.Tensor, kv, weights: torch.Tensor):
+    """The operands fp8_mqa_logits and its backward share, checked in one order: (k, kscale, M, H, 128, N)"""
+    _require(isinstance(kv, (tuple, list)) and len(kv) == 2, "kv must be (k, kscale)")
+    k, kscale = kv
+    _require(q.dim() == 3, "q must be [M, H, %d]", MQA_LOGITS_HEAD_DIM)
+    m, h, d = q.shape
+    _require(d == MQA_LOGITS_HEAD_DIM, "q must be [M, H, %d]: head dimension %d is not supported", MQA_LOGITS_HEAD_DIM, d)
+    _require(h in MQA_LOGITS_HEADS, "q must have 32 or 64 heads, got %d", h)
+    _want(_fp8_bytes(q), "q", None, (m, h, d))
+    _require(k.dim() == 2 and k.shape[0] >= 1, "k must be [N, %d] with N >= 1", d)
+    n = k.shape[0]
+    _want(_fp8_bytes(k), "k", None, (n, d))
+    _want(kscale, "kscale", torch.float32, (n,))
+    _want(weights, "weights", torch.float32, (m, h))
+    return k, kscale, m, h, d, n
+
+
 def fp8_mqa_logits(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weights: torch.Tensor, cu_seq_len_k_start: torch.Tensor,
                    cu_seq_len_k_end: torch.Tensor, out: Optional[torch.Tensor] = None, sync: bool = False) -> torch.Tensor:
     """The scoring kernel of the lightning indexer of DeepSeek sparse attention, upstream DeepGEMM's fp8_mqa_logits (dga_fp8_mqa_logits):
@@ -1812,18 +1829,7 @@ def fp8_mqa_logits(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weigh
     |logits - exact| <= (2^-22 + (H + 3) 2^-24) kscale[n] sum_h |weights| sum_d |q k| on every in-range element.  A NaN code in q poisons
     its row, one in k its column, inside the ranges only.  A token whose range misses a block of 256 keys costs that block nothing but the
     -inf stores, so a causal prefill costs about half the dense work.  M == 0 returns without a launch."""
-    _require(isinstance(kv, (tuple, list)) and len(kv) == 2, "kv must be (k, kscale)")
-    k, kscale = kv
-    _require(q.dim() == 3, "q must be [M, H, %d]", MQA_LOGITS_HEAD_DIM)
-    m, h, d = q.shape
-    _require(d == MQA_LOGITS_HEAD_DIM, "q must be [M, H, %d]: head dimension %d is not supported", MQA_LOGITS_HEAD_DIM, d)
-    _require(h in MQA_LOGITS_HEADS, "q must have 32 or 64 heads, got %d", h)
-    _want(_fp8_bytes(q), "q", None, (m, h, d))
-    _require(k.dim() == 2 and k.shape[0] >= 1, "k must be [N, %d] with N >= 1", d)
-    n = k.shape[0]
-    _want(_fp8_bytes(k), "k", None, (n, d))
-    _want(kscale, "kscale", torch.float32, (n,))
-    _want(weights, "weights", torch.float32, (m, h))
+    k, kscale, m, h, d, n = _mqa_operands(q, kv, weights)
     _want(cu_seq_len_k_start, "cu_seq_len_k_start", torch.int32, (m,))
     _want(cu_seq_len_k_end, "cu_seq_len_k_end", torch.int32, (m,))
     if out is None:
@@ -1835,6 +1841,76 @@ def fp8_mqa_logits(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weigh
         q.data_ptr(), k.data_ptr(), kscale.data_ptr(), weights.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(),
         m, n, h, d, out.data_ptr(), stream), sync)
     return out
+
+
+def _mqa_selected(t: torch.Tensor, what: str, dtype, m: int, topk: Optional[int]) -> int:
+    """indices / d_logits of fp8_mqa_logits_bwd: `dtype` [M, topk], a contiguous last dimension, stride(0) >= topk >= 1.  Returns stride(0)."""
+    _require(t.dtype == dtype and t.dim() == 2 and t.shape[0] == m and t.shape[1] >= 1 and (topk is None or t.shape[1] == topk),
+             "%s must be %s [M, topk] tensor with %s", what, "an int32" if topk is None else "a float32",
+             "topk >= 1" if topk is None else "indices' topk")
+    stride = t.stride(0) if m > 1 else t.shape[1]
+    _require((t.shape[1] == 1 or t.stride(1) == 1) and stride >= t.shape[1], "%s must have a contiguous last dimension and stride(0) >= topk", what)
+    return stride
+
+
+def fp8_mqa_logits_bwd(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weights: torch.Tensor, indices: torch.Tensor,
+                       d_logits: torch.Tensor, index_offsets: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
+                       dk: Optional[torch.Tensor] = None, d_weights: Optional[torch.Tensor] = None,
+                       sync: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The backward of fp8_mqa_logits over the selected keys (dga_fp8_mqa_logits_bwd): the lightning indexer's gradients (dq, dk,
+    d_weights) from d_logits, the derivative of a loss at the logits indexer_topk selected.  q, kv = (k, kscale) and weights are
+    fp8_mqa_logits' operands with its checks (q and k 16-byte aligned);  indices int32 [M, topk] with a contiguous last dimension and
+    stride(0) >= topk >= 1 -- indexer_topk's output, a slice of it, or its relative=True form beside index_offsets int32 [M];  d_logits
+    float32 [M, topk] under the same stride rule.  The validity rule is sparse_mla_fwd's: position j is valid iff indices[m, j] >= 0 and
+    r_j = indices[m, j] + index_offsets[m] lies in [0, N); an invalid position dereferences nothing and adds nothing, and its d_logits
+    element is never used whatever it holds; a duplicate counts once per position.  Over the valid positions, with
+    s_hj = sum_d q[m, h, d] k[r_j, d] on the code values and mask_hj = s_hj > 0:
+    d_weights[m, h] = sum_j d_logits[m, j] kscale[r_j] (mask_hj ? s_hj : 0);
+    dq[m, h, :] = weights[m, h] sum_j mask_hj d_logits[m, j] kscale[r_j] k[r_j, :];
+    dk[r_j, :] += sum_h mask_hj d_logits[m, j] weights[m, h] q[m, h, :].
+    dq float32 [M, H, 128] and d_weights float32 [M, H], contiguous (torch.empty when None; every element is written): dq is the
+    derivative with respect to the value of the q code -- the caller divides it by the q scale it folded into weights and multiplies
+    d_weights by it, which is why dq stays fp32.  dk float32 [N, 128] with a contiguous last dimension, stride(0) >= 128 and a multiple
+    of 4, 16-byte aligned: the kernel ADDS INTO it -- None allocates torch.zeros, a caller's tensor accumulates over calls (a sequence fed
+    in chunks of M); it is the straight-through derivative with respect to the dequantised key kscale[n] k[n, :].  A token with no valid
+    position gets dq = +0 and d_weights = +0 and touches no row of dk; no row of dk that no valid position names, and no byte beyond
+    column 127, is written.
+    Arithmetic: the scores on the matrix pipe in fp32 on exactly converted codes; d_weights an fp32 fused multiply-add chain; weights
+    d_logits (and its product with kscale) carried as two bf16 terms (the value rounded RNE, and its residual) into the two products that
+    follow, all sums fp32, dk added by the
+    hardware's fp32 atomic add.  Non-finite inputs -- NaN codes, a non-finite d_logits, weights or kscale at a valid position -- are
+    outside the contract: they may put anything into the elements they feed, and cause no access outside the tensors.
+    Determinism: dq and d_weights are byte-reproducible.  dk is NOT: the order of the atomic adds onto a row varies from run to run, so
+    two runs agree to fp32 rounding of the sum, and bit for bit only where the contributions to an element are exactly summable or there
+    is a single one.
+    Returns (dq, dk, d_weights).  One launch, capturable, everything read on the device; M == 0 returns without one."""
+    k, kscale, m, h, d, n = _mqa_operands(q, kv, weights)
+    idx_stride = _mqa_selected(indices, "indices", torch.int32, m, None)
+    topk = indices.shape[1]
+    dl_stride = _mqa_selected(d_logits, "d_logits", torch.float32, m, topk)
+    if index_offsets is not None:
+        _want(index_offsets, "index_offsets", torch.int32, (m,))
+    if dq is None:
+        dq = torch.empty((m, h, d), dtype=torch.float32, device=q.device)
+    else:
+        _want(dq, "dq", torch.float32, (m, h, d))
+    if d_weights is None:
+        d_weights = torch.empty((m, h), dtype=torch.float32, device=q.device)
+    else:
+        _want(d_weights, "d_weights", torch.float32, (m, h))
+    if dk is None:
+        dk = torch.zeros((n, d), dtype=torch.float32, device=q.device)
+    _require(dk.dtype == torch.float32 and dk.dim() == 2 and tuple(dk.shape) == (n, d), "dk must be a float32 [N, %d] tensor with k's N = %d rows", d, n)
+    dk_stride = dk.stride(0) if n > 1 else d
+    _require(dk.stride(1) == 1 and dk_stride >= d and dk_stride % 4 == 0,
+             "dk must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", d, dk_stride)
+    _require(all(x.data_ptr() % 16 == 0 for x in (q, k, dq, dk)), "q, k, dq and dk must be 16-byte aligned")
+    # (M == 0: the C entry returns before any launch)
+    _launch("fp8_mqa_logits_bwd", (q, k, kscale, weights, indices, index_offsets, d_logits, dq, dk, d_weights),
+            lambda L, stream: L.dga_fp8_mqa_logits_bwd(
+                q.data_ptr(), k.data_ptr(), kscale.data_ptr(), weights.data_ptr(), indices.data_ptr(), _ptr(index_offsets), d_logits.data_ptr(),
+                m, n, h, d, topk, idx_stride, dl_stride, dq.data_ptr(), dk.data_ptr(), dk_stride, d_weights.data_ptr(), stream), sync)
+    return dq, dk, d_weights
 
 
 PAGED_MQA_LOGITS_BLOCK_KV, PAGED_MQA_LOGITS_BLOCK_BYTES = 64, 8448   # keys of a cache block; its bytes: 64 * 128 codes + 64 fp32 scales

@@ -902,6 +902,44 @@ int64_t dga_rms_norm_backward_workspace_bytes(int64_t rows, int64_t h);
 int dga_fp8_mqa_logits(const void *q, const void *k, const float *kscale, const float *weights, const int32_t *ks, const int32_t *ke,
                        int64_t m, int64_t n, int heads, int head_dim, float *logits, void *stream);
 
+/* The backward of that scoring over the selected keys (csrc/dga_mqa_logits_bwd.hip): the indexer's gradients from the derivative of a loss
+ * at the logits dga_indexer_topk selected.
+ *   q, k, kscale, weights, m, n, heads, head_dim: dga_fp8_mqa_logits' (q and k 16-byte aligned here)
+ *   indices       int32 [m, topk], rows idx_stride elements apart (>= topk >= 1); index_offsets int32 [m] or NULL.  The validity rule is
+ *                 dga_sparse_mla_fwd's: position j is valid iff indices[t, j] >= 0 and r_j = indices[t, j] + index_offsets[t] lies in [0, n)
+ *   d_logits      fp32 [m, topk], rows dl_stride elements apart (>= topk): the derivative at logits[t, r_j]
+ *   dq            fp32 [m, heads, 128] contiguous, 16-byte aligned: every element is written.  The derivative with respect to the value of
+ *                 the q code (the caller divides by the q scale it folded into weights, and multiplies d_weights by it)
+ *   d_weights     fp32 [m, heads]: every element is written
+ *   dk            fp32 [n, 128], rows dk_stride elements apart (>= 128 and a multiple of 4), 16-byte aligned: ADDED INTO -- the caller zeroes
+ *                 it, or keeps accumulating over calls (a sequence fed in chunks of m).  The straight-through derivative with respect to
+ *                 the dequantised key kscale[r] k[r, :]
+ *   over the valid positions j of token t, s_hj = sum_d q[t, h, d] k[r_j, d] on the code values, mask_hj = s_hj > 0:
+ *     d_weights[t, h] = sum_j d_logits[t, j] kscale[r_j] (mask_hj ? s_hj : 0)
+ *     dq[t, h, :]     = weights[t, h] sum_j mask_hj d_logits[t, j] kscale[r_j] k[r_j, :]
+ *     dk[r_j, :]     += sum_h mask_hj d_logits[t, j] weights[t, h] q[t, h, :]
+ *   an invalid position dereferences nothing and adds nothing -- its d_logits element is never read; a duplicate counts once per
+ *   position; a token without a valid position gets dq = +0 and d_weights = +0 and touches no row of dk; no row of dk that no valid
+ *   position names is written, and no column >= 128 of any row.
+ * Arithmetic: the codes go to bf16 exactly, s is four chained v_mfma_f32_16x16x32_bf16 over d ascending in fp32; c = d_logits kscale and
+ * g = weights d_logits are fp32 products; d_weights is an fp32 fused multiply-add chain of c (mask ? s : 0) in a fixed order;
+ * Gk = mask ? g : +0 and Gq = Gk kscale enter the two products that follow as two bf16 terms each -- the value rounded to bf16 (RNE) and
+ * its residual (exact in fp32) rounded likewise: 2^-16 of the value -- and the sums of those products are fp32 on the matrix pipe: dq over tiles of DGA_MQA_LOGITS_BWD_TILE positions in list order; a tile's share of dk over all heads, then
+ * global_atomic_add_f32.  Non-finite inputs (NaN codes; a non-finite d_logits, weights or kscale at a valid position) are outside the
+ * contract: they may put anything into the elements they feed, and cause no access outside the tensors.
+ * Determinism: dq and d_weights have one writer per element and a fixed order: two runs give the same bytes.  dk does NOT: the order in
+ * which the atomic adds reach an element varies from run to run, so two runs agree to fp32 rounding of the sum, and bit for bit only where
+ * the contributions to an element are exactly summable or there is a single one.
+ * One launch of one workgroup per token (capturable), everything read on the device.
+ * Checks, all before the launch: DGA_E_SHAPE (m < 0, n < 1, head_dim != 128, heads other than 32 or 64, topk < 1, idx_stride or
+ * dl_stride < topk, dk_stride < 128);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (any pointer but index_offsets);  DGA_E_ALIGN (q,
+ * k, dq or dk not 16-byte, any other pointer not 4-byte aligned, dk_stride not a multiple of 4);  DGA_E_RANGE (n or topk + 64 beyond
+ * int32, n dk_stride beyond int64, the grid of m workgroups beyond int32). */
+#define DGA_MQA_LOGITS_BWD_TILE 64
+int dga_fp8_mqa_logits_bwd(const void *q, const void *k, const float *kscale, const float *weights, const int32_t *indices,
+                           const int32_t *index_offsets, const float *d_logits, int64_t m, int64_t n, int heads, int head_dim, int64_t topk,
+                           int64_t idx_stride, int64_t dl_stride, float *dq, float *dk, int64_t dk_stride, float *d_weights, void *stream);
+
 /* The decode half of that scoring, upstream DeepGEMM's fp8_paged_mqa_logits (csrc/dga_paged_mqa_logits.hip): each of `batch` sequences
  * scores its next_n (1 or 2) newest tokens against its whole context, whose keys live in a paged cache reached through a block table.
  *   kv_cache      block b is DGA_PAGED_MQA_LOGITS_BLOCK_BYTES = 8448 bytes at b * block_stride: bytes 0 .. 8191 the e4m3 codes of its
