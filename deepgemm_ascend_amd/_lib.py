@@ -117,6 +117,7 @@ def _smla_args(geometry, outputs):
 _SMLA_ONE_PASS = [c_void_p] * 3                                            # out, lse, stream
 _SMLA_PARTIAL = [c_int, POINTER(c_int)] + [c_void_p] * 3                   # num_splits, effective_splits, partial_out, partial_lse, stream
 _SMLA_BACKWARD = [c_void_p] * 5 + [c_int64, c_void_p]                      # out, d_out, lse, dq, dkv, dkv_stride, stream
+_SMLA_KL_LOSS = [c_void_p] * 2 + [c_int64, c_double] + [c_void_p] * 4      # lse, logits, logits_stride, grad_scale, loss, d_logits, target, stream
 
 # name -> (restype, argtypes): every symbol include/dga_hip.h declares
 SIGNATURES = {
@@ -210,6 +211,7 @@ SIGNATURES = {
     "dga_sparse_mla_fwd_partial": (c_int, _smla_args([c_int64] * 2, _SMLA_PARTIAL)),
     "dga_sparse_mla_fwd_fp8_partial": (c_int, _smla_args([c_int64] * 3, _SMLA_PARTIAL)),
     "dga_sparse_mla_bwd": (c_int, _smla_args([c_int64] * 2, _SMLA_BACKWARD)),
+    "dga_indexer_kl_loss": (c_int, _smla_args([c_int64] * 2, _SMLA_KL_LOSS)),
     "dga_sparse_mla_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,

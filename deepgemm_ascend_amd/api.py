@@ -2212,6 +2212,55 @@ def sparse_mla_bwd(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: 
     return dq, dkv
 
 
+def indexer_kl_loss(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, lse: torch.Tensor, sm_scale: float, logits: torch.Tensor,
+                    index_offsets: Optional[torch.Tensor] = None, grad_scale: float = 1.0, loss: Optional[torch.Tensor] = None,
+                    d_logits: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, want_target: bool = False,
+                    sync: bool = False):
+    """The lightning indexer's sparse-stage loss and its derivative (dga_indexer_kl_loss): KL(t || softmax(logits)) over the selected keys,
+    the target t the main attention's probabilities summed over the heads.  q, kv, indices, index_offsets and sm_scale are
+    sparse_mla_fwd's, with its checks and its validity rule: position j is valid iff indices[m, j] >= 0 and
+    r_j = indices[m, j] + index_offsets[m] lies in [0, S); an invalid position dereferences nothing and contributes nothing; a duplicate
+    counts once per position.  lse float32 [M, Hq] contiguous -- normally what sparse_mla_fwd returned for the same q, kv and list; it is
+    taken as given, nothing is renormalised.  logits float32 [M, N] with a contiguous last dimension and stride(0) >= N, N == S:
+    fp8_mqa_logits' output, key column = kv row -- the indexer's logit of position j is logits[m, r_j], and no other element is read.
+    (Indices that are physical slots of a paged cache do not name columns of logits: out of scope, and the wrapper cannot tell.)
+    grad_scale, a Python number, carries 1 / tokens and the upstream derivative of the loss.  Over the valid positions of token m:
+    p_hj = exp(sm_scale sum_d q[m, h, d] kv[r_j, d] - lse[m, h]);  t_j = (1 / Hq) sum_h p_hj (sums to 1 over j when lse is the forward's);
+    L = ln sum_j exp(logits[m, r_j]);  y_j = exp(logits[m, r_j] - L);
+    loss[m] = sum_j (t_j > 0 ? t_j (ln t_j - (logits[m, r_j] - L)) : 0);  d_logits[m, j] = grad_scale (y_j - t_j), the derivative of
+    grad_scale loss at logits[m, r_j] when sum_j t_j = 1.  The target is a constant: nothing flows into q, kv or lse.
+    loss float32 [M], d_logits float32 [M, topk] -- directly what fp8_mqa_logits_bwd takes beside the same indices --, and target float32
+    [M, topk] when want_target is set or target= is given; contiguous, torch.empty when None, every element written: an invalid position
+    gets d_logits = +0 and target = +0, a token without a valid position loss = +0 and rows of +0 whatever its lse holds.
+    Arithmetic: the scores on the matrix pipe in fp32 in sparse_mla_fwd's order of summation, p in fp32 and never rounded to bf16, every
+    sum fp32 in a fixed order.  One writer per element, no atomics: two runs give the same bytes.  A non-finite logit or lse at a valid
+    position is outside the contract: it may put anything into that token's outputs and causes no access outside the tensors.
+    Returns (loss, d_logits) or (loss, d_logits, target).  One launch, capturable, everything read on the device; M == 0 returns
+    without one."""
+    m, heads, topk, args = _smla_problem(False, q, kv, indices, sm_scale, SPARSE_MLA_D_V, index_offsets)
+    s = kv.shape[0]
+    _want(lse, "lse", torch.float32, (m, heads))
+    _require(logits.dtype == torch.float32 and logits.dim() == 2 and tuple(logits.shape) == (m, s),
+             "logits must be a float32 [M, N] tensor with N = kv's S = %d columns", s)
+    lg_stride = logits.stride(0) if m > 1 else s
+    _require((s == 1 or logits.stride(1) == 1) and lg_stride >= s, "logits must have a contiguous last dimension and stride(0) >= N")
+    _require(isinstance(grad_scale, (int, float)), "grad_scale must be a number")
+    want_target = want_target or target is not None
+    specs = (("loss", loss, (m,)), ("d_logits", d_logits, (m, topk)), ("target", target, (m, topk)))[:3 if want_target else 2]
+    outs = []
+    for name, given, shape in specs:
+        if given is None:
+            given = torch.empty(shape, dtype=torch.float32, device=q.device)
+        else:
+            _want(given, name, torch.float32, shape)
+        outs.append(given)
+    # (M == 0: the C entry returns before any launch)
+    _launch("indexer_kl_loss", (q, kv, indices, index_offsets, lse, logits, *outs), lambda L, stream: L.dga_indexer_kl_loss(
+        q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, 0, lse.data_ptr(), logits.data_ptr(), lg_stride,
+        float(grad_scale), outs[0].data_ptr(), outs[1].data_ptr(), _ptr(outs[2] if want_target else None), stream), sync)
+    return tuple(outs)
+
+
 SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values
 
 

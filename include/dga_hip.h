@@ -1145,6 +1145,32 @@ int dga_sparse_mla_bwd(const void *q, const void *kv, const int32_t *indices, co
                        int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const void *out, const void *d_out,
                        const float *lse, void *dq, float *dkv, int64_t dkv_stride, void *stream);
 
+/* The indexer's KL loss over the selected keys and its derivative at their logits (csrc/dga_indexer_kl.hip): what dga_fp8_mqa_logits_bwd
+ * takes as d_logits.  The target is the main attention's probabilities summed over the heads -- dga_sparse_mla_fwd's first product again.
+ *   q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, sm_scale, flags: dga_sparse_mla_fwd's, the validity rule too
+ *   lse           fp32 [m, heads] (natural log), normally the forward's for the same q, kv and list; taken as given, nothing is renormalised
+ *   logits        fp32 [m, s], rows logits_stride elements apart (>= s): dga_fp8_mqa_logits' output, key column = kv row; only the
+ *                 elements logits[t, r_j] of valid positions are read
+ *   grad_scale    1 / tokens times the upstream derivative of the loss
+ *   loss          fp32 [m];  d_logits fp32 [m, topk] contiguous;  target fp32 [m, topk] contiguous or null: every element is written
+ *   over the valid positions j of token t, r_j the row, L2E = (float)log2 e, LN2 = (float)ln 2:
+ *     p_hj = exp2(S_hj (float)(sm_scale log2 e) - lse[t, h] L2E),  S_hj = sum_d q[t, h, d] kv[r_j, d]
+ *     t_j  = (sum_h p_hj) (float)(1 / heads)
+ *     L    = max + LN2 log2(sum_j exp2((logits[t, r_j] - max) L2E)),  max the largest valid logit
+ *     a_j  = logits[t, r_j] - L,  y_j = exp2(a_j L2E)
+ *     loss[t] = sum_j (t_j > 0 ? t_j (LN2 log2 t_j - a_j) : 0);   d_logits[t, j] = (float)grad_scale (y_j - t_j);   target[t, j] = t_j
+ *   an invalid position dereferences nothing, contributes nothing and gets d_logits = target = +0; a duplicate counts once per position; a
+ *   token without a valid position gets loss = +0 and rows of +0 whatever its lse holds.  A non-finite logit or lse at a valid position
+ *   may put anything into that token's outputs and causes no access outside the tensors.
+ * Arithmetic: S by v_mfma_f32_16x16x32_bf16 over d ascending, the forward's chain; p in fp32, never rounded to bf16; every sum fp32 in a
+ * fixed order.  One writer per element, no atomics: two runs give the same bytes.  One launch (capturable), everything read on the device.
+ * Checks, all before the launch: dga_sparse_mla_fwd's in its order (out and lse apart; m == 0 -> DGA_OK with nothing touched), then
+ * DGA_E_SHAPE (logits_stride < s);  DGA_E_NULL (lse, logits, loss, d_logits);  DGA_E_ALIGN (any of the five not 4-byte aligned);
+ * DGA_E_RANGE (m logits_stride beyond int64). */
+int dga_indexer_kl_loss(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads, int64_t s,
+                        int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const float *lse, const float *logits,
+                        int64_t logits_stride, double grad_scale, float *loss, float *d_logits, float *target, void *stream);
+
 /* The writer of the paged fp8 latent cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
  * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
  * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
