@@ -63,6 +63,7 @@ BUILD_DEFAULT, BUILD_WSK_REGISTER, BUILD_BX_AIMAGE, BUILD_BX_IMAGE8, BUILD_BX_IM
 BUILD_BX_PERSISTENT, BUILD_BX_ONE_TILE, BUILD_BX_GROUPED, BUILD_BX_DECODE = 7, 8, 9, 10
 ROWS_A_ZERO_PADDED, ROWS_B_ZERO_PADDED = 1, 2   # dga_gemm_fp8_fp8_bf16_nt_strided flags
 CAST_UE8M0 = 1                                  # dga_cast_to_fp8_*_ex flag: block scales rounded up to powers of two
+INDEXER_PREPARE_INTERLEAVED = 0x100             # dga_indexer_prepare_* flag: RoPE pairs (x[2 i], x[2 i + 1]) instead of (x[i], x[i + 32])
 ROUTER_SOFTMAX, ROUTER_SIGMOID = 0, 1           # dga_router_topk score_func
 ROUTER_RENORMALIZE = 1                          # dga_router_topk flag
 ROUTER_BALANCE_NORMALIZE = 1                    # dga_router_balance_loss flag
@@ -216,6 +217,12 @@ SIGNATURES = {
     "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                              c_void_p, c_int, c_void_p]),
+    "dga_indexer_prepare_q": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_float, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_void_p]),
+    "dga_indexer_prepare_k": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_float, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "dga_indexer_prepare_bwd": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_float,
+                                        c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "dga_catlass_dynamic_matmul_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "dga_catlass_dynamic_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                            c_void_p]),

@@ -2481,6 +2481,186 @@ def mla_kv_cast_to_fp8_paged(kv_c: torch.Tensor, k_pe: torch.Tensor, kv_cache: t
     return kv_cache
 
 
+IndexerPrepareK = collections.namedtuple("IndexerPrepareK", ("k_fp8", "kscale", "mean", "rstd"))
+INDEXER_ROPE_DIM = 64                # the leading dimensions of a 128-wide indexer row that RoPE turns: cos_sin is [P, 64]
+
+
+def _prep_rows(x: torch.Tensor, what: str, dtypes, lead: str) -> None:
+    """The row tensor of an indexer_prepare_* call: [lead.., 128], contiguous, of one of `dtypes`, 16-byte aligned."""
+    _require(x.dtype in dtypes, "%s must be %s", what, "float32" if len(dtypes) == 1 else "float32, bfloat16 or float16")
+    _require(x.dim() == len(lead.split(",")) + 1 and x.shape[-1] == MQA_LOGITS_HEAD_DIM, "%s must be [%s, %d]", what, lead, MQA_LOGITS_HEAD_DIM)
+    _require(x.data_ptr() % 16 == 0, "%s must be 16-byte aligned", what)
+
+
+def _prep_table(positions: torch.Tensor, cos_sin: torch.Tensor, tokens: int) -> int:
+    """positions int32 / int64 [tokens] and cos_sin float32 [P, 64] contiguous, 16-byte aligned -> P."""
+    _want(positions, "positions", (torch.int32, torch.int64), (tokens,))
+    _require(cos_sin.dim() == 2 and cos_sin.shape[1] == INDEXER_ROPE_DIM, "cos_sin must be [P, %d]: cos in columns 0 .. 31, sin in 32 .. 63",
+             INDEXER_ROPE_DIM)
+    _want(cos_sin, "cos_sin", torch.float32, tuple(cos_sin.shape))
+    _require(cos_sin.data_ptr() % 16 == 0, "cos_sin must be 16-byte aligned")
+    return cos_sin.shape[0]
+
+
+def _prep_flags(interleaved: bool, use_ue8m0: bool = False) -> int:
+    return (_lib.INDEXER_PREPARE_INTERLEAVED if interleaved else 0) | (_lib.CAST_UE8M0 if use_ue8m0 else 0)
+
+
+def indexer_prepare_q(q: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                      weight_scale: float = 1.0, interleaved: bool = False, use_ue8m0: bool = False, out=None, sync: bool = False):
+    """From the indexer's query projection to fp8_mqa_logits' / fp8_paged_mqa_logits' operands in one launch (dga_indexer_prepare_q): RoPE,
+    the 128-point Hadamard rotation and the 1x128 quantiser.  q [M, H, 128] float32 / bfloat16 / float16, contiguous, 16-byte aligned, any
+    H >= 1; positions int32 or int64 [M] and cos_sin float32 [P, 64] (cos of frequency i in column i, sin in column 32 + i), contiguous,
+    read on the device.  Per row, in float32, every operation rounded on its own and none contracted:
+      RoPE on x[0 .. 63], pair i = (x[i], x[i + 32]), or (x[2 i], x[2 i + 1]) with interleaved: a' = fl(fl(a c) - fl(b s)),
+      b' = fl(fl(a s) + fl(b c));
+      the Walsh-Hadamard butterfly in natural order, strides 1, 2, .., 64, then y = fl(t C), C the float32 nearest 128^-1/2
+      (rotate_activation);
+      (q_fp8, q_scale) = per_token_cast_to_fp8(y, use_ue8m0=...) on the float32 y, byte for byte: y never passes through 16 bits.
+    Returns (q_fp8 float8_e4m3fn [M, H, 128], q_scale float32 [M, H], weights_out).  With weights ([M, H] float32 or bfloat16)
+    weights_out = fl(fl(weights weight_scale) q_scale) float32 [M, H] -- pass weight_scale = H^-1/2 softmax_scale and it is fp8_mqa_logits'
+    weights --, else None.  q_scale is always returned: indexer_prepare_backward reads it.  A token whose position lies outside [0, P)
+    is skipped: nothing is read through the table and none of its outputs is written (a padded batch passes -1).  A row holding a NaN or
+    an infinity may get anything in its own outputs and touches no other row.  out=(q_fp8, q_scale[, weights_out]) takes the caller's
+    tensors.  M == 0 returns without a launch; capturable, and a captured graph follows new positions and a new table."""
+    _prep_rows(q, "q", _CAST_DT, "M, H")
+    m, h, d = q.shape
+    _require(h >= 1, "q must have at least one head")
+    _want(q, "q", None, (m, h, d))
+    table_rows = _prep_table(positions, cos_sin, m)
+    specs = [("q_fp8", torch.uint8, (m, h, d)), ("q_scale", torch.float32, (m, h))]
+    if weights is not None:
+        _want(weights, "weights", (torch.float32, torch.bfloat16), (m, h))
+        specs.append(("weights_out", torch.float32, (m, h)))
+    weight_scale = float(weight_scale)
+    o = list(_outputs(out, specs, q.device, "out must be (q_fp8, q_scale, weights_out)" if weights is not None else "out must be (q_fp8, q_scale)"))
+    _require(o[0].data_ptr() % 8 == 0, "out q_fp8 must be 8-byte aligned")
+    if weights is None:
+        o.append(None)
+    _launch("indexer_prepare_q", (q, positions, cos_sin, weights) + tuple(o), lambda L, stream: L.dga_indexer_prepare_q(
+        q.data_ptr(), _CAST_DT[q.dtype], m, h, positions.data_ptr(), positions.dtype == torch.int64, cos_sin.data_ptr(), table_rows,
+        _ptr(weights), _lib.DT_FP32 if weights is None else _CAST_DT[weights.dtype], weight_scale, o[0].data_ptr(), o[1].data_ptr(),
+        _ptr(o[2]), _prep_flags(interleaved, use_ue8m0), stream), sync)
+    return _as_fp8(o[0]), o[1], o[2]
+
+
+def indexer_prepare_k(k: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, norm_weight: Optional[torch.Tensor] = None,
+                      norm_bias: Optional[torch.Tensor] = None, eps: float = 1e-6, kv_cache: Optional[torch.Tensor] = None,
+                      slot_mapping: Optional[torch.Tensor] = None, contiguous: bool = True, interleaved: bool = False,
+                      use_ue8m0: bool = False, out=None, sync: bool = False) -> IndexerPrepareK:
+    """From the indexer's key projection to fp8_mqa_logits' kv and / or fp8_paged_mqa_logits' cache in one launch (dga_indexer_prepare_k):
+    LayerNorm, RoPE, Hadamard rotation, 1x128 quantiser.  k [N, 128] float32 / bfloat16 / float16, contiguous, 16-byte aligned; positions
+    [N], cos_sin, interleaved, use_ue8m0, the skip of a position outside [0, P) and the arithmetic behind the norm: indexer_prepare_q's.
+    With norm_weight (gamma [128], of k's dtype or float32; norm_bias beta alike, or None) the row is LayerNorm'd first, in float32 with
+    the sums in one fixed order (a lane's 8 elements ascending, then a tree over the 16 lanes):
+      mean = fl(sum x / 128), var = fl(sum fl(fl(x - mean)^2) / 128), rstd = 1 / sqrt(var + fl32(eps));
+      |mean - exact| <= 130 2^-24 mean|x| and rstd within (128 / 2 + 8) 2^-24 relative of the float64 statistic taken with the returned mean;
+      z = fl(fl(fl(fl(x - mean) rstd) gamma) + beta) -- everything behind the statistics is an exact float32 function of the returned pair.
+    Returns the named tuple (k_fp8, kscale, mean, rstd): mean and rstd float32 [N] (None without norm_weight; a LayerNorm backward needs
+    them); with contiguous=True k_fp8 float8_e4m3fn [N, 128] and kscale float32 [N] -- fp8_mqa_logits' kv --, else None.  With kv_cache
+    (fp8_paged_mqa_logits' cache) and slot_mapping int64 [N] the token's 128 codes and its scale also go to its slot, in
+    per_token_cast_to_fp8_paged's layout and under its rule: a slot outside [0, 64 num_blocks) skips the cache write only, and no other
+    byte of the cache is touched.  One of contiguous and kv_cache must be asked for.  out: a mapping or an IndexerPrepareK with the
+    caller's tensors under the same names; what it leaves out is allocated.  N == 0 returns without a launch; capturable."""
+    _prep_rows(k, "k", _CAST_DT, "N")
+    n, d = k.shape
+    _want(k, "k", None, (n, d))
+    table_rows = _prep_table(positions, cos_sin, n)
+    _require(norm_bias is None or norm_weight is not None, "norm_bias needs norm_weight")
+    norm = norm_weight is not None
+    if norm:
+        _want(norm_weight, "norm_weight", (k.dtype, torch.float32), (d,))
+        if norm_bias is not None:
+            _want(norm_bias, "norm_bias", norm_weight.dtype, (d,))
+        _require(all(t is None or t.data_ptr() % 16 == 0 for t in (norm_weight, norm_bias)), "norm_weight and norm_bias must be 16-byte aligned")
+    eps = float(eps)
+    _require(eps >= 0.0 and eps != float("inf"), "eps must be finite and >= 0")
+    _require((kv_cache is None) == (slot_mapping is None), "kv_cache and slot_mapping go together")
+    _require(contiguous or kv_cache is not None, "one of contiguous and kv_cache must be asked for")
+    nb = stride = 0
+    if kv_cache is not None:
+        nb, stride = _paged_cache(kv_cache)
+        _want(slot_mapping, "slot_mapping", torch.int64, (n,))
+    given = {} if out is None else out._asdict() if isinstance(out, IndexerPrepareK) else out
+    _require(isinstance(given, dict) and all(key in IndexerPrepareK._fields and (v is None or isinstance(v, torch.Tensor)) for key, v in given.items()),
+             "out must map k_fp8, kscale, mean, rstd to tensors")
+    asked = {"k_fp8": contiguous, "kscale": contiguous, "mean": norm, "rstd": norm}
+    specs = {"k_fp8": (torch.uint8, (n, d)), "kscale": (torch.float32, (n,)), "mean": (torch.float32, (n,)), "rstd": (torch.float32, (n,))}
+    o = {}
+    for name, (dtype, shape) in specs.items():
+        t = given.get(name)
+        if not asked[name]:
+            _require(t is None, "out %s is given but not asked for", name)
+            o[name] = None
+        elif t is None:
+            o[name] = torch.empty(shape, dtype=dtype, device=k.device)
+        else:
+            if name == "k_fp8":
+                _fp8_bytes(t)
+            _want(t, name, None if name == "k_fp8" else dtype, shape, "out ")
+            o[name] = t
+    _require(o["k_fp8"] is None or o["k_fp8"].data_ptr() % 8 == 0, "out k_fp8 must be 8-byte aligned")
+    _launch("indexer_prepare_k", (k, positions, cos_sin, norm_weight, norm_bias, kv_cache, slot_mapping) + tuple(o.values()),
+            lambda L, stream: L.dga_indexer_prepare_k(
+                k.data_ptr(), _CAST_DT[k.dtype], n, positions.data_ptr(), positions.dtype == torch.int64, cos_sin.data_ptr(), table_rows,
+                _ptr(norm_weight), _ptr(norm_bias), _CAST_DT[norm_weight.dtype] if norm else _lib.DT_FP32, eps, _ptr(o["k_fp8"]),
+                _ptr(o["kscale"]), _ptr(o["mean"]), _ptr(o["rstd"]), _ptr(kv_cache), nb, stride, _ptr(slot_mapping),
+                _prep_flags(interleaved, use_ue8m0), stream), sync)
+    if o["k_fp8"] is not None:
+        o["k_fp8"] = _as_fp8(o["k_fp8"])
+    return IndexerPrepareK(**o)
+
+
+def indexer_prepare_backward(grad: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, row_div: Optional[torch.Tensor] = None,
+                             interleaved: bool = False, out_dtype: torch.dtype = torch.bfloat16, d_weights: Optional[torch.Tensor] = None,
+                             weight_scale: float = 1.0, out=None, sync: bool = False):
+    """The backward of indexer_prepare_q / indexer_prepare_k behind the quantiser (dga_indexer_prepare_bwd): fp8_mqa_logits_bwd's dq or dk
+    carried back through the rotation and the RoPE.  grad float32: [M, H, 128] contiguous (dq) with positions [M], or [N, 128] (dk) with a
+    contiguous last dimension and a stride(0) >= 128 that is a multiple of 4, positions [N]; 16-byte aligned.  row_div float32, one per
+    row ([M, H] / [N]): pass q_scale for q and nothing for k.  With it g = fl(grad / row_div) by IEEE division -- the straight-through
+    derivative of the quantiser: code = y / scale is differentiated with the scale taken as a constant (the amax's dependence on y is
+    dropped, and the rounding to e4m3 is the identity), which is what fp8_mqa_logits_bwd's "derivative with respect to the value of the q
+    code" asks the caller to do; dk is already a derivative with respect to the dequantised key and takes none.  Then the Hadamard
+    rotation -- its own transpose, the forward's stages and its factor C -- and the transposed RoPE a' = fl(fl(a c) + fl(b s)),
+    b' = fl(fl(b c) - fl(a s)), all in float32 with nothing contracted; grad_in in out_dtype (float32, or rounded to nearest even to
+    bfloat16 / float16), every element of every token that is not skipped (position outside [0, P): nothing of it is written).  For k the
+    result is the gradient at the LayerNorm's output; the LayerNorm backward stays with the caller (mean and rstd are what it needs).
+    With d_weights (float32, row_div's shape: fp8_mqa_logits_bwd's d_weights; needs row_div) d_weights_raw = fl(fl(d_weights weight_scale)
+    row_div), the derivative at indexer_prepare_q's weights.  Returns (grad_in, d_weights_raw or None); out=(grad_in[, d_weights_raw])
+    takes the caller's.  No rows: no launch; capturable."""
+    _require(grad.dim() in (2, 3), "grad must be [M, H, %d] or [N, %d]", MQA_LOGITS_HEAD_DIM, MQA_LOGITS_HEAD_DIM)
+    _prep_rows(grad, "grad", (torch.float32,), "M, H" if grad.dim() == 3 else "N")
+    d = grad.shape[-1]
+    lead = tuple(grad.shape[:-1])
+    if grad.dim() == 3:
+        _want(grad, "grad", None, lead + (d,))
+        heads, rows, stride = lead[1], lead[0] * lead[1], d
+        _require(heads >= 1, "grad must have at least one head")
+    else:
+        heads, rows = 1, lead[0]
+        stride = grad.stride(0) if rows > 1 else d
+        _require(grad.stride(1) == 1 and stride >= d and stride % 4 == 0,
+                 "grad must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", d, stride)
+    table_rows = _prep_table(positions, cos_sin, lead[0])
+    if row_div is not None:
+        _want(row_div, "row_div", torch.float32, lead)
+    specs = [("grad_in", out_dtype, lead + (d,))]
+    _require(out_dtype in _CAST_DT, "out_dtype must be float32, bfloat16 or float16")
+    if d_weights is not None:
+        _require(row_div is not None, "d_weights needs row_div")
+        _want(d_weights, "d_weights", torch.float32, lead)
+        specs.append(("d_weights_raw", torch.float32, lead))
+    weight_scale = float(weight_scale)
+    o = list(_outputs(out, specs, grad.device, "out must be (grad_in, d_weights_raw)" if d_weights is not None else "out must be (grad_in,)"))
+    _require(o[0].data_ptr() % 16 == 0, "out grad_in must be 16-byte aligned")
+    if d_weights is None:
+        o.append(None)
+    _launch("indexer_prepare_backward", (grad, positions, cos_sin, row_div, d_weights) + tuple(o), lambda L, stream: L.dga_indexer_prepare_bwd(
+        grad.data_ptr(), rows, heads, stride, positions.data_ptr(), positions.dtype == torch.int64, cos_sin.data_ptr(), table_rows,
+        _ptr(row_div), _ptr(d_weights), weight_scale, o[0].data_ptr(), _CAST_DT[out_dtype], _ptr(o[1]), _prep_flags(interleaved), stream), sync)
+    return o[0], o[1]
+
+
 def route_tokens(expert_ids: torch.Tensor, groups: int):
     """(counts int64 [groups], pos int64 [T]): pos[t] = slot of token t in the expert-sorted order (dga_route_tokens)."""
     _require(expert_ids.dtype == torch.int64 and expert_ids.dim() == 1 and expert_ids.is_contiguous(), "expert_ids int64 [T]")

@@ -1184,6 +1184,58 @@ int dga_cast_mla_kv_to_fp8_paged(const void *kv_c, int64_t ld_c, const void *k_p
                                  int64_t num_blocks, int64_t page_size, int64_t block_stride, const int64_t *slot_mapping, int flags,
                                  void *stream);
 
+/* What produces the indexer's operands from the projections' outputs, and its backward (csrc/dga_indexer_prepare.hip).  Common to the
+ * three entries, all in float32 with every operation rounded on its own (nothing is contracted into a fused multiply-add):
+ *   row        128 values, converted exactly from DGA_DT_FP32 / _BF16 / _FP16
+ *   RoPE       on x[0 .. 63]; cos_sin fp32 [table_rows, 64] contiguous, 16-byte aligned, cos of frequency i at column i, sin at 32 + i;
+ *              positions int32 or int64 (pos_i64 != 0) [tokens].  Pair i is (a, b) = (x[i], x[i + 32]), or (x[2 i], x[2 i + 1]) with
+ *              DGA_INDEXER_PREPARE_INTERLEAVED.  Forward a' = fl(fl(a c) - fl(b s)), b' = fl(fl(a s) + fl(b c)); the backward applies the
+ *              transpose a' = fl(fl(a c) + fl(b s)), b' = fl(fl(b c) - fl(a s)).  A token whose position lies outside [0, table_rows) is
+ *              skipped: nothing is read through the table and none of its outputs is written.  Positions and table are read on the device.
+ *   rotation   the fast Walsh-Hadamard transform in natural order: for h = 1, 2, 4, .., 64 in that order every pair (i, i + h) with bit h
+ *              of i clear becomes (fl(u + v), fl(u - v)); then y[i] = fl(t[i] C), C = 0x3DB504F3, the float32 nearest 128^-1/2
+ *   quantiser  dga_cast_to_fp8_1x128_ex on the float32 y, flags & DGA_CAST_UE8M0 included: codes and scale byte for byte
+ * A row that holds a NaN or an infinity may get anything in its own outputs; no other row is touched and nothing is accessed outside
+ * the tensors.  One launch each (capturable); 16 lanes on a row, no LDS, no atomics: two runs give the same bytes.
+ *
+ * dga_indexer_prepare_q: q [m, heads, 128] of q_dtype contiguous, 16-byte aligned, heads >= 1, the position that of the row's token ->
+ * q_fp8 e4m3fn bytes [m, heads, 128] (8-byte aligned), q_scale fp32 [m, heads]; with weights ([m, heads], w_dtype DGA_DT_FP32 or _BF16)
+ * weights_out[t, h] = fl(fl(weights[t, h] weight_scale) q_scale[t, h]) fp32 -- dga_fp8_mqa_logits' weights with the q scale folded in.
+ * Checks: DGA_E_RANGE (an unknown flag);  DGA_E_SHAPE (m < 0, heads < 1, table_rows < 0);  m == 0 -> DGA_OK with nothing touched;
+ * DGA_E_NULL (q, q_fp8, q_scale, positions, cos_sin, one of weights / weights_out without the other);  DGA_E_DTYPE;  DGA_E_ALIGN;
+ * DGA_E_RANGE (the table or the rows beyond int64, the grid).
+ *
+ * dga_indexer_prepare_k: k [n, 128] of k_dtype contiguous, 16-byte aligned, one position per row.  With norm_weight (gamma [128], w_dtype =
+ * k_dtype or DGA_DT_FP32, 16-byte aligned; norm_bias beta alike or NULL) the row is LayerNorm'd first, the sums in one order -- the 8
+ * elements of a lane ascending, then the tree over lanes l ^ 1, 2, 4, 8 --:
+ *   mean = fl(sum x / 128);  var = fl(sum fl(fl(x - mean)^2) / 128);  rstd = fl(1 / fl(sqrt(fl(var + eps))));
+ *   z = fl(fl(fl(fl(x - mean) rstd) gamma) + beta)  (no beta: no addition);  mean and rstd fp32 [n] are written (required then).
+ * Outputs, either or both: k_fp8 [n, 128] with kscale fp32 [n];  kv_cache with slot_mapping int64 [n]: dga_cast_to_fp8_1x128_paged's
+ * layout and rule -- a slot outside [0, 64 num_blocks) skips the cache write only, no other byte of the cache is touched.
+ * Checks: DGA_E_RANGE (flag);  DGA_E_SHAPE (n < 0, table_rows < 0, with kv_cache num_blocks < 1 or block_stride < 8448);  n == 0 ->
+ * DGA_OK;  DGA_E_NULL (k, positions, cos_sin, neither output, k_fp8 / kscale or kv_cache / slot_mapping one without the other, norm_bias
+ * without norm_weight, norm_weight without mean and rstd);  DGA_E_DTYPE;  DGA_E_RANGE (eps negative, NaN or infinite);  DGA_E_ALIGN
+ * (block_stride not a multiple of 16 included);  DGA_E_RANGE (sizes beyond int64, the grid).
+ *
+ * dga_indexer_prepare_bwd: grad fp32 [rows, 128], rows grad_stride floats apart (>= 128 and a multiple of 4), 16-byte aligned;
+ * rows = tokens heads, the position that of token row / heads (heads = 1 for keys).  g = fl(grad / row_div[row]) by IEEE division
+ * (row_div fp32 [rows] or NULL: g = grad), the rotation (its own transpose), the transposed RoPE -> grad_in [rows, 128] contiguous of
+ * out_dtype (DGA_DT_FP32, or rounded to nearest even to _BF16 / _FP16), every element of every row that is not skipped.  With d_weights
+ * (fp32 [rows], needs row_div): d_weights_raw[row] = fl(fl(d_weights[row] weight_scale) row_div[row]).
+ * Checks: DGA_E_RANGE (flag: only DGA_INDEXER_PREPARE_INTERLEAVED);  DGA_E_SHAPE (rows < 0, heads < 1, rows % heads, grad_stride < 128,
+ * table_rows < 0);  rows == 0 -> DGA_OK;  DGA_E_NULL;  DGA_E_DTYPE (out_dtype);  DGA_E_ALIGN;  DGA_E_RANGE (sizes beyond int64, the grid). */
+#define DGA_INDEXER_PREPARE_INTERLEAVED 0x100
+int dga_indexer_prepare_q(const void *q, int q_dtype, int64_t m, int64_t heads, const void *positions, int pos_i64, const float *cos_sin,
+                          int64_t table_rows, const void *weights, int w_dtype, float weight_scale, void *q_fp8, float *q_scale,
+                          float *weights_out, int flags, void *stream);
+int dga_indexer_prepare_k(const void *k, int k_dtype, int64_t n, const void *positions, int pos_i64, const float *cos_sin, int64_t table_rows,
+                          const void *norm_weight, const void *norm_bias, int w_dtype, float eps, void *k_fp8, float *kscale, float *mean,
+                          float *rstd, void *kv_cache, int64_t num_blocks, int64_t block_stride, const int64_t *slot_mapping, int flags,
+                          void *stream);
+int dga_indexer_prepare_bwd(const float *grad, int64_t rows, int64_t heads, int64_t grad_stride, const void *positions, int pos_i64,
+                            const float *cos_sin, int64_t table_rows, const float *row_div, const float *d_weights, float weight_scale,
+                            void *grad_in, int out_dtype, float *d_weights_raw, int flags, void *stream);
+
 /* ---- the expert-sharded forward behind the C ABI (csrc/dga_sharded.cpp) ----------------------------------
  * What a C++ host (the reference's host language: framework/csrc/python_api.cpp) calls to run BASELINE configs[4]: expert g
  * lives on rank g / (groups_total / world), one all-to-all of payload rows each way, every shape static, nothing read back.
