@@ -202,6 +202,9 @@ SIGNATURES = {
                                    c_void_p]),
     "dga_fp8_mqa_logits_bwd": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                        c_void_p, c_void_p]),
+    "dga_fp8_mqa_logits_bwd_dense_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dga_fp8_mqa_logits_bwd_dense": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                             c_void_p, c_int64, c_void_p]),
     "dga_fp8_paged_mqa_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int64,
                                          c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "dga_cast_to_fp8_1x128_paged": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),

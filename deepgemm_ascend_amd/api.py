@@ -1853,6 +1853,27 @@ def _mqa_selected(t: torch.Tensor, what: str, dtype, m: int, topk: Optional[int]
     return stride
 
 
+def _mqa_bwd_outputs(q: torch.Tensor, k: torch.Tensor, m: int, h: int, d: int, n: int, dq, dk, d_weights):
+    """The outputs the two backwards of fp8_mqa_logits share, checked in one order: dq and d_weights from torch.empty, dk from torch.zeros
+    (it is added into), or the caller's.  Returns (dq, dk, d_weights, dk's stride(0))."""
+    if dq is None:
+        dq = torch.empty((m, h, d), dtype=torch.float32, device=q.device)
+    else:
+        _want(dq, "dq", torch.float32, (m, h, d))
+    if d_weights is None:
+        d_weights = torch.empty((m, h), dtype=torch.float32, device=q.device)
+    else:
+        _want(d_weights, "d_weights", torch.float32, (m, h))
+    if dk is None:
+        dk = torch.zeros((n, d), dtype=torch.float32, device=q.device)
+    _require(dk.dtype == torch.float32 and dk.dim() == 2 and tuple(dk.shape) == (n, d), "dk must be a float32 [N, %d] tensor with k's N = %d rows", d, n)
+    dk_stride = dk.stride(0) if n > 1 else d
+    _require(dk.stride(1) == 1 and dk_stride >= d and dk_stride % 4 == 0,
+             "dk must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", d, dk_stride)
+    _require(all(x.data_ptr() % 16 == 0 for x in (q, k, dq, dk)), "q, k, dq and dk must be 16-byte aligned")
+    return dq, dk, d_weights, dk_stride
+
+
 def fp8_mqa_logits_bwd(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weights: torch.Tensor, indices: torch.Tensor,
                        d_logits: torch.Tensor, index_offsets: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
                        dk: Optional[torch.Tensor] = None, d_weights: Optional[torch.Tensor] = None,
@@ -1890,26 +1911,58 @@ def fp8_mqa_logits_bwd(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], w
     dl_stride = _mqa_selected(d_logits, "d_logits", torch.float32, m, topk)
     if index_offsets is not None:
         _want(index_offsets, "index_offsets", torch.int32, (m,))
-    if dq is None:
-        dq = torch.empty((m, h, d), dtype=torch.float32, device=q.device)
-    else:
-        _want(dq, "dq", torch.float32, (m, h, d))
-    if d_weights is None:
-        d_weights = torch.empty((m, h), dtype=torch.float32, device=q.device)
-    else:
-        _want(d_weights, "d_weights", torch.float32, (m, h))
-    if dk is None:
-        dk = torch.zeros((n, d), dtype=torch.float32, device=q.device)
-    _require(dk.dtype == torch.float32 and dk.dim() == 2 and tuple(dk.shape) == (n, d), "dk must be a float32 [N, %d] tensor with k's N = %d rows", d, n)
-    dk_stride = dk.stride(0) if n > 1 else d
-    _require(dk.stride(1) == 1 and dk_stride >= d and dk_stride % 4 == 0,
-             "dk must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", d, dk_stride)
-    _require(all(x.data_ptr() % 16 == 0 for x in (q, k, dq, dk)), "q, k, dq and dk must be 16-byte aligned")
+    dq, dk, d_weights, dk_stride = _mqa_bwd_outputs(q, k, m, h, d, n, dq, dk, d_weights)
     # (M == 0: the C entry returns before any launch)
     _launch("fp8_mqa_logits_bwd", (q, k, kscale, weights, indices, index_offsets, d_logits, dq, dk, d_weights),
             lambda L, stream: L.dga_fp8_mqa_logits_bwd(
                 q.data_ptr(), k.data_ptr(), kscale.data_ptr(), weights.data_ptr(), indices.data_ptr(), _ptr(index_offsets), d_logits.data_ptr(),
                 m, n, h, d, topk, idx_stride, dl_stride, dq.data_ptr(), dk.data_ptr(), dk_stride, d_weights.data_ptr(), stream), sync)
+    return dq, dk, d_weights
+
+
+def fp8_mqa_logits_bwd_dense(q: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor], weights: torch.Tensor, d_logits: torch.Tensor,
+                             cu_seq_len_k_start: torch.Tensor, cu_seq_len_k_end: torch.Tensor, dq: Optional[torch.Tensor] = None,
+                             dk: Optional[torch.Tensor] = None, d_weights: Optional[torch.Tensor] = None,
+                             sync: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The backward of fp8_mqa_logits over ALL keys of a token's range (dga_fp8_mqa_logits_bwd_dense): the lightning indexer's gradients
+    (dq, dk, d_weights) in the dense warm-up stage, where the indexer is trained against the main attention's distribution over every
+    key before any top-k exists.  q, kv = (k, kscale) and weights are fp8_mqa_logits' operands with its checks (q and k 16-byte
+    aligned);  cu_seq_len_k_start / cu_seq_len_k_end int32 [M] device tensors, read and clamped to [0, N] on the device exactly as the
+    forward does, ke <= ks an empty token;  d_logits float32 [M, N] with a contiguous last dimension and stride(0) >= N: an element
+    outside its token's range is never read, whatever it holds (the forward wrote -inf there, a loss may leave anything).  For token m
+    and every key n inside [ks[m], ke[m]), with s_hn = sum_d q[m, h, d] k[n, d] on the code values and mask_hn = s_hn > 0:
+    d_weights[m, h] = sum_n d_logits[m, n] kscale[n] (mask_hn ? s_hn : 0);
+    dq[m, h, :] = weights[m, h] sum_n mask_hn d_logits[m, n] kscale[n] k[n, :];
+    dk[n, :] += sum_m sum_h mask_hn d_logits[m, n] weights[m, h] q[m, h, :]
+    -- fp8_mqa_logits_bwd's definition with "valid position j" replaced by "key n inside the range".
+    dq float32 [M, H, 128] and d_weights float32 [M, H], contiguous (torch.empty when None): every element is written, +0 for a token
+    with an empty range.  dk float32 [N, 128] with a contiguous last dimension, stride(0) >= 128 and a multiple of 4, 16-byte aligned:
+    ADDED INTO -- None allocates torch.zeros, a caller's tensor accumulates over chunks of M -- as fl(prior + sum), once per element; a
+    row that no token's range names is not written, and no byte beyond column 127.
+    Arithmetic: fp8_mqa_logits_bwd's (scores on the matrix pipe in fp32 on exactly converted codes, the mask on that fp32 value,
+    d_weights an fp32 fused multiply-add chain, weights d_logits and its product with kscale carried as two bf16 terms, all sums fp32),
+    so its bounds hold.  Non-finite inputs are outside the contract and cause no access outside the tensors.
+    Determinism is the point of the dense form: no floating-point atomics; dq, d_weights AND dk are byte-reproducible, the order of
+    every sum fixed by the shapes and the ranges alone (dk: the tokens of a chunk ascending on the matrix pipe, then the chunks
+    ascending).
+    Returns (dq, dk, d_weights).  Three launches on the current stream (dq and d_weights, token-owned; dk's partial tiles, key-owned,
+    into scratch; their sum onto dk), capturable, everything read on the device; M == 0 returns without one."""
+    k, kscale, m, h, d, n = _mqa_operands(q, kv, weights)
+    _want(cu_seq_len_k_start, "cu_seq_len_k_start", torch.int32, (m,))
+    _want(cu_seq_len_k_end, "cu_seq_len_k_end", torch.int32, (m,))
+    _require(d_logits.dtype == torch.float32 and d_logits.dim() == 2 and tuple(d_logits.shape) == (m, n),
+             "d_logits must be a float32 [M, N] tensor with k's N = %d columns", n)
+    dl_stride = d_logits.stride(0) if m > 1 else n
+    _require((n == 1 or d_logits.stride(1) == 1) and dl_stride >= n, "d_logits must have a contiguous last dimension and stride(0) >= N")
+    dq, dk, d_weights, dk_stride = _mqa_bwd_outputs(q, k, m, h, d, n, dq, dk, d_weights)
+
+    def call(L, stream):
+        # (M == 0: no scratch, and the C entry returns before any launch)
+        ws_ptr, ws_bytes = _scratch("mqa_bwd_dense", q.device, int(L.dga_fp8_mqa_logits_bwd_dense_workspace_bytes(m, n)))
+        return L.dga_fp8_mqa_logits_bwd_dense(
+            q.data_ptr(), k.data_ptr(), kscale.data_ptr(), weights.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(),
+            d_logits.data_ptr(), m, n, h, d, dl_stride, dq.data_ptr(), dk.data_ptr(), dk_stride, d_weights.data_ptr(), ws_ptr, ws_bytes, stream)
+    _launch("fp8_mqa_logits_bwd_dense", (q, k, kscale, weights, cu_seq_len_k_start, cu_seq_len_k_end, d_logits, dq, dk, d_weights), call, sync)
     return dq, dk, d_weights
 
 

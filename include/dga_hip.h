@@ -940,6 +940,35 @@ int dga_fp8_mqa_logits_bwd(const void *q, const void *k, const float *kscale, co
                            const int32_t *index_offsets, const float *d_logits, int64_t m, int64_t n, int heads, int head_dim, int64_t topk,
                            int64_t idx_stride, int64_t dl_stride, float *dq, float *dk, int64_t dk_stride, float *d_weights, void *stream);
 
+/* The same gradients over ALL keys of a token's range (csrc/dga_mqa_logits_bwd_dense.hip): the dense warm-up stage, before any top-k exists.
+ *   q, k, kscale, weights, ks, ke, m, n, heads, head_dim: dga_fp8_mqa_logits' (q and k 16-byte aligned here); the ranges are read and
+ *                 clamped to [0, n] on the device exactly as the forward does, hi <= lo is an empty token
+ *   d_logits      fp32 [m, n], rows dl_stride elements apart (>= n): the derivative at logits[t, j].  An element outside its token's range is
+ *                 never read, whatever it holds (the forward wrote -inf there)
+ *   dq, d_weights, dk, dk_stride: dga_fp8_mqa_logits_bwd's, with "valid position j" replaced by "key j inside [lo[t], hi[t])":
+ *     d_weights[t, h] = sum_j d_logits[t, j] kscale[j] (mask_hj ? s_hj : 0)
+ *     dq[t, h, :]     = weights[t, h] sum_j mask_hj d_logits[t, j] kscale[j] k[j, :]
+ *     dk[j, :]       += sum_t sum_h mask_hj d_logits[t, j] weights[t, h] q[t, h, :]
+ *   every element of dq and d_weights is written (+0 for an empty token); dk is ADDED INTO, once per element: fl(prior + sum); a row that no
+ *   token's range names is not written, and no column >= 128 of any row.
+ *   workspace     dga_fp8_mqa_logits_bwd_dense_workspace_bytes(m, n) bytes, 16-byte aligned: the partial dk tiles of the token chunks
+ * Arithmetic: dga_fp8_mqa_logits_bwd's (exact codes, chained v_mfma_f32_16x16x32_bf16 scores, the mask on the fp32 accumulator, Gk a select,
+ * Gk and Gq as two bf16 terms each, fp32 sums), so its bounds hold with "n additions" for the atomics' "n atomic additions".
+ * Determinism: no floating-point atomics; each output has one owner and every sum an order that the shapes and the ranges alone fix: two
+ * runs give the same bytes in dq, d_weights AND dk.  Non-finite inputs are outside the contract and cause no access outside the tensors.
+ * Three launches (dq and d_weights by runs of DGA_MQA_LOGITS_BWD_DENSE_RUN tokens; dk's partial tiles of DGA_MQA_LOGITS_BWD_DENSE_TILE
+ * keys; their sum onto dk), capturable, everything read on the device.
+ * Checks, all before the first launch: DGA_E_SHAPE (m < 0, n < 1, head_dim != 128, heads other than 32 or 64, dl_stride < n,
+ * dk_stride < 128);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (any pointer);  DGA_E_ALIGN (q, k, dq or dk not 16-byte, any other
+ * pointer not 4-byte aligned, dk_stride not a multiple of 4);  DGA_E_RANGE (n > DGA_MQA_LOGITS_MAX_N, m dl_stride or n dk_stride beyond
+ * int64, a grid beyond int32);  DGA_E_WORKSPACE (too small, or not 16-byte aligned). */
+#define DGA_MQA_LOGITS_BWD_DENSE_TILE 64
+#define DGA_MQA_LOGITS_BWD_DENSE_RUN 2
+int64_t dga_fp8_mqa_logits_bwd_dense_workspace_bytes(int64_t m, int64_t n);
+int dga_fp8_mqa_logits_bwd_dense(const void *q, const void *k, const float *kscale, const float *weights, const int32_t *ks, const int32_t *ke,
+                                 const float *d_logits, int64_t m, int64_t n, int heads, int head_dim, int64_t dl_stride, float *dq, float *dk,
+                                 int64_t dk_stride, float *d_weights, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The decode half of that scoring, upstream DeepGEMM's fp8_paged_mqa_logits (csrc/dga_paged_mqa_logits.hip): each of `batch` sequences
  * scores its next_n (1 or 2) newest tokens against its whole context, whose keys live in a paged cache reached through a block table.
  *   kv_cache      block b is DGA_PAGED_MQA_LOGITS_BLOCK_BYTES = 8448 bytes at b * block_stride: bytes 0 .. 8191 the e4m3 codes of its
