@@ -2140,6 +2140,27 @@ def _smla_bf16_rows(q: torch.Tensor, kv: torch.Tensor) -> Tuple[int, int]:
     return s, kv_stride
 
 
+def _smla_q(q: torch.Tensor, sm_scale, d_v: int = SPARSE_MLA_D_V) -> Tuple[int, int]:
+    """q of the attention forms and of the indexer's two losses, checked with sm_scale and d_v: (M, Hq)"""
+    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
+             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
+    m, heads = q.shape[0], q.shape[1]
+    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
+             SPARSE_MLA_MAX_HEADS, heads)
+    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
+    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    return m, heads
+
+
+def _key_columns(t: torch.Tensor, name: str, m: int, s: int) -> int:
+    """a float32 [M, N] tensor of the indexer's two losses, one column a kv row, rows stride(0) >= N apart, checked: that stride"""
+    _require(t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (m, s),
+             "%s must be a float32 [M, N] tensor with N = kv's S = %d columns", name, s)
+    stride = t.stride(0) if m > 1 else s
+    _require((s == 1 or t.stride(1) == 1) and stride >= s, "%s must have a contiguous last dimension and stride(0) >= N", name)
+    return stride
+
+
 def _smla_outputs(out: Optional[torch.Tensor], lse: Optional[torch.Tensor], m: int, heads: int, device):
     """out bfloat16 [M, Hq, 512] and lse float32 [M, Hq]: torch.empty, or the caller's, checked"""
     if out is None:
@@ -2164,13 +2185,7 @@ def _smla_problem(fp8: bool, q: torch.Tensor, rows: torch.Tensor, indices: torch
     """What every attention form checks, in the order every form reports: q, the rows, indices.  Returns (M, Hq, topk, args): what the
     bodies size their outputs by, and the arguments that follow the four pointers in every C entry of the family -- M, Hq, the source's
     geometry, topk, idx_stride, sm_scale.  (The pointers are taken at the launch, behind the guard: a refused call pays for its checks.)"""
-    _require(q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[2] == SPARSE_MLA_D_QK and q.is_contiguous(),
-             "q must be a contiguous bfloat16 [M, Hq, %d] tensor", SPARSE_MLA_D_QK)
-    m, heads = q.shape[0], q.shape[1]
-    _require(heads % 16 == 0 and 16 <= heads <= SPARSE_MLA_MAX_HEADS, "Hq must be a multiple of 16 in [16, %d], got %d",
-             SPARSE_MLA_MAX_HEADS, heads)
-    _require(d_v == SPARSE_MLA_D_V, "d_v must be %d", SPARSE_MLA_D_V)
-    _require(isinstance(sm_scale, (int, float)), "sm_scale must be a number")
+    m, heads = _smla_q(q, sm_scale, d_v)
     if fp8:
         geometry = _mla_fp8_cache(rows)
         _require(q.data_ptr() % 16 == 0, "q must be 16-byte aligned")
@@ -2293,10 +2308,7 @@ def indexer_kl_loss(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, ls
     m, heads, topk, args = _smla_problem(False, q, kv, indices, sm_scale, SPARSE_MLA_D_V, index_offsets)
     s = kv.shape[0]
     _want(lse, "lse", torch.float32, (m, heads))
-    _require(logits.dtype == torch.float32 and logits.dim() == 2 and tuple(logits.shape) == (m, s),
-             "logits must be a float32 [M, N] tensor with N = kv's S = %d columns", s)
-    lg_stride = logits.stride(0) if m > 1 else s
-    _require((s == 1 or logits.stride(1) == 1) and lg_stride >= s, "logits must have a contiguous last dimension and stride(0) >= N")
+    lg_stride = _key_columns(logits, "logits", m, s)
     _require(isinstance(grad_scale, (int, float)), "grad_scale must be a number")
     want_target = want_target or target is not None
     specs = (("loss", loss, (m,)), ("d_logits", d_logits, (m, topk)), ("target", target, (m, topk)))[:3 if want_target else 2]
@@ -2312,6 +2324,65 @@ def indexer_kl_loss(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, ls
         q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, 0, lse.data_ptr(), logits.data_ptr(), lg_stride,
         float(grad_scale), outs[0].data_ptr(), outs[1].data_ptr(), _ptr(outs[2] if want_target else None), stream), sync)
     return tuple(outs)
+
+
+def indexer_kl_loss_dense(q: torch.Tensor, kv: torch.Tensor, cu_seq_len_k_start: torch.Tensor, cu_seq_len_k_end: torch.Tensor,
+                          sm_scale: float, logits: torch.Tensor, lse: Optional[torch.Tensor] = None, grad_scale: float = 1.0,
+                          want_target: bool = False, loss: Optional[torch.Tensor] = None, d_logits: Optional[torch.Tensor] = None,
+                          target: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, sync: bool = False):
+    """The lightning indexer's loss and its derivative in the dense warm-up stage (dga_indexer_kl_loss_dense): indexer_kl_loss over ALL
+    keys of a token's range, before any top-k exists, and the main attention's lse over that range.  q bfloat16 [M, Hq, 576] and kv
+    bfloat16 [S, 576] or [S, 1, 576] are sparse_mla_fwd's, with its checks;  cu_seq_len_k_start / cu_seq_len_k_end int32 [M] device
+    tensors, read and clamped to [0, S] on the device exactly as fp8_mqa_logits and fp8_mqa_logits_bwd_dense do, ke <= ks an empty
+    token;  logits float32 [M, N] with a contiguous last dimension and stride(0) >= N, N == S: fp8_mqa_logits' output, key column n =
+    kv row n, -inf outside the ranges included -- an element outside its token's range is never read;  lse float32 [M, Hq] contiguous
+    or None: given, it is taken as it is (as indexer_kl_loss does); None -- the default, no dense MLA forward exists here to supply it --
+    a first launch computes it over each token's range into lse_out (float32 [M, Hq], torch.empty when None).  grad_scale a Python number.
+    Over the keys n of [ks[m], ke[m]), indexer_kl_loss's formulas with "valid position j" replaced by "key n inside the range":
+    s_hn = sm_scale sum_d q[m, h, d] kv[n, d];  lse[m, h] = ln sum_n exp(s_hn);  p_hn = exp(s_hn - lse[m, h]);  t_n = (1 / Hq) sum_h p_hn;
+    L = ln sum_n exp(logits[m, n]);  a_n = logits[m, n] - L;  y_n = exp(a_n);  loss[m] = sum_n (t_n > 0 ? t_n (ln t_n - a_n) : 0);
+    d_logits[m, n] = grad_scale (y_n - t_n).  The target is a constant: nothing flows into q, kv or lse.
+    loss float32 [M] contiguous;  d_logits float32 [M, N] with a contiguous last dimension and stride(0) >= N -- what
+    fp8_mqa_logits_bwd_dense takes as it stands --, and target likewise when want_target is set or target= is given; torch.empty when
+    None.  Every element of every output is written on every call: outside a token's range d_logits = target = +0 (selected, never
+    computed); an empty token gets loss = +0, rows of +0, and lse = -inf where the operator computes it (a given lse of an empty token may
+    hold anything, NaN included).
+    Arithmetic: a score is the sparse forward's chain on the matrix pipe (fp32, d ascending), the same instructions in both launches, so
+    p cannot exceed 1 by more than the rounding of lse; lse from an online maximum, one rescale per tile of 32 keys; p in fp32, never
+    rounded to bf16; every sum fp32 in an order the shapes and the ranges alone fix.  One writer per element, no atomics: two runs give
+    the same bytes.  Non-finite logits or lse inside a range are outside the contract and cause no access outside the tensors.
+    Returns (loss, d_logits, lse) or (loss, d_logits, lse, target).  Two launches (one when lse is given), capturable, everything read
+    on the device; M == 0 returns without one."""
+    m, heads = _smla_q(q, sm_scale)
+    s, kv_stride = _smla_bf16_rows(q, kv)
+    _want(cu_seq_len_k_start, "cu_seq_len_k_start", torch.int32, (m,))
+    _want(cu_seq_len_k_end, "cu_seq_len_k_end", torch.int32, (m,))
+    lg_stride = _key_columns(logits, "logits", m, s)
+    _require(isinstance(grad_scale, (int, float)), "grad_scale must be a number")
+    _require(lse is None or lse_out is None, "lse_out is only written when lse is None")
+    if lse is None and lse_out is None:
+        lse_out = torch.empty((m, heads), dtype=torch.float32, device=q.device)
+    else:
+        _want(lse if lse is not None else lse_out, "lse" if lse is not None else "lse_out", torch.float32, (m, heads))
+    if loss is None:
+        loss = torch.empty((m,), dtype=torch.float32, device=q.device)
+    else:
+        _want(loss, "loss", torch.float32, (m,))
+    want_target = want_target or target is not None
+    if d_logits is None:
+        d_logits = torch.empty((m, s), dtype=torch.float32, device=q.device)
+    if want_target and target is None:
+        target = torch.empty((m, s), dtype=torch.float32, device=q.device)
+    dl_stride = _key_columns(d_logits, "d_logits", m, s)
+    tg_stride = _key_columns(target, "target", m, s) if want_target else 0
+    # (M == 0: the C entry returns before any launch)
+    _launch("indexer_kl_loss_dense", (q, kv, cu_seq_len_k_start, cu_seq_len_k_end, lse, logits, loss, d_logits, target, lse_out),
+            lambda L, stream: L.dga_indexer_kl_loss_dense(
+                q.data_ptr(), kv.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(), m, heads, s, kv_stride, float(sm_scale),
+                _ptr(lse), logits.data_ptr(), lg_stride, float(grad_scale), loss.data_ptr(), d_logits.data_ptr(), dl_stride, _ptr(target),
+                tg_stride, _ptr(lse_out), stream), sync)
+    out = (loss, d_logits, lse if lse is not None else lse_out)
+    return out + (target,) if want_target else out
 
 
 SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values

@@ -1200,6 +1200,35 @@ int dga_indexer_kl_loss(const void *q, const void *kv, const int32_t *indices, c
                         int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const float *lse, const float *logits,
                         int64_t logits_stride, double grad_scale, float *loss, float *d_logits, float *target, void *stream);
 
+/* The same loss over ALL keys of a token's range (csrc/dga_indexer_kl_dense.hip): the dense warm-up stage, before any top-k exists -- what
+ * dga_fp8_mqa_logits_bwd_dense takes as d_logits.  No list and no gather: key column n is kv row n.
+ *   q, kv, m, heads, s, kv_stride, sm_scale: dga_sparse_mla_fwd's;  ks, ke int32 [m]: read and clamped to [0, s] on the device exactly as
+ *                 dga_fp8_mqa_logits does, hi <= lo is an empty token
+ *   lse           fp32 [m, heads] (natural log) or null.  Given: taken as it is.  Null: a first launch computes
+ *                 lse[t, h] = ln sum_n exp(sm_scale sum_d q[t, h, d] kv[n, d]) over the token's range into lse_out (-inf for an empty token),
+ *                 and the loss launch reads it from there.  lse_out is not looked at when lse is given.
+ *   logits        fp32 [m, s], rows logits_stride elements apart (>= s): dga_fp8_mqa_logits' output; an element outside its token's range
+ *                 is never read, whatever it holds
+ *   loss          fp32 [m];  d_logits fp32 [m, s], rows dl_stride apart (>= s);  target fp32 [m, s], rows target_stride apart (>= s), or null
+ *   over the keys n of [lo[t], hi[t]), L2E = (float)log2 e, LN2 = (float)ln 2: dga_indexer_kl_loss's formulas with "valid position j"
+ *   replaced by "key n inside the range" (p_hn, t_n, L, a_n, y_n, loss[t], d_logits[t, n], target[t, n]).  Every element of every output
+ *   is written: outside the range d_logits = target = +0 (selected, never computed); an empty token gets loss = +0 and rows of +0 whatever a
+ *   given lse holds.  A non-finite logit or lse inside a range may put anything into that token's outputs and causes no access outside the
+ *   tensors: every address comes from the shapes and the clamped ranges.
+ * Arithmetic: a score is 18 chained v_mfma_f32_16x16x32_bf16 over d ascending from +0 in both launches (one templated walk, so the loss
+ * launch's score is the lse launch's bit for bit); lse = LN2 (max + log2 sum) from an online maximum with one rescale a tile; p in fp32,
+ * never rounded to bf16; every sum fp32 in an order the shapes and the ranges alone fix.  One writer per element, no atomics: two runs give
+ * the same bytes.  One or two launches (capturable) by runs of DGA_INDEXER_KL_DENSE_RUN tokens, everything read on the device.
+ * Checks, all before the first launch: DGA_E_SHAPE (m < 0, heads no multiple of 16 in [16, 128], s < 1, kv_stride < 576, logits_stride,
+ * dl_stride or -- with target -- target_stride < s);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (q, kv, ks, ke, logits, loss,
+ * d_logits, lse and lse_out both);  DGA_E_ALIGN (q or kv not 16-byte, any other pointer not 4-byte aligned, kv_stride not a multiple of 8);
+ * DGA_E_RANGE (s + 1024 beyond int32, m times a row stride or s kv_stride beyond int64, the grid beyond int32). */
+#define DGA_INDEXER_KL_DENSE_RUN 2
+int dga_indexer_kl_loss_dense(const void *q, const void *kv, const int32_t *ks, const int32_t *ke, int64_t m, int heads, int64_t s,
+                              int64_t kv_stride, double sm_scale, const float *lse, const float *logits, int64_t logits_stride,
+                              double grad_scale, float *loss, float *d_logits, int64_t dl_stride, float *target, int64_t target_stride,
+                              float *lse_out, void *stream);
+
 /* The writer of the paged fp8 latent cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
  * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
  * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
