@@ -83,6 +83,9 @@ int launch_bf16x_image(const GemmParams &p, int waves, hipStream_t stream);
 // the persistent form of the 128 x 256 in-register build (bf16 rows: dense / masked grouped rasters; the fp32 forms: dense);
 // DGA_E_TILING: not a launch it takes
 int launch_bf16x_persistent(const GemmParams &p, Out out, hipStream_t stream);
+// its paired body (gemm_fp8_bf16x_pair_kernel.hpp; dga_launch_menu_q.hip): dense bf16 rasters, K a multiple of 128; grid 0: one
+// workgroup per CU.  launch_bf16x_persistent decides when it runs
+int launch_bf16x_pair(const GemmParams &p, unsigned grid, hipStream_t stream);
 // the k-grouped weight-gradient builds (KGROUP = 1; dga_launch_menu_p.hip): the one-tile tiles, the persistent 128 x 256 build and the
 // strict kernel (bm 64 or 32) on the G x tiles(M, N) raster whose groups lie along K; DGA_E_TILING for any other raster
 template <class Cfg>
