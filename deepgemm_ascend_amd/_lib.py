@@ -218,6 +218,7 @@ SIGNATURES = {
     "dga_indexer_kl_loss": (c_int, _smla_args([c_int64] * 2, _SMLA_KL_LOSS)),
     "dga_indexer_kl_loss_dense": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int64, c_int64, c_double, c_void_p, c_void_p, c_int64, c_double,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "dga_mla_fwd_dense": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int64, c_int64, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,

@@ -2336,7 +2336,7 @@ def indexer_kl_loss_dense(q: torch.Tensor, kv: torch.Tensor, cu_seq_len_k_start:
     tensors, read and clamped to [0, S] on the device exactly as fp8_mqa_logits and fp8_mqa_logits_bwd_dense do, ke <= ks an empty
     token;  logits float32 [M, N] with a contiguous last dimension and stride(0) >= N, N == S: fp8_mqa_logits' output, key column n =
     kv row n, -inf outside the ranges included -- an element outside its token's range is never read;  lse float32 [M, Hq] contiguous
-    or None: given, it is taken as it is (as indexer_kl_loss does); None -- the default, no dense MLA forward exists here to supply it --
+    or None: given, it is taken as it is (as indexer_kl_loss does); None -- the default; mla_fwd_dense returns one over the same ranges --
     a first launch computes it over each token's range into lse_out (float32 [M, Hq], torch.empty when None).  grad_scale a Python number.
     Over the keys n of [ks[m], ke[m]), indexer_kl_loss's formulas with "valid position j" replaced by "key n inside the range":
     s_hn = sm_scale sum_d q[m, h, d] kv[n, d];  lse[m, h] = ln sum_n exp(s_hn);  p_hn = exp(s_hn - lse[m, h]);  t_n = (1 / Hq) sum_h p_hn;
@@ -2383,6 +2383,40 @@ def indexer_kl_loss_dense(q: torch.Tensor, kv: torch.Tensor, cu_seq_len_k_start:
                 tg_stride, _ptr(lse_out), stream), sync)
     out = (loss, d_logits, lse if lse is not None else lse_out)
     return out + (target,) if want_target else out
+
+
+def mla_fwd_dense(q: torch.Tensor, kv: torch.Tensor, cu_seq_len_k_start: torch.Tensor, cu_seq_len_k_end: torch.Tensor, sm_scale: float,
+                  d_v: int = 512, out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, sync: bool = False,
+                  _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The main attention of the dense stage (dga_mla_fwd_dense): MLA attention, forward, in the absorbed (MQA) form over EVERY key of a
+    token's range -- the dense warm-up stage, a dense-MLA layer, a prefill whose range exceeds sparse_mla_fwd's list.  No list and no
+    gather: key n is kv row n.  q bfloat16 [M, Hq, 576] and kv bfloat16 [S, 576] or [S, 1, 576] are sparse_mla_fwd's, with its checks;
+    cu_seq_len_k_start / cu_seq_len_k_end int32 [M] device tensors, read and clamped to [0, S] on the device exactly as fp8_mqa_logits
+    and indexer_kl_loss_dense do, ke <= ks an empty token;  d_v must be 512.
+    Over the keys n of [ks[m], ke[m]):  s_n = sm_scale sum_d q[m, h, d] kv[n, d];  lse[m, h] = ln sum_n exp(s_n) (float32 [M, Hq], natural
+    log -- what indexer_kl_loss_dense(lse=...) takes as given, which saves that operator its own score pass);
+    out[m, h, :] = sum_n exp(s_n - lse) kv[n, :512] (bfloat16 [M, Hq, 512]).  An empty token gets out = +0 and lse = -inf.  Every element
+    of both outputs is written on every call.
+    What kv rows may hold: a row outside EVERY token's clamped range of the call (below the smallest ks or at or above the largest ke of
+    the non-empty tokens) is never read and may hold anything, NaN included.  A row inside that span but outside token m's own range
+    contributes nothing to m provided it is finite: its weight is a selected 0, which a NaN among its value columns would not survive.
+    Non-finite values inside the span are outside the contract and cause no access outside the tensors.  No row >= S and no column
+    >= 576 of any row is read.
+    Arithmetic: sparse_mla_fwd's, over tiles of 32 consecutive rows ascending: exact bf16 products summed in fp32 on the matrix pipe
+    over d ascending; an online softmax, one rescale a tile; the weights rounded to bf16 (RNE) for the second product while their sum l
+    stays unrounded fp32; one multiplication by 1 / l at the end.  One writer per element, no atomics, every sum in an order the shapes
+    and the ranges alone fix: two runs give the same bytes.  Returns (out, lse), the caller's out= / lse= when given.  One launch,
+    capturable -- a replayed graph follows new ranges, q and kv; M == 0 returns without one."""
+    m, heads = _smla_q(q, sm_scale, d_v)
+    s, kv_stride = _smla_bf16_rows(q, kv)
+    _want(cu_seq_len_k_start, "cu_seq_len_k_start", torch.int32, (m,))
+    _want(cu_seq_len_k_end, "cu_seq_len_k_end", torch.int32, (m,))
+    out, lse = _smla_outputs(out, lse, m, heads, q.device)
+    # (M == 0: the C entry returns before any launch)
+    _launch("mla_fwd_dense", (q, kv, cu_seq_len_k_start, cu_seq_len_k_end, out, lse), lambda L, stream: L.dga_mla_fwd_dense(
+        q.data_ptr(), kv.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(), m, heads, s, kv_stride, float(sm_scale),
+        _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
+    return out, lse
 
 
 SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values

@@ -1229,6 +1229,35 @@ int dga_indexer_kl_loss_dense(const void *q, const void *kv, const int32_t *ks, 
                               double grad_scale, float *loss, float *d_logits, int64_t dl_stride, float *target, int64_t target_stride,
                               float *lse_out, void *stream);
 
+/* The main attention of the dense stage (csrc/dga_mla_dense.hip): MLA attention, forward, in the absorbed (MQA) form over EVERY key of a
+ * token's range -- the dense warm-up stage's attention, a dense-MLA layer, a prefill beyond dga_sparse_mla_fwd's list length.  No list and
+ * no gather: key n is kv row n, key (all 576 columns) and value (its first 512) of every head.
+ *   q, kv, m, heads, s, kv_stride, sm_scale: dga_sparse_mla_fwd's;  ks, ke int32 [m]: read and clamped to [0, s] on the device exactly as
+ *                 dga_fp8_mqa_logits and dga_indexer_kl_loss_dense do, hi <= lo is an empty token
+ *   over the keys n of [lo[t], hi[t]):  s_n = sm_scale sum_d q[t, h, d] kv[n, d];  lse[t, h] = ln sum_n exp(s_n)  (fp32 [m, heads], natural
+ *   log: what dga_indexer_kl_loss_dense takes as lse);  out[t, h, :] = sum_n exp(s_n - lse) kv[n, :512]  (bf16 [m, heads, 512], 16-byte
+ *   aligned).  An empty token: out = +0, lse = -inf.  Every element of out and lse is written at every call.
+ *   What kv rows may hold: a row outside EVERY token's clamped range of the call (below the smallest lo or at or above the largest hi of
+ *   the non-empty tokens) is never read and may hold anything, NaN included.  A row inside that span but outside token t's own range
+ *   contributes nothing to t provided it is finite: its weight is a selected 0, which a NaN among its value columns would not survive.
+ *   Non-finite values inside the span are outside the contract; they cause no access outside the tensors: every address comes from the
+ *   shapes and the clamped ranges.  No row >= s and no column >= 576 is read.
+ * Arithmetic: dga_sparse_mla_fwd's per tile of DGA_SPARSE_MLA_TILE consecutive rows, tile tl the rows 32 tl .. 32 tl + 31, ascending: a
+ * score is 18 chained v_mfma_f32_16x16x32_bf16 over d ascending from +0, times (float)(sm_scale log2 e); an online softmax with one rescale
+ * a tile, the running sum l of the unrounded fp32 weights, the weights rounded to bf16 (RNE) for the second product, its sums fp32 in key
+ * order; one multiplication by 1 / l at the end; lse = ln 2 (max + log2 l).  One writer per output, no atomics, every sum in an order the
+ * shapes and the ranges alone fix: two runs give the same bytes.  One launch (capturable) of ceil(m heads / 64) workgroups, everything read
+ * on the device: a captured graph follows new ranges, q and kv.
+ * flags: DGA_MLA_DENSE_LINEAR_GRID runs the workgroups in ascending order of their rows (the default is descending: under causal ranges
+ * the longest walks start first); same bits.
+ * Checks, all before the launch: DGA_E_RANGE (an unknown flag);  DGA_E_SHAPE (m < 0, heads no multiple of 16 in [16, 128], s < 1,
+ * kv_stride < 576);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (q, kv, ks, ke, out, lse);  DGA_E_ALIGN (q, kv or out not 16-byte,
+ * ks, ke or lse not 4-byte aligned, kv_stride not a multiple of 8);  DGA_E_RANGE (s + 1024 beyond int32, m heads 576 or s kv_stride beyond
+ * int64, the grid beyond int32). */
+#define DGA_MLA_DENSE_LINEAR_GRID 1
+int dga_mla_fwd_dense(const void *q, const void *kv, const int32_t *ks, const int32_t *ke, int64_t m, int heads, int64_t s,
+                      int64_t kv_stride, double sm_scale, int flags, void *out, float *lse, void *stream);
+
 /* The writer of the paged fp8 latent cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
  * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
  * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
