@@ -219,6 +219,9 @@ SIGNATURES = {
     "dga_indexer_kl_loss_dense": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int64, c_int64, c_double, c_void_p, c_void_p, c_int64, c_double,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "dga_mla_fwd_dense": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int64, c_int64, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "dga_mla_bwd_dense_workspace_bytes": (c_int64, [c_int64, c_int, c_int64]),
+    "dga_mla_bwd_dense": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int64, c_int64, c_double, c_int] + [c_void_p] * 5 + [c_int64, c_void_p,
+                                  c_int64, c_void_p]),
     "dga_sparse_mla_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "dga_sparse_mla_splits": (c_int, [c_int64, c_int, c_int64, c_int]),
     "dga_cast_mla_kv_to_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64,

@@ -2237,6 +2237,27 @@ def sparse_mla_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_
     return _smla_one_pass(False, q, kv, indices, sm_scale, d_v, index_offsets, out, lse, sync, _flags)
 
 
+def _smla_bwd_operands(q: torch.Tensor, s: int, m: int, heads: int, out, d_out, lse, dq, dkv):
+    """What a backward of the attention takes beside its forward's operands, checked: out, d_out, lse as given; dq (torch.empty when None)
+    and dkv (torch.zeros when None: it is added into).  Returns (dq, dkv, dkv_stride)."""
+    _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    _want(d_out, "d_out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
+    _want(lse, "lse", torch.float32, (m, heads))
+    if dq is None:
+        dq = torch.empty((m, heads, SPARSE_MLA_D_QK), dtype=torch.bfloat16, device=q.device)
+    else:
+        _want(dq, "dq", torch.bfloat16, (m, heads, SPARSE_MLA_D_QK))
+    if dkv is None:
+        dkv = torch.zeros((s, SPARSE_MLA_D_QK), dtype=torch.float32, device=q.device)
+    _require(dkv.dtype == torch.float32 and dkv.dim() == 2 and tuple(dkv.shape) == (s, SPARSE_MLA_D_QK),
+             "dkv must be a float32 [S, %d] tensor with kv's S = %d rows", SPARSE_MLA_D_QK, s)
+    dkv_stride = dkv.stride(0) if s > 1 else SPARSE_MLA_D_QK
+    _require(dkv.stride(1) == 1 and dkv_stride >= SPARSE_MLA_D_QK and dkv_stride % 4 == 0,
+             "dkv must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", SPARSE_MLA_D_QK, dkv_stride)
+    _require(all(x.data_ptr() % 16 == 0 for x in (out, d_out, dq, dkv)), "out, d_out, dq and dkv must be 16-byte aligned")
+    return dq, dkv, dkv_stride
+
+
 def sparse_mla_bwd(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, indices: torch.Tensor, lse: torch.Tensor,
                    sm_scale: float, d_v: int = 512, index_offsets: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
                    dkv: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2257,22 +2278,7 @@ def sparse_mla_bwd(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: 
     element are exactly summable or there is a single one.
     Returns (dq, dkv).  One launch, capturable, everything read on the device; M == 0 returns without one."""
     m, heads, _, args = _smla_problem(False, q, kv, indices, sm_scale, d_v, index_offsets)
-    s = kv.shape[0]
-    _want(out, "out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
-    _want(d_out, "d_out", torch.bfloat16, (m, heads, SPARSE_MLA_D_V))
-    _want(lse, "lse", torch.float32, (m, heads))
-    if dq is None:
-        dq = torch.empty((m, heads, SPARSE_MLA_D_QK), dtype=torch.bfloat16, device=q.device)
-    else:
-        _want(dq, "dq", torch.bfloat16, (m, heads, SPARSE_MLA_D_QK))
-    if dkv is None:
-        dkv = torch.zeros((s, SPARSE_MLA_D_QK), dtype=torch.float32, device=q.device)
-    _require(dkv.dtype == torch.float32 and dkv.dim() == 2 and tuple(dkv.shape) == (s, SPARSE_MLA_D_QK),
-             "dkv must be a float32 [S, %d] tensor with kv's S = %d rows", SPARSE_MLA_D_QK, s)
-    dkv_stride = dkv.stride(0) if s > 1 else SPARSE_MLA_D_QK
-    _require(dkv.stride(1) == 1 and dkv_stride >= SPARSE_MLA_D_QK and dkv_stride % 4 == 0,
-             "dkv must have a contiguous last dimension and a stride(0) >= %d that is a multiple of 4, got %d", SPARSE_MLA_D_QK, dkv_stride)
-    _require(all(x.data_ptr() % 16 == 0 for x in (out, d_out, dq, dkv)), "out, d_out, dq and dkv must be 16-byte aligned")
+    dq, dkv, dkv_stride = _smla_bwd_operands(q, kv.shape[0], m, heads, out, d_out, lse, dq, dkv)
     # (M == 0: the C entry returns before any launch)
     _launch("sparse_mla_bwd", (q, kv, indices, index_offsets, out, d_out, lse, dq, dkv), lambda L, stream: L.dga_sparse_mla_bwd(
         q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, _flags, out.data_ptr(), d_out.data_ptr(),
@@ -2417,6 +2423,45 @@ def mla_fwd_dense(q: torch.Tensor, kv: torch.Tensor, cu_seq_len_k_start: torch.T
         q.data_ptr(), kv.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(), m, heads, s, kv_stride, float(sm_scale),
         _flags, out.data_ptr(), lse.data_ptr(), stream), sync)
     return out, lse
+
+
+def mla_bwd_dense(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, cu_seq_len_k_start: torch.Tensor,
+                  cu_seq_len_k_end: torch.Tensor, lse: torch.Tensor, sm_scale: float, d_v: int = 512, dq: Optional[torch.Tensor] = None,
+                  dkv: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The backward of mla_fwd_dense (dga_mla_bwd_dense): (dq, dkv) from d_out over EVERY key of a token's range -- the gradient step of a
+    dense-MLA layer, or of a warm-up step that also trains the main model.  q, kv, cu_seq_len_k_start / cu_seq_len_k_end, sm_scale and
+    d_v are mla_fwd_dense's, with its checks; the ranges are read and clamped to [0, S] on the device as the forward clamps them, ke <= ks
+    an empty token.  out, d_out, lse, dq and dkv are sparse_mla_bwd's, with its checks: out and d_out bfloat16 [M, Hq, 512], contiguous
+    and 16-byte aligned, lse float32 [M, Hq] contiguous -- out and lse normally what the forward returned;  dq bfloat16 [M, Hq, 576]
+    (torch.empty when None; every element is written);  dkv float32 [S, 576] with a contiguous last dimension, stride(0) >= 576 and a
+    multiple of 4, 16-byte aligned: ADDED INTO -- None allocates torch.zeros, a caller's tensor accumulates over calls.
+    Over the keys n of [ks[m], ke[m]), sparse_mla_bwd's formulas with "valid position j, row r_j" replaced by "key n inside the range,
+    row n":  p_n = exp(s_n - lse[m, h]);  delta = sum_c out[m, h, c] d_out[m, h, c];  dP_n = sum_c d_out[m, h, c] kv[n, c] (c < 512);
+    dS_n = sm_scale p_n (dP_n - delta);  dq[m, h, :] = sum_n dS_n kv[n, :576];  dkv[n, :576] += sum_{m, h} dS_n q[m, h, :];
+    dkv[n, :512] += sum_{m, h} p_n d_out[m, h, :].  A key outside its token's range has p = dS = +0 by a select; an empty token gets
+    dq = +0 and contributes to no row of dkv whatever its lse, out and d_out hold; a row of dkv that no token's range contains, and every
+    byte beyond column 575, keeps its bytes.  What kv rows may hold is the forward's rule: a row outside every token's range of the call
+    may hold anything and influences no output; a row inside the call's span but outside token m's own range must be finite.
+    Arithmetic: sparse_mla_bwd's per tile of 32 consecutive rows (scores and dP on the matrix pipe in fp32, p and dS rounded to bf16
+    (RNE) for the three products that follow, all sums fp32, dq rounded once at the end), so its bounds hold.  Two passes each recompute
+    the scores and every output element has one writer: there is no atomic add, and dq AND dkv are byte-reproducible -- dkv[n, c]
+    becomes fl(prior + sum), the sum over the flat rows of a chunk ascending on the matrix pipe, then over the chunks ascending, stored
+    once per element.  Returns (dq, dkv).  Three launches on the current stream (dq and delta by blocks of 32 flat rows; dkv's partial
+    tiles by key tile into scratch; their sum onto dkv), capturable, everything read on the device; M == 0 returns without one."""
+    m, heads = _smla_q(q, sm_scale, d_v)
+    s, kv_stride = _smla_bf16_rows(q, kv)
+    _want(cu_seq_len_k_start, "cu_seq_len_k_start", torch.int32, (m,))
+    _want(cu_seq_len_k_end, "cu_seq_len_k_end", torch.int32, (m,))
+    dq, dkv, dkv_stride = _smla_bwd_operands(q, s, m, heads, out, d_out, lse, dq, dkv)
+
+    def call(L, stream):
+        # (M == 0: no scratch, and the C entry returns before any launch)
+        ws_ptr, ws_bytes = _scratch("mla_bwd_dense", q.device, int(L.dga_mla_bwd_dense_workspace_bytes(m, heads, s)))
+        return L.dga_mla_bwd_dense(
+            q.data_ptr(), kv.data_ptr(), cu_seq_len_k_start.data_ptr(), cu_seq_len_k_end.data_ptr(), m, heads, s, kv_stride, float(sm_scale),
+            _flags, out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), dq.data_ptr(), dkv.data_ptr(), dkv_stride, ws_ptr, ws_bytes, stream)
+    _launch("mla_bwd_dense", (q, kv, cu_seq_len_k_start, cu_seq_len_k_end, out, d_out, lse, dq, dkv), call, sync)
+    return dq, dkv
 
 
 SPARSE_MLA_FP8_ROW_BYTES = 656       # DGA_SPARSE_MLA_FP8_ROW_BYTES: 512 e4m3fn codes, 4 float32 scales, 64 bfloat16 rope values

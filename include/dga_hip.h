@@ -1258,6 +1258,43 @@ int dga_indexer_kl_loss_dense(const void *q, const void *kv, const int32_t *ks, 
 int dga_mla_fwd_dense(const void *q, const void *kv, const int32_t *ks, const int32_t *ke, int64_t m, int heads, int64_t s,
                       int64_t kv_stride, double sm_scale, int flags, void *out, float *lse, void *stream);
 
+/* The backward of dga_mla_fwd_dense (csrc/dga_mla_dense_bwd.hip): dq and dkv from d_out, the forward's out and lse, over every key of a
+ * token's range.  No atomics: every output element has one writer, dq AND dkv are byte-reproducible.
+ *   q, kv, ks, ke, m, heads, s, kv_stride, sm_scale: dga_mla_fwd_dense's, the ranges clamped to [0, s] on the device as it clamps them,
+ *                 hi <= lo an empty token
+ *   out, d_out    bf16 [m, heads, 512] contiguous, 16-byte aligned; lse fp32 [m, heads] (natural log) -- out and lse normally the forward's
+ *   dq            bf16 [m, heads, 576] contiguous, 16-byte aligned: every element is written
+ *   dkv           fp32 [s, 576], rows dkv_stride elements apart (>= 576 and a multiple of 4), 16-byte aligned: ADDED INTO -- the caller
+ *                 zeroes it, or keeps accumulating over calls (a sequence fed in chunks of m)
+ *   workspace     dga_mla_bwd_dense_workspace_bytes(m, heads, s) bytes, 16-byte aligned: dkv's partial tiles, per key whether a range
+ *                 named it, and delta.  The size is a function of its three arguments alone (0 for an invalid shape).
+ *   over the keys n of [lo[t], hi[t]), L2E = (float)log2 e: dga_sparse_mla_bwd's formulas with "valid position j, row r_j" replaced by
+ *   "key n inside the range, row n":
+ *     p_n   = exp2(S_n (float)(sm_scale log2 e) - lse[t, h] L2E),  S_n = sum_d q[t, h, d] kv[n, d]
+ *     delta = sum_c out[t, h, c] d_out[t, h, c],  dP_n = sum_c d_out[t, h, c] kv[n, c]  (c < 512)
+ *     dS_n  = ((float)sm_scale p_n) (dP_n - delta)
+ *     dq[t, h, :] = sum_n dS_n kv[n, :576];   dkv[n, :576] += sum_{t, h} dS_n q[t, h, :];   dkv[n, :512] += sum_{t, h} p_n d_out[t, h, :]
+ *   a key outside its token's range has p = dS = +0 by a select; an empty token gets dq = +0 and contributes to no row of dkv whatever its
+ *   lse, out and d_out hold; a row of dkv that no token's range contains, and every byte beyond column 575, keeps its bytes.
+ *   What kv rows may hold: dga_mla_fwd_dense's rule -- a row outside every token's clamped range of the call influences no output, a row
+ *   inside the span but outside token t's own range must be finite; non-finite values inside the span cause no access outside the tensors.
+ * Arithmetic: dga_sparse_mla_bwd's per tile of DGA_SPARSE_MLA_TILE consecutive rows: S, dP by v_mfma_f32_16x16x32_bf16 over d ascending;
+ * delta in fp32 in its fixed order; p and dS rounded to bf16 (RNE) for the three products that follow, whose sums are fp32 on the matrix
+ * pipe: dq over the tiles ascending, one rounding to bf16 at the end; dkv over the 32-row blocks of a chunk ascending, then
+ * dkv[n, c] = fl(prior + ((p_0 + p_1) + ... + p_last)) over the chunks ascending, stored once per element.
+ * Three launches (capturable): dq and delta by blocks of 32 flat rows; dkv's partials by (key tile, chunk of blocks) -- the number of
+ * chunks follows from (m, heads, s) alone; their sum onto dkv.  Everything is read on the device.
+ * flags: none defined.
+ * Checks, all before the first launch: DGA_E_RANGE (an unknown flag);  DGA_E_SHAPE (m < 0, heads no multiple of 16 in [16, 128], s < 1,
+ * kv_stride < 576, dkv_stride < 576);  m == 0 -> DGA_OK with nothing touched;  DGA_E_NULL (any pointer but stream);  DGA_E_ALIGN (q, kv,
+ * out, d_out, dq or dkv not 16-byte, ks, ke or lse not 4-byte aligned, kv_stride not a multiple of 8, dkv_stride not of 4);  DGA_E_RANGE
+ * (s + 1024 or the blocks of 32 flat rows beyond int32, s kv_stride or s dkv_stride beyond int64, a grid beyond int32);  DGA_E_WORKSPACE
+ * (fewer bytes than dga_mla_bwd_dense_workspace_bytes, or not 16-byte aligned). */
+int64_t dga_mla_bwd_dense_workspace_bytes(int64_t m, int heads, int64_t s);
+int dga_mla_bwd_dense(const void *q, const void *kv, const int32_t *ks, const int32_t *ke, int64_t m, int heads, int64_t s,
+                      int64_t kv_stride, double sm_scale, int flags, const void *out, const void *d_out, const float *lse, void *dq,
+                      float *dkv, int64_t dkv_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The writer of the paged fp8 latent cache (csrc/dga_cast_mla_paged.hip).  kv_c [tokens, 512] and k_pe [tokens, 64], both of dtype x_dtype (DGA_DT_FP32 /
  * BF16 / FP16), rows ld_c and ld_pe elements apart (>= 512, >= 64; base and row pitch multiples of 16 bytes: two column slices of one
  * [tokens, 576] tensor are valid), slot_mapping int64 [tokens].  For every t with 0 <= slot_mapping[t] < num_blocks page_size, row slot
