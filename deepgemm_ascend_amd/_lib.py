@@ -215,6 +215,9 @@ SIGNATURES = {
     "dga_sparse_mla_fwd_partial": (c_int, _smla_args([c_int64] * 2, _SMLA_PARTIAL)),
     "dga_sparse_mla_fwd_fp8_partial": (c_int, _smla_args([c_int64] * 3, _SMLA_PARTIAL)),
     "dga_sparse_mla_bwd": (c_int, _smla_args([c_int64] * 2, _SMLA_BACKWARD)),
+    "dga_sparse_mla_bwd_det_workspace_bytes": (c_int64, [c_int64, c_int, c_int64, c_int64]),
+    # (the backward's outputs, then chunk_tokens, workspace, workspace_bytes, stream)
+    "dga_sparse_mla_bwd_det": (c_int, _smla_args([c_int64] * 2, _SMLA_BACKWARD[:-1] + [c_int64, c_void_p, c_int64, c_void_p])),
     "dga_indexer_kl_loss": (c_int, _smla_args([c_int64] * 2, _SMLA_KL_LOSS)),
     "dga_indexer_kl_loss_dense": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int64, c_int64, c_double, c_void_p, c_void_p, c_int64, c_double,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

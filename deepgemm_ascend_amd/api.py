@@ -2260,7 +2260,8 @@ def _smla_bwd_operands(q: torch.Tensor, s: int, m: int, heads: int, out, d_out, 
 
 def sparse_mla_bwd(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, indices: torch.Tensor, lse: torch.Tensor,
                    sm_scale: float, d_v: int = 512, index_offsets: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
-                   dkv: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                   dkv: Optional[torch.Tensor] = None, sync: bool = False, _flags: int = 0, deterministic: bool = False,
+                   _chunk_tokens: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The backward of sparse_mla_fwd (dga_sparse_mla_bwd): (dq, dkv) from d_out.  q, kv, indices, index_offsets, sm_scale and d_v are
     sparse_mla_fwd's, with its validity rule;  out and d_out bfloat16 [M, Hq, 512], contiguous and 16-byte aligned, lse float32 [M, Hq]
     contiguous -- out and lse normally what the forward returned;  dq bfloat16 [M, Hq, 576] (torch.empty when None; every element is
@@ -2276,9 +2277,30 @@ def sparse_mla_bwd(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, d_out: 
     Determinism: dq is byte-reproducible.  dkv is NOT -- the first output of this package that is not: the order of the atomic adds onto
     a row varies from run to run, so two runs agree to fp32 rounding of the sum, and bit for bit only where the contributions to an
     element are exactly summable or there is a single one.
-    Returns (dq, dkv).  One launch, capturable, everything read on the device; M == 0 returns without one."""
-    m, heads, _, args = _smla_problem(False, q, kv, indices, sm_scale, d_v, index_offsets)
+    Returns (dq, dkv).  One launch, capturable, everything read on the device; M == 0 returns without one.
+    deterministic=True (dga_sparse_mla_bwd_det; a bool, nothing else) is the same contract -- validity rule, index_offsets, dkv added
+    into, duplicates once per position, untouched rows and padding -- without any floating-point atomic: dq AND dkv are
+    byte-reproducible, dq the bytes of the default path.  The order of dkv's sums: the tokens go in chunks of C consecutive tokens,
+    C = max(1, min(M, 2 GiB / (topk 2304))), a function of the shapes alone; per chunk, position (m, j)'s contribution T[m, j, :]
+    (float32 [576]) is summed over ALL Hq heads on the matrix pipe from +0, head blocks of 32 ascending, and stored once by a plain
+    vector store; per kv row r, acc = +0, then acc = fl32(acc + T[m, j, c]) over the chunk's valid positions that name r in ascending
+    (m, j); then dkv[r, c] = fl32(dkv[r, c] + acc), stored once per chunk and element, chunks ascending on the stream.  That is one
+    of the orders the any-order bound of the default path covers.  1 + 7 launches a chunk on the current stream (dq; a row inverse --
+    int32 counts, scan, fill, rank; the dkv pass; the key-owned sum), scratch held per stream, capturable."""
+    m, heads, topk, args = _smla_problem(False, q, kv, indices, sm_scale, d_v, index_offsets)
     dq, dkv, dkv_stride = _smla_bwd_operands(q, kv.shape[0], m, heads, out, d_out, lse, dq, dkv)
+    _require(isinstance(deterministic, bool), "deterministic must be a bool, got %s", type(deterministic).__name__)
+    if deterministic:
+        _require(_chunk_tokens is None or (isinstance(_chunk_tokens, int) and _chunk_tokens > 0), "_chunk_tokens must be a positive int")
+
+        def call(L, stream):
+            # (M == 0: no scratch, and the C entry returns before any launch)
+            ws_ptr, ws_bytes = _scratch("sparse_mla_bwd_det", q.device, int(L.dga_sparse_mla_bwd_det_workspace_bytes(m, heads, topk, kv.shape[0])))
+            return L.dga_sparse_mla_bwd_det(
+                q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, _flags, out.data_ptr(), d_out.data_ptr(),
+                lse.data_ptr(), dq.data_ptr(), dkv.data_ptr(), dkv_stride, _chunk_tokens or 0, ws_ptr, ws_bytes, stream)
+        _launch("sparse_mla_bwd_det", (q, kv, indices, index_offsets, out, d_out, lse, dq, dkv), call, sync)
+        return dq, dkv
     # (M == 0: the C entry returns before any launch)
     _launch("sparse_mla_bwd", (q, kv, indices, index_offsets, out, d_out, lse, dq, dkv), lambda L, stream: L.dga_sparse_mla_bwd(
         q.data_ptr(), kv.data_ptr(), indices.data_ptr(), _ptr(index_offsets), *args, _flags, out.data_ptr(), d_out.data_ptr(),

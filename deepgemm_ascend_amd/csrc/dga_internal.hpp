@@ -133,4 +133,20 @@ inline int check_sparse_mla(const SmlaCall &c, const SmlaSource &src, bool outpu
     *launch = true;
     return DGA_OK;
 }
+
+// What the two backward entries (dga_sparse_mla_bwd.hip; dga_sparse_mla_bwd_det.hip) take beside SmlaCall, the checks they share in the
+// documented order, and the launch of the backward kernel: with phase C and its atomic adds onto dkv, or dq alone (dkv is not looked at).
+// Both are defined in dga_sparse_mla_bwd.hip.
+struct SmlaBwdCall {
+    SmlaCall c;
+    const void *kv;
+    int64_t s, kv_stride;
+    const void *out, *d_out;
+    const float *lse;
+    void *dq;
+    float *dkv;
+    int64_t dkv_stride;
+};
+int check_sparse_mla_bwd(const SmlaBwdCall &b, bool *launch);
+int launch_sparse_mla_bwd(const SmlaBwdCall &b, bool with_dkv);
 }  // namespace dga

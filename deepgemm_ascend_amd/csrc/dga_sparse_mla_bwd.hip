@@ -39,41 +39,9 @@
 
 namespace dga {
 
-constexpr int SMLB_HEADS = DGA_SPARSE_MLA_BWD_HEADS;         // heads of a workgroup: 32
-constexpr int SMLB_DO_ROW_BYTES = SMLA_DV * 2 + 32;          // 1056
-constexpr int SMLB_W_ROW_BYTES = SMLA_TILE * 2 + 16;         // 80: a head's 32 weights (p or dS) of the tile
-constexpr int SMLB_DTILES = SMLA_D / 16;                     // column tiles of dq and dkv: 36
-constexpr int SMLB_WAVE_TILES = SMLB_DTILES / 2;             // ... of one wave: 18
-constexpr int SMLB_GROUP = 3;                                // column tiles whose LDS reads are in flight together
-static_assert(SMLB_HEADS == SMLA_TILE && SMLB_WAVE_TILES % SMLB_GROUP == 0 && SMLB_HEADS * 8 == SMLA_THREADS && SMLA_DV % 64 == 0,
-              "the backward's geometry");
-
-typedef int32_t smlb_v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float smlb_bf16(uint32_t bits) { return __uint_as_float(bits << 16); }
-// the products of the eight bf16 pairs of two 16-byte chunks, added to `sum` in ascending order
-__device__ __forceinline__ float smlb_dot8(float sum, const uint4 &a, const uint4 &b)
-{
-    const uint32_t x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        sum = sum + smlb_bf16(x[i] & 0xFFFFu) * smlb_bf16(y[i] & 0xFFFFu);
-        sum = sum + smlb_bf16(x[i] >> 16) * smlb_bf16(y[i] >> 16);
-    }
-    return sum;
-}
-__device__ __forceinline__ uint32_t smlb_lds(const void *p)
-{
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)p;
-}
-// one 16 x 32 (or 32 x 16) bf16 fragment by two transposed reads: the blocks at `addr` and sixteen image rows (`half` bytes) below it
-__device__ __forceinline__ smla_v8bf smlb_read_tr(uint32_t addr, int half)
-{
-    const smla_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<smla_v4s __attribute__((address_space(3))) *>(addr));
-    const smla_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<smla_v4s __attribute__((address_space(3))) *>(addr + half));
-    return __builtin_bit_cast(smla_v8bf, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
+// DKV: with phase C and its atomic adds onto dkv (dga_sparse_mla_bwd); without, dq alone by the same text in the same order
+// (dga_sparse_mla_bwd_det's first pass: dkv is not looked at)
+template <bool DKV>
 __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_bwd_kernel(const uint16_t *__restrict__ q, const void *__restrict__ kv, int64_t kv_stride,
                                                                       int64_t s_rows, const int32_t *__restrict__ indices, int64_t idx_stride,
                                                                       int topk, const int32_t *__restrict__ offsets, int heads, int head_blocks,
@@ -268,7 +236,7 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_bwd_kernel(const uint
         }
 
         // ---- C ----
-        {
+        if constexpr (DKV) {
             const smla_v8bf pa = smlb_read_tr(smlb_lds(&wimg[0][0]) + wt_at, 16 * SMLB_W_ROW_BYTES);
             const smla_v8bf dsa = smlb_read_tr(smlb_lds(&wimg[1][0]) + wt_at, 16 * SMLB_W_ROW_BYTES);
             const smlb_v4i rv = *reinterpret_cast<const smlb_v4i *>(&rowidx[16 * wlo + 4 * g]);
@@ -320,34 +288,50 @@ __global__ void __launch_bounds__(SMLA_THREADS) sparse_mla_bwd_kernel(const uint
     }
 }
 
+// The forward's call and its checks first (check_sparse_mla, in the documented order), then what a backward entry adds, in the same order
+int check_sparse_mla_bwd(const SmlaBwdCall &b, bool *launch)
+{
+    const SmlaSource src{false, b.kv, b.s, 1, b.kv_stride};
+    const int rc = check_sparse_mla(b.c, src, false, nullptr, nullptr, launch);
+    if (!*launch) return rc;
+    *launch = false;
+    if (b.dkv_stride < SMLA_D) return DGA_E_SHAPE;
+    if (!b.out || !b.d_out || !b.lse || !b.dq || !b.dkv) return DGA_E_NULL;
+    if (reinterpret_cast<uintptr_t>(b.out) % 16 || reinterpret_cast<uintptr_t>(b.d_out) % 16 || reinterpret_cast<uintptr_t>(b.dq) % 16 ||
+        reinterpret_cast<uintptr_t>(b.dkv) % 16 || reinterpret_cast<uintptr_t>(b.lse) % 4 || b.dkv_stride % 4)
+        return DGA_E_ALIGN;
+    const int head_blocks = (b.c.heads + SMLB_HEADS - 1) / SMLB_HEADS;
+    if (b.c.m > (0x7FFFFFFFll - 8) / head_blocks || b.dkv_stride > 0x7FFFFFFFFFFFFFFFll / 4 / b.s) return DGA_E_RANGE;
+    *launch = true;
+    return DGA_OK;
+}
+
+int launch_sparse_mla_bwd(const SmlaBwdCall &b, bool with_dkv)
+{
+    const int head_blocks = (b.c.heads + SMLB_HEADS - 1) / SMLB_HEADS;
+    const int64_t blocks = b.c.m * head_blocks;
+    const bool linear = (b.c.flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
+    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
+    const int64_t grid = linear ? blocks : chunk * 8;
+    hipLaunchKernelGGL(with_dkv ? sparse_mla_bwd_kernel<true> : sparse_mla_bwd_kernel<false>, dim3(static_cast<unsigned>(grid)),
+                       dim3(SMLA_THREADS), 0, static_cast<hipStream_t>(b.c.stream), static_cast<const uint16_t *>(b.c.q), b.kv, b.kv_stride, b.s,
+                       b.c.indices, b.c.idx_stride, static_cast<int>(b.c.topk), b.c.index_offsets, b.c.heads, head_blocks, blocks, chunk,
+                       static_cast<float>(b.c.sm_scale * 1.4426950408889634), static_cast<float>(b.c.sm_scale),
+                       static_cast<const uint16_t *>(b.out), static_cast<const uint16_t *>(b.d_out), b.lse, static_cast<uint16_t *>(b.dq), b.dkv,
+                       b.dkv_stride);
+    return record_hip(hipGetLastError());
+}
+
 }  // namespace dga
 
-// The forward's call and its checks first (check_sparse_mla, in the documented order), then what this entry adds, in the same order
 extern "C" int dga_sparse_mla_bwd(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
                                   int64_t s, int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const void *out,
                                   const void *d_out, const float *lse, void *dq, float *dkv, int64_t dkv_stride, void *stream)
 {
     using namespace dga;
-    const SmlaCall c{q, indices, index_offsets, m, heads, topk, idx_stride, sm_scale, flags, stream};
-    const SmlaSource src{false, kv, s, 1, kv_stride};
+    const SmlaBwdCall b{{q, indices, index_offsets, m, heads, topk, idx_stride, sm_scale, flags, stream}, kv, s, kv_stride, out, d_out, lse, dq,
+                        dkv, dkv_stride};
     bool launch;
-    const int rc = check_sparse_mla(c, src, false, nullptr, nullptr, &launch);
-    if (!launch) return rc;
-    if (dkv_stride < SMLA_D) return DGA_E_SHAPE;
-    if (!out || !d_out || !lse || !dq || !dkv) return DGA_E_NULL;
-    if (reinterpret_cast<uintptr_t>(out) % 16 || reinterpret_cast<uintptr_t>(d_out) % 16 || reinterpret_cast<uintptr_t>(dq) % 16 ||
-        reinterpret_cast<uintptr_t>(dkv) % 16 || reinterpret_cast<uintptr_t>(lse) % 4 || dkv_stride % 4)
-        return DGA_E_ALIGN;
-    const int head_blocks = (heads + SMLB_HEADS - 1) / SMLB_HEADS;
-    if (m > (0x7FFFFFFFll - 8) / head_blocks || dkv_stride > 0x7FFFFFFFFFFFFFFFll / 4 / s) return DGA_E_RANGE;
-    const int64_t blocks = m * head_blocks;
-    const bool linear = (flags & DGA_SPARSE_MLA_LINEAR_GRID) != 0;
-    const int64_t chunk = linear ? 0 : (blocks + 7) / 8;
-    const int64_t grid = linear ? blocks : chunk * 8;
-    hipLaunchKernelGGL(sparse_mla_bwd_kernel, dim3(static_cast<unsigned>(grid)), dim3(SMLA_THREADS), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint16_t *>(q), kv, kv_stride, s, indices, idx_stride, static_cast<int>(topk), index_offsets, heads,
-                       head_blocks, blocks, chunk, static_cast<float>(sm_scale * 1.4426950408889634), static_cast<float>(sm_scale),
-                       static_cast<const uint16_t *>(out), static_cast<const uint16_t *>(d_out), lse, static_cast<uint16_t *>(dq), dkv,
-                       dkv_stride);
-    return record_hip(hipGetLastError());
+    const int rc = check_sparse_mla_bwd(b, &launch);
+    return launch ? launch_sparse_mla_bwd(b, true) : rc;
 }

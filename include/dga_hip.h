@@ -1174,6 +1174,34 @@ int dga_sparse_mla_bwd(const void *q, const void *kv, const int32_t *indices, co
                        int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const void *out, const void *d_out,
                        const float *lse, void *dq, float *dkv, int64_t dkv_stride, void *stream);
 
+/* dga_sparse_mla_bwd with a deterministic dkv and no floating-point atomic (csrc/dga_sparse_mla_bwd_det.hip): the same arguments, contract
+ * and per-element arithmetic, then chunk_tokens, workspace, workspace_bytes.  dq is dga_sparse_mla_bwd's byte for byte (its kernel without
+ * phase C); dq AND dkv are byte-reproducible.
+ * Order of summation.  The tokens are processed in chunks of C consecutive tokens, chunks ascending on the stream;
+ *   C = max(1, min(m, DGA_SPARSE_MLA_BWD_DET_STAGING_BYTES / (topk 2304)))  (chunk_tokens == 0), or min(m, chunk_tokens) (> 0).
+ * For a chunk and a kv row r:
+ *   T[m, j, :]  fp32 [576], position (m, j)'s contribution sum_h bf16(dS) q[m, h, :] (+ sum_h bf16(p) d_out[m, h, :] on columns < 512),
+ *               summed over ALL heads on the matrix pipe from +0, head blocks of DGA_SPARSE_MLA_BWD_HEADS ascending (in a block dS^T Q,
+ *               then P^T dO), stored once per valid position by a plain vector store into the workspace
+ *   acc = +0;  for the valid positions of the chunk that name r, in ascending (m, j):  acc = fl32(acc + T[m, j, c])
+ *   dkv[r, c] = fl32(dkv[r, c] + acc), stored once per chunk and element; a row no position of the chunk names is not touched.
+ * The order is one of the orders dga_sparse_mla_bwd's any-order bound on dkv covers, so its bounds apply unchanged.
+ * Launches (capturable, everything read on the device): dq; then per chunk the row inverse (clear, count -- int32 atomic adds, whose sums
+ * are order-free --, exclusive scan, fill through an int32 cursor, rank by counting inside a row's segment: exact for every input,
+ * quadratic in the length of a segment), the dkv pass (one workgroup a token and tile of 32 positions, looping over the head blocks) and
+ * the key-owned reduction.  No floating-point value passes through an atomic.
+ *   workspace     dga_sparse_mla_bwd_det_workspace_bytes(m, heads, topk, s) bytes (the rule's C; 0 for an invalid shape or m == 0),
+ *                 16-byte aligned: T [C, topk, 576] fp32, count / start / cursor int32 [s + 1] each, two int32 lists [C topk]
+ * Checks, all before the first launch: dga_sparse_mla_bwd's in its order, then DGA_E_SHAPE (chunk_tokens < 0, or min(m, chunk_tokens)
+ * topk beyond int32);  DGA_E_NULL (workspace);  DGA_E_ALIGN (workspace not 16-byte aligned);  DGA_E_WORKSPACE (fewer bytes than the C
+ * in force needs). */
+#define DGA_SPARSE_MLA_BWD_DET_STAGING_BYTES 2147483648ll
+int64_t dga_sparse_mla_bwd_det_workspace_bytes(int64_t m, int heads, int64_t topk, int64_t s);
+int dga_sparse_mla_bwd_det(const void *q, const void *kv, const int32_t *indices, const int32_t *index_offsets, int64_t m, int heads,
+                           int64_t s, int64_t kv_stride, int64_t topk, int64_t idx_stride, double sm_scale, int flags, const void *out,
+                           const void *d_out, const float *lse, void *dq, float *dkv, int64_t dkv_stride, int64_t chunk_tokens,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The indexer's KL loss over the selected keys and its derivative at their logits (csrc/dga_indexer_kl.hip): what dga_fp8_mqa_logits_bwd
  * takes as d_logits.  The target is the main attention's probabilities summed over the heads -- dga_sparse_mla_fwd's first product again.
  *   q, kv, indices, index_offsets, m, heads, s, kv_stride, topk, idx_stride, sm_scale, flags: dga_sparse_mla_fwd's, the validity rule too
